@@ -12,12 +12,16 @@ end_point that requires grad.  Under N>1 each rank draws differen
 is wrapped in DDP (gradient all-reduce over RCCL/xGMI, SyncBatchNorm as in the reference) and
 value = N * 8 * K / max-over-ranks(time): weak scaling.
 
-Rank 0 prints ONE JSON line; besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints it; with
+--full the line also carries what takes runs of its own:
   roofline     : the native kernel that took the most device time inside the timed region,
                  timed with events on the launch stream, against its algorithmic bytes
-                 (SURVEY.md 8d formulas) and the 8 TB/s HBM peak;
+                 (SURVEY.md 8d formulas) and the 8 TB/s HBM peak (with sa_stage, breakdown_ms_per_step,
+                 eager_ms_per_step and the measured HBM copy ceiling);
   cpu_baseline : the same model on the CPU oracle ("port"), timed on a bounded sample on rank 0
                  at N=1 only -- a reported baseline, not a target.
+--dump-outputs DIR writes what the last timed step computed (loss, end_points, parameter gradients) as
+DIR/<name>.npy, so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import collections
@@ -75,11 +79,17 @@ def parse():
     ap.add_argument("--loss-scale", type=float, default=0.0,
                     help="the loss is multiplied by this before backward (what torch.amp.GradScaler does for fp16: a mean "
                          "over 1e5 elements hands every element a gradient below fp16's normal range); 0 = 16384 for fp16, 1 otherwise")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline, the event-timed eager steps after the timed region "
+                         "(roofline, sa_stage, breakdown_ms_per_step, eager_ms_per_step) and the HBM copy ceiling")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, end_points, parameter gradients) "
+                         "as DIR/<name>.npy in float32 / float64; arrays larger than a fixed cap are a seeded sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-sample-scenes", type=int, default=0, help="scenes per CPU-baseline step (0: the batch size)")
     ap.add_argument("--cpu-steps", type=int, default=3, help="timed CPU-baseline steps (after one warm-up)")
     ap.add_argument("--cpu-threads", type=int, default=32, help="thread count tried next to 'all cores'")
-    ap.add_argument("--no-op-timing", action="store_true")
+    ap.add_argument("--no-op-timing", action="store_true", help="--full without the event-timed eager steps")
     ap.add_argument("--sa-markers", action="store_true",
                     help="measurement runs under rocprofv3 only: bracket every SA-stage span with one-wave marker kernels "
                          "(sa_fused.SPAN_MARKERS) so that tools/sa_replay_timing.py can sum the stage's kernels inside the "
@@ -110,7 +120,12 @@ def parse():
                     help="means (headline, SURVEY 8d): sum of the means of every float output; supervised (SURVEY 8f-2): "
                          "the reference's get_loss (models/loss_helper_pq.py:412-486, physical-constraint term included) on "
                          "synthetic labels in the data loader's format, computed by the HIP row kernels")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.breakdown and not (args.full and not args.no_op_timing):
+        ap.error("--breakdown prints the event-timed steps of --full (without --no-op-timing)")
+    return args
 
 
 class LossConfig:
@@ -445,6 +460,35 @@ def stage_breakdown(table, steps):
     return {k: round(v, 3) for k, v in groups.items()}
 
 
+DUMP_BYTES = 64_000_000        # --dump-outputs: all files together, .npy headers included
+DUMP_SAMPLE = 1 << 16          # elements kept of a larger array (halved while the files would not fit DUMP_BYTES)
+NPY_HEADER = 128               # bytes of np.save's header for these arrays
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every (name, tensor) as DIR/<name>.npy; float64 stays float64, other floats become float32,
+    integers and booleans float64 (exact).  An array of more than `cap` elements is replaced by `cap` of them at sorted
+    indices drawn from a generator seeded with the array's name: the same elements in every run and every build."""
+    import zlib
+
+    def itemsize(v):
+        return 8 if v.dtype == torch.float64 or not v.is_floating_point() else 4
+
+    cap = DUMP_SAMPLE
+    while sum(min(v.numel(), cap) * itemsize(v) + NPY_HEADER for _, v in arrays) > DUMP_BYTES:
+        cap //= 2
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in arrays:
+        out = v.detach()
+        if out.numel() > cap:
+            gen = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(out.numel(), (cap,), generator=gen).sort().values
+            out = out.reshape(-1)[idx.to(out.device)]
+        out = out.to(torch.float64 if itemsize(v) == 8 else torch.float32).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), out)
+    return cap
+
+
 def cpu_baseline(args):
     """The oracle-backed model (C restatement of the native ops + PyTorch CPU for the rest) on a
     bounded sample of the same workload.  Runs in THIS process before any GPU work is timed."""
@@ -720,7 +764,7 @@ def main():
         args.gpus = world
 
     cpu_rec = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_rec = cpu_baseline(args)
 
     force_dist = os.environ.get("OMNIPQ_BENCH_FORCE_DIST") == "1"      # single-rank exercise of the N>1 path
@@ -857,9 +901,21 @@ def main():
     ext.fps_check()
     if args.feeder is not None:
         args.feeder.close()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives after its last step (graph mode: the static tensors the replays rewrite);
+        # taken before --full's eager steps overwrite the gradients
+        st = args.stepper
+        arrays = [("loss", loss)]
+        arrays += [(f"end_points.{k}", v) for k, v in sorted((st.end_points or {}).items()) if torch.is_tensor(v)]
+        arrays += [(f"teacher_end_points.{k}", v) for k, v in sorted((st.teacher_end_points or {}).items())
+                   if torch.is_tensor(v)]
+        arrays += [(f"grad.{k}", p.grad) for k, p in net.named_parameters() if p.grad is not None]
+        cap = dump_outputs(args.dump_outputs, arrays)
+        print(f"bench.py: {len(arrays)} arrays of the last timed step -> {args.dump_outputs} (larger ones: a seeded sample "
+              f"of {cap} elements)", file=sys.stderr)
     timing_note = ""
     timing_steps = args.steps
-    if not args.no_op_timing:
+    if args.full and not args.no_op_timing:
         # A graph replay cannot host events (and in eager mode two events per launch cost a third of the step on the
         # host), so the per-kernel durations for the roofline are taken right after the timed region from eager
         # steps over the same batches (same kernels, same shapes; rocprofv3 of this command sees both and its

@@ -187,3 +187,32 @@ def test_bench_labels_committed_counter_figures_taken_on_other_kernel_sources():
     assert bench.counters_stale({"kernel_sources_sha1": now}) is False
     assert bench.counters_stale({"kernel_sources_sha1": "0" * 40}) is True
     assert bench.counters_stale({"total_traffic_bytes_per_step": 1.0}) is None       # summaries older than the stamp
+
+
+def test_bench_dump_outputs_writes_float_arrays_and_samples_the_same_elements(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 / float64 .npy files (integers exact as float64), small arrays whole, larger ones a
+    sample at the same indices in every run, and never more than DUMP_BYTES in all."""
+    import os
+    import numpy as np
+    import bench
+    gen = torch.Generator().manual_seed(3)
+    big = torch.randn(3, 70000, generator=gen).to(torch.bfloat16)
+    arrays = [("loss", torch.tensor(1.5)), ("end_points.inds", torch.arange(12, dtype=torch.int32).view(3, 4)),
+              ("end_points.big", big), ("grad.w", torch.randn(5, 7, generator=gen, dtype=torch.float64))]
+    cap = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert cap == bench.DUMP_SAMPLE
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in os.listdir(tmp_path / "a")}
+    assert sorted(got) == sorted(n for n, _ in arrays)
+    assert got["loss"].dtype == np.float32 and got["loss"].shape == () and float(got["loss"]) == 1.5
+    assert got["end_points.inds"].dtype == np.float64 and (got["end_points.inds"] == np.arange(12).reshape(3, 4)).all()
+    assert got["grad.w"].dtype == np.float64 and (got["grad.w"] == arrays[3][1].numpy()).all()
+    sample = got["end_points.big"]
+    assert sample.dtype == np.float32 and sample.shape == (cap,)
+    assert np.isin(sample, big.float().numpy()).all()
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    assert (np.load(tmp_path / "b" / "end_points.big.npy") == sample).all()
+    # a budget the full sample would overflow: fewer elements per large array, still within it
+    monkeypatch.setattr(bench, "DUMP_BYTES", 200_000)
+    cap = bench.dump_outputs(str(tmp_path / "c"), arrays)
+    assert cap < bench.DUMP_SAMPLE
+    assert sum(os.path.getsize(tmp_path / "c" / n) for n in os.listdir(tmp_path / "c")) <= 200_000

@@ -4,7 +4,7 @@
 # then, back in the container (gpurun_out/ has been merged):
 #     bash tools/refresh_profiles.sh r01 --collect
 # Passes (each its own process, as MI355X_MICROARCH.md prescribes: PMC never together with other traces):
-#   1. bench.py, default flags                        -> the bench line
+#   1. bench.py --full                                -> the bench line
 #   2. rocprofv3 --kernel-trace --stats, bench.py     -> per-kernel durations of the hipGraph replays
 #   3. rocprofv3 --kernel-trace --stats, --graph off  -> the same for eager launches
 #   4./5. rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE on bench.py --graph off (whole step)
@@ -18,9 +18,9 @@ OUT=$R/gpurun_out/refresh
 if [ "${2:-}" != "--collect" ]; then
   mkdir -p $OUT
   cd /tmp && export TMPDIR=/tmp
-  python $R/bench.py > $OUT/bench.log 2>&1
+  python $R/bench.py --full > $OUT/bench.log 2>&1
   tail -1 $OUT/bench.log > $OUT/bench_line.json
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/graph -o g -- python $R/bench.py --steps 8 --warmup 3 --no-cpu-baseline > $OUT/graph.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/graph -o g -- python $R/bench.py --full --steps 8 --warmup 3 --no-cpu-baseline > $OUT/graph.log 2>&1
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/eager -o e -- python $R/bench.py --graph off --steps 6 --warmup 2 --no-cpu-baseline --no-op-timing > $OUT/eager.log 2>&1
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout 900 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_$c -o pmc -- python $R/bench.py --no-cpu-baseline --no-op-timing --graph off --steps 3 --warmup 2 > $OUT/pmc_$c.log 2>&1
@@ -66,7 +66,7 @@ if [ "${2:-}" != "--collect" ]; then
   : > $OUT/other_lines.jsonl
   for F in "--mean-teacher" "--loss supervised" "--input-pipeline" "--dtype fp16 --batch 16 --points 80000 --cloud uniform" "--dtype bf16 --batch 16 --points 80000 --cloud uniform" "--batch 4 --points 50000 --extra-channels 6" "--dtype fp16" "--prefetch-at backward" "--fps-footprint fast" "--set sa_fused.ROW_PLAN=False" "--cloud uniform" "--dtype fp32"; do
     # every line carries its own event-timed roofline (never --no-op-timing for a line that goes into profiles/)
-    python $R/bench.py --no-cpu-baseline --steps 30 $F 2>/dev/null | grep "^{" | python -c "
+    python $R/bench.py --full --no-cpu-baseline --steps 30 $F 2>/dev/null | grep "^{" | python -c "
 import sys, json
 for l in sys.stdin:
     d = json.loads(l)
