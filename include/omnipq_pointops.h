@@ -41,8 +41,10 @@ extern "C" {
  *    new: omnipq_sa_last_bwd_prep, omnipq_gemm_nt_e16_dz_bnbwd, omnipq_gemm_tn_dz, omnipq_sa_last_wgrad_combine,
  *    omnipq_sa_pool_bwd_stats_sel_hot, omnipq_ipc_* (omnipq_sa.h), omnipq_ffn_fused_* (omnipq_decoder.h); timing aids
  *    omnipq_gemm_nt_small_tile_limit, omnipq_attn_block_map (results do not depend on them).
+ * 4: omnipq_row_plan lost { tickets, ticket_words } again (the in-GEMM statistics fold was slower and left the library);
+ *    omnipq_ffn_fused_* removed (never wired into the model).
  * A binding must refuse a library whose version it was not written against: the argument lists differ. */
-#define OMNIPQ_ABI_VERSION 3
+#define OMNIPQ_ABI_VERSION 4
 
 #define OMNIPQ_OK 0
 #define OMNIPQ_EINVAL 10001     /* bad shape / null pointer */

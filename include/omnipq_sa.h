@@ -31,13 +31,6 @@ typedef struct omnipq_row_plan {
   long long rows;              /* the static row count the stage's launches are issued with */
   int gs;                      /* rows per group: 8 or 16 */
   const float *pool_gamma;     /* see below; may be NULL */
-  /* Scratch of the BatchNorm-statistics folds inside the GEMMs (round 6; csrc/gemm_bf16.hip: stats_ticket_fold), may be NULL:
-   * ticket_words 32-bit words, ZERO when the first call that is handed them starts; every call leaves them zero, so calls
-   * issued one after another on ONE stream may share them.  With them a statistics GEMM over more than 8192 rows folds its
-   * per-tile partial sums itself (no reduction launch); a call needs ceil(ceil(M / 128) / 16) * ceil(N / 128) words and
-   * ignores a scratch that is too small.  Independent of the row plan: rows_dev may be NULL (every row) with tickets set. */
-  void *tickets;
-  long long ticket_words;
 } omnipq_row_plan;
 
 #endif

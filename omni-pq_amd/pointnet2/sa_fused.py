@@ -52,8 +52,7 @@ def _call(fn, anchor, *args):
 class RowPlanArg(ctypes.Structure):
     """include/omnipq_sa.h: omnipq_row_plan"""
     _fields_ = [("rows_dev", ctypes.c_void_p), ("row_w", ctypes.c_void_p), ("goff", ctypes.c_void_p),
-                ("rows", ctypes.c_longlong), ("gs", ctypes.c_int), ("pool_gamma", ctypes.c_void_p),
-                ("tickets", ctypes.c_void_p), ("ticket_words", ctypes.c_longlong)]
+                ("rows", ctypes.c_longlong), ("gs", ctypes.c_int), ("pool_gamma", ctypes.c_void_p)]
 
 
 PLAN_AWARE = _ext.PLAN_AWARE      # asked of the loaded library (omnipq_plan_aware_entry_points), not parsed from a header
@@ -288,9 +287,6 @@ _FOLD_SMALL = True
 # computation up to the order of the f32 sums (tests/test_gpu_fused_sa.py::test_row_plan_equals_the_full_stage).
 # ROW_PLAN = False: every row is computed.
 ROW_PLAN = True
-STATS_TICKETS = False           # the partial-sum statistics of the big GEMMs folded inside the GEMM instead of a partial_reduce launch: built and
-                                # measured in round 6 -- SLOWER (sa1: xyz_bnbwd 74 -> 120 us, bnaffine_pool 124 -> 143): the contended f64
-                                # atomics of 272 groups and a ticket round trip per tile cost more than the 5 us launch
 PLAN_GROUP = 8                  # rows per group of a plan: 8 or 16
 ONE_SIDED_EXTREMA = True        # planned stages with 8-row groups: record max OR min per column, by the sign of gamma
 # (A BatchNorm weight of EXACTLY zero makes every row of a ball tie after BatchNorm + ReLU; the reference's max-pool then picks
@@ -398,7 +394,6 @@ def plan_from_state(flat, B, M, P):
 class _PlanState(threading.local):       # per Python thread (forward thread / autograd thread): which plan _call passes
     arg = None                           # ctypes pointer to a RowPlanArg, or None
     struct = None
-    keep = None                          # the ticket words the struct points at
 
 
 _plan_state = _PlanState()
@@ -411,26 +406,17 @@ class _row_plan:
         self.plan, self.rows = plan, rows
 
     def __enter__(self):
-        self.prev = (_plan_state.arg, _plan_state.struct, _plan_state.keep)
-        # ticket words of the statistics folds inside the GEMMs (include/omnipq_sa.h: omnipq_row_plan.tickets): zero from the
-        # pool, shared by the block's launches (one stream, one after another; every launch leaves them zero)
-        tk, words = None, 0
-        if STATS_TICKETS and self.rows >= (1 << 13) and torch.cuda.is_available():
-            words = ((self.rows // 128 + 15) // 16 + 1) * 8
-            tk = zeros_f32(words, torch.device("cuda", torch.cuda.current_device()))
+        self.prev = (_plan_state.arg, _plan_state.struct)
         if self.plan is not None:
             st = RowPlanArg(_p(self.plan.rows_dev).value, _p(self.plan.row_w).value, _p(self.plan.goff).value, self.rows,
-                            self.plan.gs, None, _p(tk).value, words)
-        elif tk is not None:
-            st = RowPlanArg(None, None, None, self.rows, 16, None, _p(tk).value, words)
+                            self.plan.gs, None)
         else:
             st = None
         _plan_state.struct = st
         _plan_state.arg = ctypes.pointer(st) if st is not None else None
-        _plan_state.keep = tk
 
     def __exit__(self, *exc):
-        _plan_state.arg, _plan_state.struct, _plan_state.keep = self.prev
+        _plan_state.arg, _plan_state.struct = self.prev
 
 
 def _plan_pool_gamma(gamma):
@@ -518,11 +504,13 @@ last_no_dy_uses = 0
 _lib.omnipq_gemm_tn_dz_workspace_floats.restype = ctypes.c_longlong
 
 
-def last_no_dy_ok(plan, L, c2, c3, S, below_keeps_y_only):
-    """a plan with its unit map, the layer below consumed as (Y, a, b), whole 128-column tiles on both sides"""
+def last_no_dy_ok(plan, L, P, c2, c3, S, below_keeps_y_only):
+    """a plan with its unit map, the layer below consumed as (Y, a, b), whole 128-column tiles on both sides, and more
+    row tiles than the statistics take straight to f64 atomics (P rows: ceil(P / 128) > 64, as omnipq_gemm_nt_e16_dz_bnbwd
+    and the no-store omnipq_gemm_nt_e16_bnaffine_pool require)"""
     return LAST_NO_DY and c3 <= LAST_NO_DY_MAX_C3 and plan is not None and getattr(plan, "unit_src", None) is not None and L >= 2 and \
-        below_keeps_y_only and c2 % 128 == 0 and c3 % 128 == 0 and c2 + 32 <= 1024 and S >= 8 and (S & (S - 1)) == 0 and \
-        AFFINE_OPERANDS and POOL_EPILOGUE and _FOLD_SMALL
+        (P + 127) // 128 > 64 and below_keeps_y_only and c2 % 128 == 0 and c3 % 128 == 0 and c2 + 32 <= 1024 and S >= 8 and \
+        (S & (S - 1)) == 0 and AFFINE_OPERANDS and POOL_EPILOGUE and _FOLD_SMALL
 
 
 def last_wgrad_dz(Y2, below, hot, plan, S, C3, C2, P, alpha, beta, Wp, out=None):
@@ -750,21 +738,6 @@ def _refuse_ddp(wt):
             "reduce with data_parallel.GradientBuckets")
 
 
-# True: the SA stages' collected weight gradients start when their stage's backward pass ends, on a stream of their own (see
-# deferred_wgrads.flush_sa_side); False: all of them in one grouped launch when the block ends.  Measured (round 6, default
-# step): True 8.63 ms against 7.81 ms, SA stage 0.48 against 0.54 of the roofline -- five launches cut for one stage each
-# fill the chip worse than one cut for all, and what runs beside them slows down by more than the overlap gives back.
-SA_WGRAD_SIDE = False
-_SA_WGRAD_STREAMS = {}
-
-
-def _sa_wgrad_stream(device):
-    st = _SA_WGRAD_STREAMS.get(device)
-    if st is None:
-        st = _SA_WGRAD_STREAMS[device] = torch.cuda.Stream(device=device)
-    return st
-
-
 class deferred_wgrads:
     """`with deferred_wgrads(): loss.backward()` -- inside the block the rows engine does not launch the weight
     (and bias) gradient of a linear layer whose weight is a Parameter (a row range of one, or a cat_params of
@@ -793,8 +766,8 @@ class deferred_wgrads:
         return self
 
     def _note_producer(self, t):
-        """Operands are recorded on whatever stream their backward node runs on (the prediction heads have their own,
-        models/pq_transformer.py: _HEADS_SIDE); a flush waits for those streams as well."""
+        """Operands are recorded on whatever stream their backward node runs on (the decoder's key sides have their own,
+        models/decoder_rows.py: precompute_key_sides); a flush waits for those streams as well."""
         if t.is_cuda:
             self.producers.add(torch.cuda.current_stream(t.device))
 
@@ -923,22 +896,6 @@ class deferred_wgrads:
                     buf = last_wgrad_dz(Y2, below, hot, plan, S, C3, C2, P, alpha, beta, Wp)
                 assign.append((wt[1], buf.view(wt[1].shape)))
             self.__dict__.setdefault("_inflight", []).extend(todo)
-
-    def flush_sa_side(self, device):
-        """A stage's backward pass has just ended (SA_WGRAD_SIDE): its layers' weight gradients start NOW on a side stream,
-        underneath the next stage's backward pass, instead of with every other stage's when the block ends (where they run
-        alone: 0.5 ms at the end of the step with nothing beside them).  Operands stay referenced until the block ends; the
-        stream is joined there."""
-        if not (self.sa_items or self.dz_items):
-            return
-        st = _sa_wgrad_stream(device)
-        st.wait_stream(torch.cuda.current_stream(device))
-        self._wait_producers(st)
-        streams = self.__dict__.setdefault("_side_streams", [])
-        if st not in streams:
-            streams.append(st)
-        with torch.cuda.stream(st):
-            self._flush_sa()
 
     def _flush_items(self, items):
         dev = items[0][0].device
@@ -1449,7 +1406,7 @@ class FusedSAStage(torch.autograd.Function):
                 elif l > 0 and X is None:
                     # the layer below never stored relu(bn(Y)): this GEMM rebuilds it while staging its operand
                     nody = l == L - 1 and pool is not None and layers[l - 1].fin is not None and \
-                        last_no_dy_ok(getattr(ctx, "plan", None), L, K, cout, S, True)
+                        last_no_dy_ok(getattr(ctx, "plan", None), L, P, K, cout, S, True)
                     if nody:
                         global last_no_dy_uses
                         last_no_dy_uses += 1
@@ -1553,11 +1510,7 @@ class FusedSAStage(torch.autograd.Function):
         if g_out is None:                       # the stage's output took no part in the loss
             return (None,) * ctx.n_inputs
         with _tagged("@sa", getattr(ctx, "stage_label", None)), _row_plan(getattr(ctx, "plan", None), ctx.geom[4]):
-            out = FusedSAStage._backward(ctx, g_out)
-        dfr = deferred_wgrads.active
-        if SA_WGRAD_SIDE and dfr is not None and g_out.is_cuda:
-            dfr.flush_sa_side(g_out.device)           # (outside the stage's row plan: the grouped launch carries its own)
-        return out
+            return FusedSAStage._backward(ctx, g_out)
 
     @staticmethod
     def _backward(ctx, g_out):

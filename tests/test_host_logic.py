@@ -170,6 +170,16 @@ def test_joint_params_reseat_once_and_stay_consistent():
     assert all(h.weight.grad is None for h in own.heads)
 
 
+def test_last_layer_without_dy_needs_the_row_count_the_c_side_accepts(built_lib):
+    """sa_fused.last_no_dy_ok implies what omnipq_gemm_nt_e16_dz_bnbwd and the no-store omnipq_gemm_nt_e16_bnaffine_pool
+    accept: more than 64 row tiles of 128 (P > 8192), else they return EINVAL."""
+    import types
+    import sa_fused
+    plan = types.SimpleNamespace(unit_src=object())
+    assert not sa_fused.last_no_dy_ok(plan, 3, 8192, 128, 256, 32, True)
+    assert sa_fused.last_no_dy_ok(plan, 3, 16384, 128, 256, 32, True)
+
+
 def test_bench_labels_committed_counter_figures_taken_on_other_kernel_sources():
     """bench.py reads HBM traffic / MFMA-busy from the counter summaries under profiles/; each carries the digest of the
     kernel sources it was measured on, and a figure from other sources is labelled stale in the JSON line."""

@@ -5,7 +5,6 @@ run
 run --set pq_transformer._WGRAD_SIDE=False
 run --set pq_transformer._OVERLAP_KEY_SIDE=never
 run --set pq_transformer._KEY_SIDE_EARLY=False
-run --set pq_transformer._HEADS_SIDE=capture
 run --prefetch-at backward
 run --fps-footprint fast
 run --no-prefetch

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of a module switch on the replayed step:  bash tools/ab_set.sh sa_fused.SA_WGRAD_SIDE False True False True
+# A/B of a module switch on the replayed step:  bash tools/ab_set.sh sa_fused.ONE_SIDED_EXTREMA True False True False
 K=$1; shift
 for V in "$@"; do
   python bench.py --full --no-cpu-baseline --steps 40 --set $K=$V 2>/dev/null | tail -1 | \

@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """Furthest-point sampling at the benchmark's sa1 shape (8 scenes x 40 000 points -> 2048): the default kernel (8 points per
 thread) against the small-footprint variant (16 per thread, omnipq_furthest_point_sampling_ex flags), event-timed, us per
-round.  (The exact PRUNED variant of round 4 -- slower, profiles/r04_fps_pruned_vs_default.txt -- left the product library in
-round 5: tools/probe/src/fps_pruned.hip.txt.)
+round.  (The exact PRUNED variant of round 4 -- slower -- left the product library in round 5; DESIGN.md section 10 records
+it.)
 
     python tools/bench_fps.py [--batch 8] [--points 40000] [--samples 2048] [--reps 5]
 """

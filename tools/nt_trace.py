@@ -83,10 +83,6 @@ def dgrad(M, N, K):
     report(f"bnbwd {M} x {N} x {K}", timed(run), (M // 128) * ((N + 127) // 128))
 
 
-if "--ring" in sys.argv:                       # (with tools/probe/gemm_nt_ring.patch applied: the LDS-DMA ring variants)
-    lib.omnipq_nt_ring(2)
-elif "--no-ring" in sys.argv and hasattr(lib, "omnipq_nt_ring"):
-    lib.omnipq_nt_ring(0)
 if "--small" in sys.argv:                      # sa4 / vote aggregation: 32 768 grouped positions, one round of workgroups
     forward_pool(1 << 15, 512, 256, 16)
     dgrad(1 << 15, 256, 512)

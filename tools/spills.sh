@@ -1,7 +1,7 @@
 #!/bin/bash
 # Register use of the kernels of one csrc file (hipcc's kernel-resource-usage remarks): VGPRs, scratch bytes per lane,
 # occupancy, name -- only the kernels with scratch unless `all` is given.
-#     bash tools/spills.sh gemm_strip [all]
+#     bash tools/spills.sh gemm_bf16 [all]
 R=$(cd "$(dirname "$0")/.." && pwd)
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -I$R/include -c $R/omni-pq_amd/csrc/$1.hip -o /dev/null --cuda-device-only \
   -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c "
