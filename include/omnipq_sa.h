@@ -399,11 +399,13 @@ int omnipq_place_rows(long long rows, int C, const void *src, void *dst, int ldd
  *                                 X2out (may be NULL): e16 [M][lda], receives X2 = relu(a y2 + b) for omnipq_gemm_tn_dz.
  *   omnipq_gemm_tn_dz             workspace[0 .. (C3 + N) N) = R = [[a hit]^T X2 ; Gram] (f32, reduced over *slabs_out slabs),
  *                                 workspace + *cs_offset_out = float[*slabs_out][C3 + N] partial rows of cs (entries C3 ..).
- *                                 workspace: omnipq_gemm_tn_dz_workspace_floats(C3, N, P) floats.  C3, N multiples of 128.
+ *                                 workspace: omnipq_gemm_tn_dz_workspace_floats(C3, N, P) floats.
  *                                 ba == bb == NULL: the operand IS X2 (omnipq_gemm_nt_e16_dz_bnbwd's X2out), no affine.
  *   omnipq_sa_last_wgrad_combine  out f32 [C3][out_ld] (+)= dW3 from R, the cs rows, alpha, beta and the prepared weight Wp
  *                                 (e16 [C3][ldw], K-contiguous over C2).
- * All four REQUIRE the stage's plan where they take one. */
+ * Preconditions, checked by all four (OMNIPQ_EINVAL otherwise): C2 (= N) and C3 multiples of 128.  omnipq_gemm_nt_e16_dz_bnbwd
+ * and omnipq_gemm_tn_dz also REQUIRE the stage's plan with plan->rows equal to their row count (M / P), more than 64 row tiles
+ * of 128 (dz_bnbwd; the no-store omnipq_gemm_nt_e16_bnaffine_pool likewise) and nsample a power of two >= 8. */
 int omnipq_sa_last_bwd_prep(long long balls, int C3, int C2, const double *sums, double total_positions, const float *a,
                             const float *mean, const float *invstd, const float *g_out, const void *out_pm,
                             const unsigned char *arg, const void *Wt, int ldwt, unsigned *hot, void *B1, int ldb1,

@@ -1546,7 +1546,7 @@ extern "C" int omnipq_gemm_nt_e16_dz_bnbwd(int M, int N, int C3, const void *Y2,
   using namespace omnipq;
   if (M <= 0 || N <= 0 || C3 <= 0) return OMNIPQ_EINVAL;
   if (!Y2 || !B1 || !B2 || !hot || !unit_src || !C || !sums || !workspace || !a || !b || !mean || !invstd) return OMNIPQ_EINVAL;
-  if ((N % GBK) || (C3 % GBK) || (lda % 8) || (ldb1 % 8) || (ldb2 % 8) || (ldc % 8) || lda != ldc || lda < N || ldb1 < N + GBK ||
+  if ((N % 128) || (C3 % 128) || (lda % 8) || (ldb1 % 8) || (ldb2 % 8) || (ldc % 8) || lda != ldc || lda < N || ldb1 < N + GBK ||
       ldb2 < C3 || N + GBK > kAffMaxK || nsample < 8 || (nsample & (nsample - 1)))
     return OMNIPQ_EINVAL;
   const int K = N + GBK;

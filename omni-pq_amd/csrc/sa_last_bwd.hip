@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void sa_last_bwd_prep_kernel(
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const float out = (e & 1) ? e16_hi(ow[e >> 1]) : e16_lo(ow[e >> 1]);
-    const float val = out > 0.f ? av[e] * gg[e] : 0.f;               // the pooled ReLU's mask
+    const float val = av[e] * (out > 0.f ? gg[e] : 0.f);             // the pooled ReLU's mask (the same bits as _sel_hot)
     w[e] = ((unsigned)lb_bits(val) << 16) | (unsigned)((packed >> (8 * e)) & 0xFF);
   }
   uint4 *dst = reinterpret_cast<uint4 *>(hot + o);
@@ -228,7 +228,7 @@ extern "C" int omnipq_sa_last_bwd_prep(long long balls, int C3, int C2, const do
                                         const void *out_pm, const unsigned char *arg, const void *Wt, int ldwt, unsigned *hot,
                                         void *B1, int ldb1, float *alpha, float *beta, float *gb, void *stream) {
   using namespace omnipq;
-  if (balls <= 0 || C3 <= 0 || C2 <= 0 || (C3 % 64) || (C2 % 32) || !(total_positions > 0)) return OMNIPQ_EINVAL;
+  if (balls <= 0 || C3 <= 0 || C2 <= 0 || (C3 % 128) || (C2 % 128) || !(total_positions > 0)) return OMNIPQ_EINVAL;
   if (!sums || !a || !mean || !invstd || !Wt || !B1 || !alpha || !beta) return OMNIPQ_EINVAL;
   if (hot && (!g_out || !out_pm || !arg)) return OMNIPQ_EINVAL;
   if (ldwt < C3 || (ldwt % 8) || ldb1 < C2 + 32 || (ldb1 % 8)) return OMNIPQ_EINVAL;
@@ -247,7 +247,7 @@ extern "C" int omnipq_sa_last_wgrad_combine(int C3, int C2, const float *R, cons
                                              const float *alpha, const float *beta, const void *Wp, int ldw, float *out,
                                              int out_ld, int accumulate, void *stream) {
   using namespace omnipq;
-  if (C3 <= 0 || C2 <= 0 || (C3 % 32) || (C2 % 32) || slabs < 1) return OMNIPQ_EINVAL;
+  if (C3 <= 0 || C2 <= 0 || (C3 % 128) || (C2 % 128) || slabs < 1) return OMNIPQ_EINVAL;
   if (!R || !cs_part || !alpha || !beta || !Wp || !out || ldw < C2 || (ldw % 4) || out_ld < C2 || cs_ld < C3 + C2) return OMNIPQ_EINVAL;
   sa_last_wgrad_combine_kernel<<<(C3 / 32) * (C2 / 32), 256, 0, (hipStream_t)stream>>>(
       C3, C2, R, cs_part, slabs, cs_ld, alpha, beta, (const e16_t *)Wp, ldw, out, out_ld, accumulate);

@@ -494,7 +494,7 @@ def hoist_ok(training, features, cin, cin_raw, L, c1, xgen):
 # dY3 = a hit - w (alpha + beta Y3) with Y3 = X2 W3^T substituted, so that dX2 and dW3 are contractions of X2 (rebuilt from Y2
 # as everywhere), the one-hot pool gradient `hit` (generated inside the two GEMMs from one word per ball and column) and
 # C2-sized matrices.  Neither dY3 nor Y3 exists: the forward's last GEMM stores statistics and ball extrema only.
-# LAST_NO_DY = False restores the stored Y3 / dY3 (tests compare the two).
+# LAST_NO_DY = False restores the stored Y3 / dY3 (tests/test_gpu_last_no_dy.py and tests/test_gpu_fused_sa.py compare the two).
 LAST_NO_DY = True
 LAST_NO_DY_MAX_C3 = 256         # ... for last layers up to this width: sa1 (128 -> 256) gains ~20 us per step, sa2 (256 -> 512: 12 + 16
                                 # K-steps in the data-gradient GEMM, six 128 x 128 tiles per slab in the weight gradient) LOSES

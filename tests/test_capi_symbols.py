@@ -114,3 +114,60 @@ def test_argument_validation_needs_no_gpu(built_lib):
     assert lib.omnipq_gemm_nt_e16(0, 128, 32, p, 32, p, 32, p, 128, null, null) == 0
     assert lib.omnipq_interp_rows(0, 10, 5, 64, p, p, p, p, 64, 0, null) == 0
     assert lib.omnipq_relu_dropout(ll(0), p, f(0.0), null, 0, null) == 0
+
+
+def test_last_layer_route_rejects_the_shapes_it_does_not_compute(built_lib):
+    """The entry points of a planned stage's last-layer backward without dY3 (include/omnipq_sa.h) check the
+    preconditions their header states before they touch the device: C2 and C3 multiples of 128 (all four), the stage's plan with
+    their row count (dz_bnbwd, tn_dz), more than 64 row tiles (dz_bnbwd, the no-store forward), nsample a power of two."""
+    import sa_fused
+    lib = capi.lib()
+    EINVAL = 10001
+    p = ctypes.c_void_p(0x1000)                       # never dereferenced: every call below is rejected first
+    null = ctypes.c_void_p(0)
+    ll, d, f = ctypes.c_longlong, ctypes.c_double, ctypes.c_float
+    P, S = 10240, 32
+
+    def plan(rows):
+        return ctypes.pointer(sa_fused.RowPlanArg(0x1000, 0x1000, 0x1000, rows, 8, None))
+
+    def prep(C3, C2, hot=null, g=null):
+        return lib.omnipq_sa_last_bwd_prep(ll(P // S), C3, C2, p, d(float(P)), p, p, p, g, g, g, p, C3, hot, p, C2 + 32, p, p,
+                                           null, null)
+
+    def dz(M, N, C3, nsample=S, pl=None):
+        pl = plan(M) if pl is None else pl
+        return lib.omnipq_gemm_nt_e16_dz_bnbwd(M, N, C3, p, N, p, N + 32, p, C3, p, p, nsample, p, N, p, p, p, p, p, p, null,
+                                               pl, null)
+
+    def tn(C3, N, P_, nsample=S, pl=None):
+        pl = plan(P_) if pl is None else pl
+        slabs, off = ctypes.c_int(0), ctypes.c_longlong(0)
+        return lib.omnipq_gemm_tn_dz(C3, N, P_, p, N, null, null, p, p, nsample, p, ctypes.byref(slabs), ctypes.byref(off), pl,
+                                     null)
+
+    def combine(C3, C2):
+        return lib.omnipq_sa_last_wgrad_combine(C3, C2, p, p, 1, C3 + C2, p, p, p, C2, p, C2, 0, null)
+
+    for C3, C2 in ((192, 128), (256, 160), (64, 128), (128, 96), (256, 32)):
+        assert prep(C3, C2) == EINVAL, ("prep", C3, C2)
+        assert dz(P, C2, C3) == EINVAL, ("dz_bnbwd", C3, C2)
+        assert tn(C3, C2, P) == EINVAL, ("tn_dz", C3, C2)
+        assert combine(C3, C2) == EINVAL, ("combine", C3, C2)
+    assert prep(256, 128, hot=p) == EINVAL                                            # hot without g_out / out_pm / arg
+    assert dz(P, 128, 256, nsample=48) == EINVAL and tn(256, 128, P, nsample=48) == EINVAL      # nsample not a power of two
+    assert dz(P, 128, 256, nsample=4) == EINVAL and tn(256, 128, P, nsample=4) == EINVAL
+    assert dz(P, 128, 256, pl=null) == EINVAL and tn(256, 128, P, pl=null) == EINVAL            # no plan
+    assert dz(P, 128, 256, pl=plan(P + 128)) == EINVAL                                  # a plan of another row count
+    assert tn(256, 128, P, pl=plan(P - 128)) == EINVAL                                  # rows != P
+    assert dz(8192, 128, 256) == EINVAL                                                 # 64 row tiles: m_tiles <= 64
+    # the no-store forward (C = NULL) on 64 row tiles
+    assert lib.omnipq_gemm_nt_e16_bnaffine_pool(8192, 256, 128, p, 128, p, d(8192.0), p, p, f(1e-5), f(0.1), null, null, null,
+                                                p, p, p, p, p, 128, null, 256, null, p, p, 8, p, p, p, p, plan(8192),
+                                                null) == EINVAL
+    # ... and the host sends the route nothing else (sa_fused.last_no_dy_ok)
+    import types
+    pl = types.SimpleNamespace(unit_src=object())
+    assert sa_fused.last_no_dy_ok(pl, 3, P, 128, 256, S, True)
+    assert not sa_fused.last_no_dy_ok(pl, 3, P, 160, 256, S, True) and not sa_fused.last_no_dy_ok(pl, 3, P, 128, 192, S, True)
+    assert not sa_fused.last_no_dy_ok(pl, 3, 8192, 128, 256, S, True)

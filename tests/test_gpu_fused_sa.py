@@ -1045,3 +1045,78 @@ def test_first_layer_on_the_source_points_equals_the_grouped_first_layer(case, m
         assert e < 2e-2, (k, e)
     for k in grouped[3]:
         assert rel_l2(hoisted[3][k], grouped[3][k]) < 1e-4, k
+
+
+@pytest.mark.parametrize("case", ["sa1_coordinates_only", "six_extra_channels", "plan_group_16", "deferred_grouped",
+                                  "last_x2_off", "force_collectives", "sa2_feature_gradient", "fp16"])
+def test_last_layer_without_dy_equals_the_stored_route(case, monkeypatch):
+    """sa_fused.LAST_NO_DY on one stage, on and off from the same state: the route engages exactly when on, the
+    forward is the same bits (it only stores less: outputs, pooled indices, running statistics), and every gradient is as close
+    to the f32 op-by-op composition (OMNIPQ_SA=composed) as the stored-dY3 route's -- at most 1.25 times its rel-L2 plus one
+    e16 rounding.  Cases: sa1 at 2 x 40 000 points, six extra input channels, 16-row plan groups, inside deferred_wgrads, the
+    weight gradient on Y2 with the affine (LAST_X2 = False), the SyncBatchNorm branch without a process group
+    (_FORCE_COLLECTIVES: gb = NULL, statistics "all-reduced"), sa2 on the route (LAST_NO_DY_MAX_C3 = 1 << 30) with a feature
+    gradient, fp16."""
+    import pointnet2_modules
+    import sa_fused
+    dtype = torch.float16 if case == "fp16" else torch.bfloat16
+    g_scale = 1024.0 if dtype == torch.float16 else 1.0
+    cin = 6 if case == "six_extra_channels" else 0
+    spec = dict(npoint=2048, radius=0.2, nsample=64, mlp=[cin, 128, 128, 256], use_xyz=True, normalize_xyz=True)
+    B, n, feat_grad = 2, 40000, False
+    if case == "sa2_feature_gradient":
+        cin, B, n, feat_grad = 256, 8, 2048, True
+        spec = dict(npoint=1024, radius=0.4, nsample=32, mlp=[cin, 256, 256, 512], use_xyz=True, normalize_xyz=True)
+        monkeypatch.setattr(sa_fused, "LAST_NO_DY_MAX_C3", 1 << 30)
+    if case == "plan_group_16":
+        monkeypatch.setattr(sa_fused, "PLAN_GROUP", 16)
+    if case == "last_x2_off":
+        monkeypatch.setattr(sa_fused, "LAST_X2", False)
+    if case == "force_collectives":
+        monkeypatch.setattr(sa_fused, "_FORCE_COLLECTIVES", True)
+    xyz = synth.make_clouds(83, B, n, kind="room").to(dev())
+    feats = procedural_tensor("nody.feats", (B, cin, n), torch.float32).to(dev()) * 0.5 if cin else None
+
+    def run(mode):
+        mod = load_procedural(pointnet2_modules.PointnetSAModuleVotes(
+            mlp=list(spec["mlp"]), **{k: v for k, v in spec.items() if k != "mlp"}), 3).to(dev()).train()
+        with torch.no_grad():
+            for name, prm in mod.named_parameters():
+                if name.endswith("bn.bn.weight"):
+                    prm[::3] *= -1.0
+        f = None if feats is None else feats.clone().requires_grad_(feat_grad)
+        uses = sa_fused.last_no_dy_uses
+        monkeypatch.setenv("OMNIPQ_SA", "composed" if mode == "f32" else "fused")
+        monkeypatch.setattr(sa_fused, "LAST_NO_DY", mode == "on")
+        with torch.autocast("cuda", dtype=dtype, enabled=mode != "f32"):
+            _, out, inds = mod(xyz, f)
+        used = sa_fused.last_no_dy_uses - uses
+        g_up = procedural_tensor("nody.g_up", tuple(out.shape), torch.float32).to(dev()) * g_scale
+        if case == "deferred_grouped" and mode != "f32":
+            with sa_fused.deferred_wgrads() as dfr:
+                out.backward(g_up)
+                assert len(dfr.dz_items) == (1 if mode == "on" else 0)
+        else:
+            out.backward(g_up)
+        torch.cuda.synchronize()
+        grads = {k: p.grad.detach().clone() for k, p in mod.named_parameters()}
+        if feat_grad:
+            grads["features"] = f.grad.detach().clone()
+        return out.detach().clone(), inds.clone(), grads, {k: b.detach().clone() for k, b in mod.named_buffers()}, used
+
+    try:
+        want, on, off = run("f32"), run("on"), run("off")
+    finally:
+        sa_fused.E16.select(torch.bfloat16)
+    assert on[4] == 1 and off[4] == 0 and want[4] == 0
+    assert torch.equal(on[0], off[0]) and torch.equal(on[1], off[1]) and torch.equal(on[1], want[1])
+    for k in off[3]:
+        assert torch.equal(on[3][k], off[3][k]), k
+    floor = 2.0 ** -9 if dtype == torch.bfloat16 else 2.0 ** -12
+    apart_max = 1.2e-2 if dtype == torch.bfloat16 else 1.5e-3     # ~2x the largest measured (5.2e-3 bf16, 7.1e-4 fp16)
+    print(f"\n{case}: rel-L2 vs the f32 composition, without dY3 | stored dY3")
+    for k in want[2]:
+        e_on, e_off, apart = rel_l2(on[2][k], want[2][k]), rel_l2(off[2][k], want[2][k]), rel_l2(on[2][k], off[2][k])
+        print(f"  {k:40s} {e_on:.2e} | {e_off:.2e}   (routes apart {apart:.2e})")
+        assert e_on <= 1.25 * e_off + floor, (k, e_on, e_off)
+        assert apart <= apart_max, (k, apart)
