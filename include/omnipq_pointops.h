@@ -43,6 +43,7 @@ extern "C" {
  *    omnipq_gemm_nt_small_tile_limit, omnipq_attn_block_map (results do not depend on them).
  * 4: omnipq_row_plan lost { tickets, ticket_words } again (the in-GEMM statistics fold was slower and left the library);
  *    omnipq_ffn_fused_* removed (never wired into the model).
+ *    Added under 4 (additive: no existing argument list changed): omnipq_furthest_point_sampling_resume.
  * A binding must refuse a library whose version it was not written against: the argument lists differ. */
 #define OMNIPQ_ABI_VERSION 4
 
@@ -99,6 +100,18 @@ int omnipq_fps_init(void);
 #define OMNIPQ_FPS_SMALL_FOOTPRINT 1u
 int omnipq_furthest_point_sampling_ex(int b, int n, int m, const float *dataset, float *temp, int *idxs, unsigned flags,
                                       void *stream);
+/* Extension: the same sampling in pieces.  Runs the rounds [first, first + count) of the sampling of `m` points per scene
+ * (round 0 writes idxs[:,0] = 0; round j >= 1 folds pick j-1 into temp and writes idxs[:,j]); m is also the row pitch of idxs.
+ *   State between two pieces: temp (b,n) and idxs[:, 0 .. first) exactly as the previous piece left them -- nothing else, so
+ *   the pieces of one sampling may use different `flags` and different streams (the caller orders them).  The caller fills
+ *   temp with 1e10 before the piece with first == 0 and leaves it alone afterwards; a piece with first > 0 reads
+ *   idxs[:, first-1] (clamped into [0, n): a stale buffer gives wrong picks, not a stray read), and no piece reads or
+ *   writes any other column outside [first, first + count).  FPS is prefix-stable: after [0, k) the state equals that of a
+ *   sampling with m = k.
+ *   OMNIPQ_EINVAL for first < 0, count < 0, first + count > m (checked before the device is touched); count == 0 and b == 0
+ *   succeed and write nothing.  omnipq_furthest_point_sampling_ex(..., flags, stream) == ..._resume(b, n, m, 0, m, ...). */
+int omnipq_furthest_point_sampling_resume(int b, int n, int m, int first, int count, const float *dataset, float *temp,
+                                          int *idxs, unsigned flags, void *stream);
 
 /* replaces gather_points_kernel_wrapper (sampling.cpp:11-13).
  *   points (b,c,n), idx (b,npoints) -> out (b,c,npoints) */

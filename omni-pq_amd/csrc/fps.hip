@@ -8,6 +8,10 @@
 //   its shared-memory reduction tree induces (see tie_key below).
 //   If no point qualifies the round yields 0.
 //
+// A launch runs the rounds [first, end) of that loop (omnipq_furthest_point_sampling_resume): round 0 is "idx[0] = 0",
+// round j >= 1 folds pick j-1 into temp and writes pick j.  The state between two launches is (temp, idxs[0 .. first)) in
+// global memory and nothing else, so the pieces of one sampling may run in different launch shapes and on different streams.
+//
 // MI355X design (not the reference's one-block-per-scene, re-read-everything loop):
 //   * every point (x, y, z, running min-distance) lives in VGPRs for the whole kernel:
 //     HBM/L2 traffic is the compulsory 12n + 4n in, 4n + 4m out;
@@ -138,8 +142,8 @@ __device__ __forceinline__ Winner wave_winner(float d2, unsigned c, float x, flo
 // coordinates (needs 5*G <= 64 polling lanes); otherwise the chosen point is re-read from memory.
 template <int THREADS, int PPT, bool MULTI, bool XG>
 __global__ __launch_bounds__(THREADS) void fps_kernel(
-    int n, int m, int bs_mask, int G, const float *__restrict__ dataset,
-    float *__restrict__ temp, int *__restrict__ idxs,
+    int n, int m, int first, int end, int bs_mask, int G, const float *__restrict__ dataset,
+    float *__restrict__ temp, int *__restrict__ idxs,    // m: row pitch of idxs; rounds [first, end), 0 <= first < end <= m
     unsigned long long *__restrict__ slots,  // [2][scenes][5][G] {value, tag} granules (MULTI only)
     int *__restrict__ err_word, int scene0, int spin_limit, int nscenes_multi) {
   constexpr int NW = THREADS / 64;
@@ -206,17 +210,29 @@ __global__ __launch_bounds__(THREADS) void fps_kernel(
   // put a global-load wait on the critical path of EVERY round.
   const float x0 = dataset[0], y0 = dataset[1], z0 = dataset[2];
   float x1 = x0, y1 = y0, z1 = z0;
-  if (tid == 0) s_idx[0] = 0;
+  if (first == 0) {
+    if (tid == 0) s_idx[0] = 0;
+  } else {
+    // resumed: the previous pick comes out of the caller's buffer, once per launch.  Clamped before it is an address: a stale
+    // buffer gives wrong picks, never an out-of-bounds read.
+    int kp = idxs[first - 1];
+    kp = kp < 0 ? 0 : (kp >= n ? n - 1 : kp);
+    x1 = dataset[kp * 3 + 0];
+    y1 = dataset[kp * 3 + 1];
+    z1 = dataset[kp * 3 + 2];
+  }
+  const int j0 = first > 1 ? first : 1;        // this launch's first round of the loop
 
   const unsigned my_xcc = MULTI ? xcc_id() : 0u;
   bool same_xcd = false;               // wave 0 (MULTI): the hand-offs of rounds >= 2 go through this XCD's L2
   unsigned peer_xcc = 0;
-  for (int j = 1; j < m; ++j) {
+  for (int j = j0; j < end; ++j) {
     const int par = j & 1;
-    if ((j & (IDXBUF - 1)) == 0) {      // flush picks j-1024 .. j-1
+    if ((j & (IDXBUF - 1)) == 0) {      // flush picks j-1024 .. j-1 (a launch that began inside the window: from `first`)
       __syncthreads();
       if (g == 0)
-        for (int t = tid; t < IDXBUF; t += THREADS) idxs[j - IDXBUF + t] = s_idx[t];
+        for (int t = tid; t < IDXBUF; t += THREADS)
+          if (j - IDXBUF + t >= first) idxs[j - IDXBUF + t] = s_idx[t];
       __syncthreads();
     }
     FPS_STAMP(0);
@@ -309,8 +325,8 @@ __global__ __launch_bounds__(THREADS) void fps_kernel(
       if (wave == 0) {
         const Winner gw = wave_winner<true>(slot4.x, __builtin_bit_cast(unsigned, slot4.y), slot4.z, slot4.w, slotz);
         FPS_STAMP(4);
-        // rounds start at 1, slots start zeroed.  The tag also carries the writer's XCD: round 1 goes through memory
-        // (agent scope, right wherever the workgroups are) and tells every workgroup of the scene whether all of them share
+        // rounds start at 1, slots start zeroed.  The tag also carries the writer's XCD: the launch's FIRST round (round 1, or
+        // `first` of a resumed launch) goes through memory (agent scope, right wherever the workgroups are) and tells every workgroup of the scene whether all of them share
         // an XCD (the launch deals them that way, see above; verified here rather than assumed); the later rounds then
         // hand off through that XCD's L2
         const unsigned tag = (unsigned)j | (my_xcc << 24);
@@ -351,7 +367,7 @@ __global__ __launch_bounds__(THREADS) void fps_kernel(
             }
             __builtin_amdgcn_s_sleep(1);
           }
-          if (j == 1 && !failed) same_xcd = __all(lane >= npoll || peer_xcc == my_xcc);
+          if (j == j0 && !failed) same_xcd = __all(lane >= npoll || peer_xcc == my_xcc);
           const unsigned cval = (unsigned)__shfl((int)myval, lane + G);   // tie key of workgroup `lane`
           if (lane < G && !failed) {
             fd2 = __builtin_bit_cast(float, myval);
@@ -424,8 +440,8 @@ __global__ __launch_bounds__(THREADS) void fps_kernel(
   }
   __syncthreads();
   if (g == 0) {
-    const int done = ((m - 1) / IDXBUF) * IDXBUF;       // first pick not flushed yet
-    for (int t = done + tid; t < m; t += THREADS) idxs[t] = s_idx[t - done];
+    const int done = ((end - 1) / IDXBUF) * IDXBUF;     // first pick not flushed yet
+    for (int t = (done > first ? done : first) + tid; t < end; t += THREADS) idxs[t] = s_idx[t - done];
   }
 
 #pragma unroll
@@ -453,8 +469,9 @@ __device__ __forceinline__ int wave_slot_point(int j, int r_log2, int ppt_log2, 
 }
 
 template <int PPT>
-__global__ __launch_bounds__(64) void fps_wave_kernel(int n, int m, int bs_mask, const float *__restrict__ dataset,
-                                                      float *__restrict__ temp, int *__restrict__ idxs) {
+__global__ __launch_bounds__(64) void fps_wave_kernel(int n, int m, int first, int end, int bs_mask,
+                                                      const float *__restrict__ dataset, float *__restrict__ temp,
+                                                      int *__restrict__ idxs) {
   constexpr int PPT_LOG2 = PPT == 16 ? 4 : (PPT == 8 ? 3 : 2);
   const int lane = (int)threadIdx.x;
   const int scene = (int)blockIdx.x;
@@ -481,8 +498,16 @@ __global__ __launch_bounds__(64) void fps_wave_kernel(int n, int m, int bs_mask,
   }
   const float x0 = dataset[0], y0 = dataset[1], z0 = dataset[2];
   float x1 = x0, y1 = y0, z1 = z0;
-  if (lane == 0) idxs[0] = 0;
-  for (int jr = 1; jr < m; ++jr) {
+  if (first == 0) {
+    if (lane == 0) idxs[0] = 0;
+  } else {
+    int kp = idxs[first - 1];                  // resumed: see fps_kernel
+    kp = kp < 0 ? 0 : (kp >= n ? n - 1 : kp);
+    x1 = dataset[kp * 3 + 0];
+    y1 = dataset[kp * 3 + 1];
+    z1 = dataset[kp * 3 + 2];
+  }
+  for (int jr = first > 1 ? first : 1; jr < end; ++jr) {
     float bd2 = -1.f;
     int bi = 0;
 #pragma unroll
@@ -599,16 +624,16 @@ static int fps_resident_blocks() {
 }
 
 template <int THREADS, int PPT>
-static int launch_single(int b, int n, int m, int bs_mask, const float *dataset, float *temp,
+static int launch_single(int b, int n, int m, int first, int end, int bs_mask, const float *dataset, float *temp,
                          int *idxs, hipStream_t stream) {
-  fps_kernel<THREADS, PPT, false, false><<<b, THREADS, 0, stream>>>(n, m, bs_mask, 1, dataset, temp, idxs,
+  fps_kernel<THREADS, PPT, false, false><<<b, THREADS, 0, stream>>>(n, m, first, end, bs_mask, 1, dataset, temp, idxs,
                                                                     nullptr, nullptr, 0, 0, 0);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }
 
 template <int PPT>
-static int launch_multi(int b, int n, int m, int bs_mask, int G, const float *dataset, float *temp,
+static int launch_multi(int b, int n, int m, int first, int end, int bs_mask, int G, const float *dataset, float *temp,
                         int *idxs, hipStream_t stream) {
   constexpr int THREADS = 1024;
   // all G workgroups of a scene must be co-resident: what the occupancy query says the device holds, minus an
@@ -626,10 +651,10 @@ static int launch_multi(int b, int n, int m, int bs_mask, int G, const float *da
     OMNIPQ_HIP(hipMemsetAsync(ws->slots, 0, (size_t)2 * ns * 5 * G * sizeof(unsigned long long), stream));
     if (5 * G <= 64)
       fps_kernel<THREADS, PPT, true, true><<<8 * G * ((ns + 7) / 8), THREADS, 0, stream>>>(
-          n, m, bs_mask, G, dataset, temp, idxs, ws->slots, ws->err, s0, 1 << 22, ns);
+          n, m, first, end, bs_mask, G, dataset, temp, idxs, ws->slots, ws->err, s0, 1 << 22, ns);
     else
       fps_kernel<THREADS, PPT, true, false><<<8 * G * ((ns + 7) / 8), THREADS, 0, stream>>>(
-          n, m, bs_mask, G, dataset, temp, idxs, ws->slots, ws->err, s0, 1 << 22, ns);
+          n, m, first, end, bs_mask, G, dataset, temp, idxs, ws->slots, ws->err, s0, 1 << 22, ns);
     OMNIPQ_LAUNCH_CHECK();
   }
   return OMNIPQ_OK;
@@ -703,13 +728,13 @@ extern "C" int omnipq_fps_check(void *stream) {
   return omnipq_fps_poll();
 }
 
-extern "C" int omnipq_furthest_point_sampling_ex(int b, int n, int m, const float *dataset, float *temp, int *idxs,
-                                                 unsigned flags, void *stream_);
+extern "C" int omnipq_furthest_point_sampling_resume(int b, int n, int m, int first, int count, const float *dataset,
+                                                     float *temp, int *idxs, unsigned flags, void *stream_);
 
 // The reference-shaped entry point (sampling.cpp:11-20 + stream): the fastest rounds.
 extern "C" int omnipq_furthest_point_sampling(int b, int n, int m, const float *dataset, float *temp, int *idxs,
                                               void *stream_) {
-  return omnipq_furthest_point_sampling_ex(b, n, m, dataset, temp, idxs, 0u, stream_);
+  return omnipq_furthest_point_sampling_resume(b, n, m, 0, m, dataset, temp, idxs, 0u, stream_);
 }
 
 // flags: OMNIPQ_FPS_SMALL_FOOTPRINT (bit 0) -- clouds of more than 8192 points are sampled with 16 points per thread on
@@ -717,33 +742,42 @@ extern "C" int omnipq_furthest_point_sampling(int b, int n, int m, const float *
 // ends before it).  An explicit argument: no per-thread mode (round 5; was omnipq_fps_footprint).
 extern "C" int omnipq_furthest_point_sampling_ex(int b, int n, int m, const float *dataset, float *temp, int *idxs,
                                                  unsigned flags, void *stream_) {
+  return omnipq_furthest_point_sampling_resume(b, n, m, 0, m, dataset, temp, idxs, flags, stream_);
+}
+
+// Rounds [first, first + count) of the sampling of m points per scene: the whole sampling is (0, m); a piece with first > 0
+// continues from (temp, idxs[:, :first]) as an earlier piece left them.  `flags` as above, per piece.
+extern "C" int omnipq_furthest_point_sampling_resume(int b, int n, int m, int first, int count, const float *dataset,
+                                                     float *temp, int *idxs, unsigned flags, void *stream_) {
   const bool t_small_footprint = (flags & 1u) != 0;
   using namespace omnipq;
   hipStream_t stream = (hipStream_t)stream_;
-  if (b < 0 || n < 0 || m < 0) return OMNIPQ_EINVAL;
-  if (b == 0 || m == 0) return OMNIPQ_OK;  // sampling_gpu.cu:78  `if (m <= 0) return;`
+  if (b < 0 || n < 0 || m < 0 || first < 0 || count < 0) return OMNIPQ_EINVAL;
+  if ((long long)first + count > m) return OMNIPQ_EINVAL;
+  if (b == 0 || count == 0) return OMNIPQ_OK;  // sampling_gpu.cu:78  `if (m <= 0) return;`
   if (n == 0) return OMNIPQ_EINVAL;
   if (!dataset || !temp || !idxs) return OMNIPQ_EINVAL;
   if (n > (1 << kKBits)) return OMNIPQ_ETOOLARGE;
   const int bs_mask = omnipq_opt_n_threads(n) - 1;
+  const int end = first + count;
 
-  if (n <= 256) return launch_single<256, 1>(b, n, m, bs_mask, dataset, temp, idxs, stream);
+  if (n <= 256) return launch_single<256, 1>(b, n, m, first, end, bs_mask, dataset, temp, idxs, stream);
   // (measured per round at b = 8: 512 threads x 1-2 points beat 256 x 2-4 by ~7 %, 64-128 threads x 8-16 are
   // 25-65 % slower, 1024 x 1 is slower again: the per-lane update is short, the block argmax grows with waves)
   // 256 < n <= 1024: one wave per scene (fps_wave_kernel); bs = 256 / 512 / 1024 = 64 r with r <= PPT
   if (n <= 512) {
-    fps_wave_kernel<8><<<b, 64, 0, stream>>>(n, m, bs_mask, dataset, temp, idxs);
+    fps_wave_kernel<8><<<b, 64, 0, stream>>>(n, m, first, end, bs_mask, dataset, temp, idxs);
     OMNIPQ_LAUNCH_CHECK();
     return OMNIPQ_OK;
   }
   if (n <= 1024) {
-    fps_wave_kernel<16><<<b, 64, 0, stream>>>(n, m, bs_mask, dataset, temp, idxs);
+    fps_wave_kernel<16><<<b, 64, 0, stream>>>(n, m, first, end, bs_mask, dataset, temp, idxs);
     OMNIPQ_LAUNCH_CHECK();
     return OMNIPQ_OK;
   }
-  if (n <= 2048) return launch_single<512, 4>(b, n, m, bs_mask, dataset, temp, idxs, stream);
-  if (n <= 4096) return launch_single<1024, 4>(b, n, m, bs_mask, dataset, temp, idxs, stream);
-  if (n <= 8192) return launch_single<1024, 8>(b, n, m, bs_mask, dataset, temp, idxs, stream);
+  if (n <= 2048) return launch_single<512, 4>(b, n, m, first, end, bs_mask, dataset, temp, idxs, stream);
+  if (n <= 4096) return launch_single<1024, 4>(b, n, m, first, end, bs_mask, dataset, temp, idxs, stream);
+  if (n <= 8192) return launch_single<1024, 8>(b, n, m, first, end, bs_mask, dataset, temp, idxs, stream);
   // several workgroups per scene, every point visited every round
   // up to 12 workgroups the exchange also carries the winner's coordinates (5*G polling lanes)
   const int per4 = 1024 * 4, per8 = 1024 * 8;
@@ -756,12 +790,12 @@ extern "C" int omnipq_furthest_point_sampling_ex(int b, int n, int m, const floa
     // 2.6 us: 16 distance updates per lane in front of the same exchange), the chain occupies 24 instead of 40 CUs -- for a
     // chain that runs underneath a whole training step and ends well before it (omnipq_fps_footprint)
     const int G16 = (n + 1024 * 16 - 1) / (1024 * 16);
-    if (G16 <= 12) return launch_multi<16>(b, n, m, bs_mask, G16, dataset, temp, idxs, stream);
+    if (G16 <= 12) return launch_multi<16>(b, n, m, first, end, bs_mask, G16, dataset, temp, idxs, stream);
   }
-  if (prefer8 && G8 <= 12) return launch_multi<8>(b, n, m, bs_mask, G8, dataset, temp, idxs, stream);
-  if (G4 <= 12) return launch_multi<4>(b, n, m, bs_mask, G4, dataset, temp, idxs, stream);
-  if (G8 <= 12) return launch_multi<8>(b, n, m, bs_mask, G8, dataset, temp, idxs, stream);
-  if (G4 <= 32) return launch_multi<4>(b, n, m, bs_mask, G4, dataset, temp, idxs, stream);
-  if (G8 <= 64) return launch_multi<8>(b, n, m, bs_mask, G8, dataset, temp, idxs, stream);
+  if (prefer8 && G8 <= 12) return launch_multi<8>(b, n, m, first, end, bs_mask, G8, dataset, temp, idxs, stream);
+  if (G4 <= 12) return launch_multi<4>(b, n, m, first, end, bs_mask, G4, dataset, temp, idxs, stream);
+  if (G8 <= 12) return launch_multi<8>(b, n, m, first, end, bs_mask, G8, dataset, temp, idxs, stream);
+  if (G4 <= 32) return launch_multi<4>(b, n, m, first, end, bs_mask, G4, dataset, temp, idxs, stream);
+  if (G8 <= 64) return launch_multi<8>(b, n, m, first, end, bs_mask, G8, dataset, temp, idxs, stream);
   return OMNIPQ_ETOOLARGE;
 }

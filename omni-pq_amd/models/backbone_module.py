@@ -63,14 +63,106 @@ class Pointnet2Backbone(nn.Module):
         # streams, events and the plan's index buffers are per-instance run-time state: copies and pickles of
         # the module (copy.deepcopy for an EMA teacher, torch.save of the whole model) start without them
         state = self.__dict__.copy()
-        for k in ("_plan", "_side", "_plan_bufs", "_extra", "_pending"):
+        for k in ("_plan", "_side", "_plan_bufs", "_extra", "_pending", "_head_side", "_head", "_tail"):
             state.pop(k, None)
         return state
 
+    @staticmethod
+    def _new_stream(device, avoid=()):
+        """A stream for a sampling chain that is neither one of `avoid` nor the stream torch captures graphs on.  torch
+        hands streams out of a pool of 32 per device, round-robin: a new Stream object can BE an earlier one.  The plan of the
+        first captured batch is launched before the capture and its events are waited for inside it; when the sampling stream
+        is the capture stream itself that wait is refused (hipErrorStreamCaptureIsolation: the event's stream is capturing,
+        the event is not part of the capture) and the capture is lost."""
+        taken = {s.cuda_stream for s in avoid if s is not None}
+        cap = getattr(torch.cuda.graph, "default_capture_stream", None)
+        if cap is not None:
+            taken.add(cap.cuda_stream)
+        stream = torch.cuda.Stream(device=device)
+        for _ in range(64):
+            if stream.cuda_stream not in taken:
+                break
+            stream = torch.cuda.Stream(device=device)
+        return stream
+
     def _side_stream(self, device):
         if self._side is None or self._side.device != device:
-            self._side = torch.cuda.Stream(device=device)
+            self._side = self._new_stream(device, (self._head_side,))
         return self._side
+
+    # ---- the sa1 level in two pieces ------------------------------------------------------------------------------------------
+    # The sa1 level is 2047 of the chain's ~3800 dependent rounds.  Its rounds [0, k) -- the HEAD -- can run one step earlier than
+    # the rest of the chain, on a second side stream (prefetch_head), into a persistent head state (temp, idx[:, :k]); once
+    # that has been handed over (hand_over_head) a chain started with prefetch(..., resume=True) -- the TAIL -- continues the
+    # level at round k instead of sampling from 0.  Everything behind sa1's picks is the same code.  Indices are identical:
+    # _ext.furthest_point_sampling_resume continues a sampling from exactly that state.
+    _head_side = None
+    _head = None            # host record of the head in flight: {"rounds", "event", "key", "trusted"}
+    _tail = None            # ... of the handed-over state the next resumed chain continues: {"rounds", "key", "trusted"}
+    resumed_levels = 0      # sa1 levels that continued a head (launched or captured) -- for tests and A/B scripts
+
+    def _head_stream(self, device):
+        if self._head_side is None or self._head_side.device != device:
+            self._head_side = self._new_stream(device, (self._side,))
+        return self._head_side
+
+    def _split_buffers(self, pointcloud):
+        """Persistent state of the split sa1 level (one set per batch shape): head (temp, idx) and tail (temp, idx)."""
+        B, n = pointcloud.shape[0], pointcloud.shape[1]
+        key = ("split", B, n, str(pointcloud.device))
+        bufs = self.__dict__.setdefault("_plan_bufs", {})
+        if key not in bufs:
+            mk = lambda shape, dt: torch.zeros(shape, device=pointcloud.device, dtype=dt)
+            bufs[key] = {"head_temp": mk((B, n), torch.float32), "head_idx": mk((B, self.sa1.npoint), torch.int32),
+                         "tail_temp": mk((B, n), torch.float32), "tail_idx": mk((B, self.sa1.npoint), torch.int32)}
+        return bufs[key]
+
+    def prefetch_head(self, pointcloud, rounds, trusted=False, footprint="small"):
+        """Rounds [0, rounds) of the sa1 sampling of a batch TWO steps ahead, on a second side stream, into the persistent
+        head state.  hand_over_head() -- or the next prefetch(..., resume=True), which calls it when no state has been handed
+        over -- makes it the state a resumed chain continues.  trusted: as prefetch().  footprint: "small" (default) / "fast":
+        a head runs next to a tail and, with a teacher, next to two more samplings, and every multi-workgroup sampling
+        launch needs all workgroups of its scenes resident at once: the small footprint keeps four of them at 8 scenes
+        on 4 x 8 x 3 = 96 compute units instead of 160."""
+        if not pointcloud.is_cuda:
+            return
+        ext = pointnet2_utils._ext
+        if not hasattr(ext, "furthest_point_sampling_resume"):
+            raise RuntimeError("prefetch_head: this binding cannot resume a sampling")
+        npoint = self.sa1.npoint
+        rounds = int(rounds)
+        if not 1 <= rounds <= npoint:
+            raise ValueError(f"prefetch_head: rounds must be in [1, {npoint}]")
+        main = torch.cuda.current_stream(pointcloud.device)
+        side = self._head_stream(pointcloud.device)
+        side.wait_stream(main)
+        st = self._split_buffers(pointcloud)
+        if not torch.cuda.is_current_stream_capturing():
+            pointcloud.record_stream(side)
+            for t in (st["head_temp"], st["head_idx"]):
+                t.record_stream(side)
+        with torch.cuda.stream(side), torch.no_grad():
+            xyz = pointcloud[..., 0:3].contiguous()
+            st["head_temp"].fill_(1e10)
+            ext.furthest_point_sampling_resume(xyz, st["head_idx"], st["head_temp"], 0, rounds, small_footprint=footprint == "small")
+            ev = torch.cuda.Event()
+            ev.record(side)
+        self._head = {"rounds": rounds, "event": ev, "key": self._key(pointcloud), "trusted": trusted, "src": pointcloud}
+
+    def hand_over_head(self):
+        """Head state -> tail state on the current stream (temp and idx[:, :rounds]: 1.3 MB at 8 x 40 000 points), ordered
+        behind the head.  The head buffers are free for the next head afterwards."""
+        head, self._head = self._head, None
+        if head is None:
+            raise RuntimeError("hand_over_head: no head was sampled (prefetch_head)")
+        st = self._split_buffers(head["src"])
+        cur = torch.cuda.current_stream(head["src"].device)
+        cur.wait_event(head["event"])
+        k = head["rounds"]
+        with torch.no_grad():
+            st["tail_temp"].copy_(st["head_temp"])
+            st["tail_idx"][:, :k].copy_(st["head_idx"][:, :k])
+        self._tail = {"rounds": k, "key": head["key"], "trusted": head["trusted"]}
 
     @staticmethod
     def _key(xyz_src):
@@ -158,10 +250,18 @@ class Pointnet2Backbone(nn.Module):
             (extra_layout[0], flat[extra_layout[2]:extra_layout[2] + B * extra_layout[1]].view(B, extra_layout[1]))
         return out, fp_views, extra
 
-    def _launch_plan(self, pointcloud, trusted=False, small=False, group=False):
+    def _launch_plan(self, pointcloud, trusted=False, small=False, group=False, resume=False):
         """FPS chain for `pointcloud` on the side stream -> {"key", "inds": [4 x (B,npoint) int32],
         "events": [4 x Event]}; the caller's stream has to wait on events[i] before using inds[i].
-        group: also the stages' centres / ball queries / row plans (GROUP_AHEAD) -> plan["group"] = (flat buffer, event)."""
+        group: also the stages' centres / ball queries / row plans (GROUP_AHEAD) -> plan["group"] = (flat buffer, event).
+        resume: the sa1 level continues the handed-over tail state (see prefetch_head) instead of sampling from 0."""
+        tail = None
+        if resume:
+            tail, self._tail = self._tail, None
+            if tail is not None and not (tail["trusted"] or trusted or tail["key"] == self._key(pointcloud)):
+                tail = None                    # the head of some other cloud: sample this one from 0
+            if tail is not None:
+                self.resumed_levels += 1
         main = torch.cuda.current_stream(pointcloud.device)
         side = self._side_stream(pointcloud.device)
         side.wait_stream(main)
@@ -190,11 +290,20 @@ class Pointnet2Backbone(nn.Module):
             pointcloud.record_stream(side)
             for buf in bufs:
                 buf.record_stream(side)
+            if tail is not None:
+                for t in self._split_buffers(pointcloud).values():
+                    t.record_stream(side)
         with torch.cuda.stream(side), torch.no_grad():
             xyz = pointcloud[..., 0:3].contiguous()
             for li, name in enumerate(("sa1", "sa2", "sa3", "sa4")):
                 npoint = getattr(self, name).npoint
-                if hasattr(ext, "set_timing_sink"):          # the product binding: write in place
+                if li == 0 and tail is not None:
+                    # the level's rounds [k, npoint) from the tail state; the picks [0, k) move into the plan's buffer
+                    st, k = self._split_buffers(pointcloud), tail["rounds"]
+                    inds = bufs[0]
+                    inds[:, :k].copy_(st["tail_idx"][:, :k])
+                    ext.furthest_point_sampling_resume(xyz, inds, st["tail_temp"], k, npoint - k, small_footprint=small)
+                elif hasattr(ext, "set_timing_sink"):          # the product binding: write in place
                     inds = ext.furthest_point_sampling(xyz, npoint, out=bufs[li], small_footprint=small)
                 else:
                     inds = ext.furthest_point_sampling(xyz, npoint)
@@ -251,7 +360,7 @@ class Pointnet2Backbone(nn.Module):
                 plan["group"] = (gflat, g_ev, planned, glayout, sa_fused.PLAN_GROUP)
         return plan
 
-    def prefetch(self, pointcloud, trusted=False, at_next_forward=False, footprint=None):
+    def prefetch(self, pointcloud, trusted=False, at_next_forward=False, footprint=None, resume=False):
         """Start the sampling plan of a FUTURE batch now (e.g. while the current batch is in backward).
         A later forward() on the very same tensor picks the result up; any other input recomputes.
         trusted=True: the next forward() takes the plan whatever tensor it is given (the caller vouches
@@ -262,14 +371,19 @@ class Pointnet2Backbone(nn.Module):
         included, instead of the backward pass only.
         footprint: "small" runs the 40 000-point level on 3 instead of 5 compute units per scene with ~40 % longer rounds
         (_ext.furthest_point_sampling(small_footprint=True): same indices) -- right when the chain ends well before the
-        step it hides under, which is the default for at_next_forward; "fast" otherwise (e.g. two chains per step)."""
+        step it hides under, which is the default for at_next_forward; "fast" otherwise (e.g. two chains per step).
+        resume=True: the sa1 level continues at the round where prefetch_head() of this cloud stopped (the state handed over
+        by hand_over_head(); handed over here if that has not happened yet).  Without a head, or with the head of another
+        cloud, the level is sampled from 0 as usual (`resumed_levels` counts the levels that did continue one)."""
         if not pointcloud.is_cuda:
             return
         small = (footprint or ("small" if at_next_forward else "fast")) == "small"
+        if resume and self._tail is None and self._head is not None:
+            self.hand_over_head()
         if at_next_forward:
-            self._pending = (pointcloud, trusted, small, True)
+            self._pending = (pointcloud, trusted, small, True, resume)
         else:
-            self._plan = self._launch_plan(pointcloud, trusted, small, True)
+            self._plan = self._launch_plan(pointcloud, trusted, small, True, resume)
 
     def forget_plan(self):
         """Drop the HOST-side record of a plan in flight / pending (not the device work).  A captured step replays its
@@ -280,11 +394,14 @@ class Pointnet2Backbone(nn.Module):
         self._plan = None
         self._pending = None
         self._extra = None
+        self._head = None
+        self._tail = None
 
     def join(self, device=None):
-        """Make the current stream wait for everything queued on the sampling stream."""
-        if self._side is not None:
-            torch.cuda.current_stream(self._side.device).wait_stream(self._side)
+        """Make the current stream wait for everything queued on the sampling streams."""
+        for side in (self._side, self._head_side):
+            if side is not None:
+                torch.cuda.current_stream(side.device).wait_stream(side)
 
     def take_extra(self, name):
         """Indices of the plan's extra level `name` for the batch just run through forward(), or None."""

@@ -775,12 +775,22 @@ class PQ_Transformer(nn.Module):
                     seat_head_parameters(m)
         return out
 
-    def prefetch(self, inputs, trusted=False, at_next_forward=False, footprint=None):
+    def prefetch(self, inputs, trusted=False, at_next_forward=False, footprint=None, resume=False):
         """Optional: start the coordinate-only sampling (FPS chain of the backbone) of a FUTURE batch on
         a side stream; `forward` on the same `inputs['point_clouds']` tensor then skips it.  Results do
         not change (sa1's FPS depends only on the input cloud).  at_next_forward: start it inside the
-        next forward() call (of the CURRENT batch) instead of now, see Pointnet2Backbone.prefetch."""
-        self.backbone.prefetch(inputs['point_clouds'], trusted, at_next_forward, footprint)
+        next forward() call (of the CURRENT batch) instead of now, see Pointnet2Backbone.prefetch.  resume: continue the
+        sa1 level where prefetch_head() of this batch stopped."""
+        self.backbone.prefetch(inputs['point_clouds'], trusted, at_next_forward, footprint, resume)
+
+    def prefetch_head(self, inputs, rounds, trusted=False, footprint="small"):
+        """Optional: the first `rounds` rounds of the sa1 sampling of a batch TWO steps ahead, on a second side stream
+        (Pointnet2Backbone.prefetch_head); `prefetch(..., resume=True)` of that batch continues from there."""
+        self.backbone.prefetch_head(inputs['point_clouds'], rounds, trusted, footprint)
+
+    def hand_over_head(self):
+        """Make the sampled head the state the next resumed chain continues (Pointnet2Backbone.hand_over_head)."""
+        self.backbone.hand_over_head()
 
     def forget_prefetch(self):
         """Forget the host-side record of a sampling plan in flight (Pointnet2Backbone.forget_plan)."""

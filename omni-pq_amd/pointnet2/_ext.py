@@ -284,6 +284,30 @@ def furthest_point_sampling(points, nsamples, out=None, small_footprint=False):
     return out
 
 
+def furthest_point_sampling_resume(points, idx, temp, first, count, small_footprint=False):
+    """Rounds [first, first + count) of the sampling of idx.shape[1] points per scene, in place on the caller's
+    idx (B,m) i32 and temp (B,n) f32 (extension; omnipq_furthest_point_sampling_resume).  The caller fills temp with 1e10 before
+    the piece that starts at 0; the state between two pieces is (temp, idx[:, :first]) and nothing else, so every piece may
+    choose small_footprint (see furthest_point_sampling) and its stream for itself.  Returns idx."""
+    _check(points, "points", torch.float32)
+    _need_gpu(points)
+    _check(idx, "idx", torch.int32, cuda_like=points)
+    _check(temp, "temp", torch.float32, cuda_like=points)
+    _fps_prepare(points.device)
+    b, n = points.shape[0], points.shape[1]
+    if points.dim() != 3 or points.shape[2] != 3 or idx.dim() != 2 or idx.shape[0] != b or tuple(temp.shape) != (b, n):
+        raise ValueError("furthest_point_sampling_resume: points (B, N, 3), idx (B, m), temp (B, N)")
+    if idx.device != points.device or temp.device != points.device:
+        raise ValueError("furthest_point_sampling_resume: idx and temp must be on the device of points")
+    m = idx.shape[1]
+    first, count = int(first), int(count)
+    if first < 0 or count < 0 or first + count > m:
+        raise ValueError(f"furthest_point_sampling_resume: rounds [{first}, {first + count}) outside [0, {m})")
+    _run(_lib0.omnipq_furthest_point_sampling_resume, points, b, n, m, first, count, _ptr(points), _ptr(temp), _ptr(idx),
+         ctypes.c_uint(1 if small_footprint else 0))          # flags: OMNIPQ_FPS_SMALL_FOOTPRINT
+    return idx
+
+
 def three_nn(unknowns, knows):
     """(B,n,3), (B,m,3) -> [dist2 (B,n,3) squared, idx (B,n,3) i32]   [interpolate.cpp:22-48]"""
     _check(unknowns, "unknowns", torch.float32)

@@ -2,6 +2,7 @@
 `pointnet2/pointnet2_utils.py` (same callables, argument order and return conventions):
 
     furthest_point_sample(xyz, npoint)            -> (B, npoint) int32      [:51-80]
+    FurthestPointSampler(shape, npoint, device)   the same sampling in pieces (extension: begin / advance)
     gather_operation(features, idx)               -> (B, C, npoint)         [:83-117]
     three_nn(unknown, known)                      -> (dist, idx)  dist = sqrt(d2)  [:120-149]
     three_interpolate(features, idx, weight)      -> (B, C, n)              [:152-206]
@@ -77,6 +78,80 @@ class FurthestPointSampling(Function):
 
 
 furthest_point_sample = FurthestPointSampling.apply
+
+
+class FurthestPointSampler:
+    """furthest_point_sample in pieces (extension): one sampling of `npoint` points per scene, advanced a number of rounds at
+    a time -- in time slices next to other work, or grown later (the first m picks of a longer sampling ARE the m-sampling).
+
+        s = FurthestPointSampler(xyz.shape, 2048, xyz.device)
+        s.begin(xyz); s.advance(1024); ...; s.advance()          # s.idx == furthest_point_sample(xyz, 2048)
+
+    The sampler owns its persistent buffers `idx` (B, npoint) int32 and `temp` (B, n) float32 (the running minimum
+    distances), so begin / advance may be captured into a graph and replayed on new contents of the bound cloud.  The whole
+    state of a sampling is (temp, idx[:, :position]) on the device plus `position` on the host; nothing here reads device
+    memory from the host.  Every call launches on the current stream: a caller that spreads the pieces over several streams
+    orders them.  small_footprint: as furthest_point_sample's binding (fewer workgroups per scene on clouds of more than
+    8192 points); it may differ from piece to piece (advance(..., small_footprint=...))."""
+
+    def __init__(self, xyz_shape, npoint, device, small_footprint=False):
+        shape = tuple(int(v) for v in xyz_shape)
+        if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3):
+            raise ValueError("FurthestPointSampler: xyz_shape is (B, n, 3) or (B, n)")
+        self.batch, self.n = shape[0], shape[1]
+        self.npoint = int(npoint)
+        if self.npoint < 0:
+            raise ValueError("FurthestPointSampler: npoint must not be negative")
+        self.small_footprint = bool(small_footprint)
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("CPU not supported")
+        self.idx = torch.zeros((self.batch, self.npoint), device=device, dtype=torch.int32)
+        self.temp = torch.empty((self.batch, self.n), device=device, dtype=torch.float32)
+        self.xyz = None
+        self.position = 0            # rounds done: idx[:, :position] is valid
+
+    @property
+    def done(self):
+        return self.xyz is not None and self.position == self.npoint
+
+    def begin(self, xyz):
+        """Bind a contiguous (B, n, 3) float32 cloud and start over: position 0, temp filled on the current stream."""
+        if xyz.dtype != torch.float32 or not xyz.is_contiguous() or tuple(xyz.shape) != (self.batch, self.n, 3) or \
+                xyz.device != self.idx.device:
+            raise ValueError(f"FurthestPointSampler.begin: xyz must be a contiguous ({self.batch}, {self.n}, 3) float32 tensor "
+                             f"on {self.idx.device}")
+        self.xyz = xyz
+        self.temp.fill_(1e10)
+        self.position = 0
+        return self
+
+    def advance(self, rounds=None, small_footprint=None):
+        """Run the next `rounds` rounds (None: all that are left; more than are left: those) -> the new position."""
+        if self.xyz is None:
+            raise RuntimeError("FurthestPointSampler.advance: begin(xyz) first")
+        left = self.npoint - self.position
+        count = left if rounds is None else int(rounds)
+        if count < 0:
+            raise ValueError("FurthestPointSampler.advance: rounds must not be negative")
+        count = min(count, left)
+        if count:
+            _ext.furthest_point_sampling_resume(self.xyz, self.idx, self.temp, self.position, count,
+                                                self.small_footprint if small_footprint is None else small_footprint)
+            self.position += count
+        return self.position
+
+    def copy_state_from(self, other):
+        """Take over `other`'s sampling where it stands: device-side copies of temp and idx[:, :position] on the current
+        stream, the bound cloud and the position.  Both samplers then continue independently."""
+        if (other.batch, other.n, other.npoint) != (self.batch, self.n, self.npoint) or other.idx.device != self.idx.device:
+            raise ValueError("FurthestPointSampler.copy_state_from: samplers of different shape or device")
+        self.temp.copy_(other.temp)
+        if other.position:
+            self.idx[:, :other.position].copy_(other.idx[:, :other.position])
+        self.xyz = other.xyz
+        self.position = other.position
+        return self
 
 
 class GatherOperation(Function):

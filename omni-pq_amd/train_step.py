@@ -63,12 +63,40 @@ class CapturedStep:
                      (decay, step) pair is accepted for old callers; its step is ignored).
     world / buckets  data parallelism: `buckets` = data_parallel.GradientBuckets(net, world, group) or None (single rank).
     defer            False: leave the weight gradients to autograd (needed under DistributedDataParallel).
+    lookahead        1 (default): the sampling chain of the NEXT batch runs underneath this step, so one step contains a whole
+                     chain.  2: the chain is spread over two steps -- this step runs the rounds [head_rounds, npoint) of the
+                     next batch's sa1 level plus levels 2-4 on the sampling stream (the TAIL) and, side by side on a second
+                     stream, the rounds [0, head_rounds) of the sa1 level of the batch AFTER the next (the HEAD, announced
+                     as step(..., after_next_inputs=...)); after both have joined, the head state (running distances and picks:
+                     1.3 MB at 8 x 40 000 points) is copied to where the next step's tail continues it.  A batch that was
+                     not announced two calls ahead gets its head sampled in front of the replay.  Same indices either way.
+                     Samplings in flight at once: 2 (4 with a teacher); each multi-workgroup launch needs every workgroup
+                     of its scenes resident, so all pieces of the split step use the small footprint (3 compute units per
+                     40 000-point scene: 4 x 8 x 3 = 96 of 256 at batch 8, against 160 with the fast one) unless `fps_footprint`
+                     says otherwise.  Needs prefetch="forward".
+    head_rounds      lookahead=2: where the sa1 level is cut.  None = 0.50 x its npoint (1024 of 2048), the best MEASURED cut on
+                     the mean-teacher step (profiles/fps_resume_ab.txt: 12.35 ms against 13.15 at 0.70 x -- the value derived
+                     from the chain's proportions, (6.2 / 2) / 4.44 -- and 13.86 at 0.85 x; the plain step preferred 0.70 x by
+                     0.06 ms).  Neither beat lookahead=1 on this runtime (10.97 ms; plain step 7.77 vs 7.81): opt-in.
     """
 
     def __init__(self, net, criterion, example_inputs, example_labels=None, *, model=None, amp_dtype=torch.bfloat16,
                  loss_scale=1.0, graph=True, prefetch="forward", fps_footprint=None, teacher=None, teacher_example=None,
                  ema=None, buckets=None, defer=True, warmup=3, distributed=False, before_capture=None,
-                 teacher_to_criterion=False):
+                 teacher_to_criterion=False, lookahead=1, head_rounds=None):
+        if lookahead not in (1, 2):
+            raise ValueError("CapturedStep: lookahead is 1 or 2")
+        if lookahead == 2 and prefetch != "forward":
+            raise ValueError('CapturedStep: lookahead=2 needs prefetch="forward"')
+        self.lookahead = lookahead
+        self.head_rounds = None
+        if lookahead == 2:
+            npoint = net.backbone.sa1.npoint
+            self.head_rounds = int(0.50 * npoint) if head_rounds is None else int(head_rounds)
+            if not 1 <= self.head_rounds < npoint:
+                raise ValueError(f"CapturedStep: head_rounds must be in [1, {npoint})")
+            if fps_footprint is None:
+                fps_footprint = "small"
         self.net, self.model, self.criterion = net, (model if model is not None else net), criterion
         self.amp_dtype, self.scale = amp_dtype, float(loss_scale)
         self.prefetch_at, self.footprint = prefetch, fps_footprint
@@ -87,10 +115,12 @@ class CapturedStep:
         pc = _cloud(example_inputs)
         self.cur, self.nxt = pc.clone(), pc.clone()
         self.lab = {k: v.clone() for k, v in example_labels.items()} if example_labels is not None else None
-        self.cur_t = self.nxt_t = None
+        self.nxt2 = pc.clone() if lookahead == 2 else None
+        self.cur_t = self.nxt_t = self.nxt2_t = None
         if teacher is not None:
             tpc = _cloud(teacher_example if teacher_example is not None else example_inputs)
             self.cur_t, self.nxt_t = tpc.clone(), tpc.clone()
+            self.nxt2_t = tpc.clone() if lookahead == 2 else None
         self.graph = None
         self.static_loss = None
         self.end_points = None
@@ -98,6 +128,7 @@ class CapturedStep:
         self.replays = 0
         self._promised = None          # the tensor announced as `next_inputs` by the previous call (kept alive: compared with `is`)
         self._have_next = False        # does `nxt` (and the plan in flight) hold the batch the next call will run?
+        self._promised2 = None         # lookahead=2: the tensor announced as `after_next_inputs` by the previous call
         if graph:
             self._capture(warmup, before_capture)
 
@@ -124,17 +155,33 @@ class CapturedStep:
                 dropout_state.STATE.use("teacher"):
             return self.teacher({"point_clouds": batch})            # train mode, no grad (train.py:462, 490-491)
 
-    def _body(self, cur, nxt, lab, cur_t, nxt_t, trusted):
+    def _body(self, cur, nxt, lab, cur_t, nxt_t, trusted, nxt2=None, nxt2_t=None):
         """forward + loss (+ teacher forward) + backward (+ EMA) on `cur`, with the sampling plan of `nxt` started on the
-        side stream.  trusted: the plan in flight IS the plan of `cur` whatever tensor object forward() is handed."""
+        side stream.  trusted: the plan in flight IS the plan of `cur` whatever tensor object forward() is handed.
+        lookahead=2: the chain of `nxt` continues the head sampled a step ago, and the head of `nxt2` runs next to it."""
         net, teacher = self.net, self.teacher
         for p in net.parameters():
             p.grad = None
         early = self.prefetch_at == "forward" and nxt is not None
-        if early:
+        split = self.lookahead == 2
+        if early and not split:
             net.prefetch({"point_clouds": nxt}, trusted=trusted, at_next_forward=True, footprint=self.footprint)
             if teacher is not None:
                 teacher.prefetch({"point_clouds": nxt_t}, trusted=trusted, at_next_forward=True, footprint=self.footprint)
+        heads = []
+        if split:
+            if early:
+                net.prefetch({"point_clouds": nxt}, trusted=trusted, at_next_forward=True, footprint=self.footprint, resume=True)
+                if teacher is not None:
+                    teacher.prefetch({"point_clouds": nxt_t}, trusted=trusted, at_next_forward=True, footprint=self.footprint,
+                                     resume=True)
+            if nxt2 is not None:
+                # the heads fork from (and join to) THIS stream, not from inside the sampling streams
+                net.prefetch_head({"point_clouds": nxt2}, self.head_rounds, trusted=trusted, footprint=self.footprint)
+                heads.append(net)
+                if teacher is not None:
+                    teacher.prefetch_head({"point_clouds": nxt2_t}, self.head_rounds, trusted=trusted, footprint=self.footprint)
+                    heads.append(teacher)
         tep = None
         if teacher is not None and self.TEACHER_FIRST:
             # The two forwards are independent (train.py:489-491 runs the student's first; nothing reads one from the other
@@ -162,10 +209,14 @@ class CapturedStep:
                 teacher.prefetch({"point_clouds": nxt_t}, trusted=trusted)
         self._backward(loss)
         if not self._capturing:
+            for m in heads:
+                m.hand_over_head()                   # (this stream waits for the head; the host does not)
             return loss                              # eager mode: the plan keeps running underneath whatever comes next
         net.join_prefetch()
         if teacher is not None:
             teacher.join_prefetch()
+        for m in heads:
+            m.hand_over_head()                       # head state -> the state the next step's chain continues
         return loss
 
     def update_teacher(self, global_step):
@@ -192,6 +243,14 @@ class CapturedStep:
             self.nxt.copy_(self.cur)
             if teacher is not None:
                 self.nxt_t.copy_(self.cur_t)
+            split = self.lookahead == 2
+            if split:
+                # the warm-up steps run the split body, so the exchange workspaces of BOTH sampling streams exist (they grow
+                # on first use, which a capture cannot do) and the first of them finds a head to continue
+                self.nxt2.copy_(self.cur)
+                if teacher is not None:
+                    self.nxt2_t.copy_(self.cur_t)
+                self._sample_head_now()
             if self.prefetch_at is not None:
                 net.prefetch({"point_clouds": self.nxt}, trusted=True)          # plan of the first batch
                 if teacher is not None:
@@ -200,7 +259,8 @@ class CapturedStep:
                 self.cur.copy_(self.nxt)
                 if teacher is not None:
                     self.cur_t.copy_(self.nxt_t)
-                self._body(self.cur, self.nxt if self.prefetch_at else None, self.lab, self.cur_t, self.nxt_t, True)
+                self._body(self.cur, self.nxt if self.prefetch_at else None, self.lab, self.cur_t, self.nxt_t, True,
+                           self.nxt2, self.nxt2_t)
             torch.cuda.synchronize()
             if self.distributed:
                 _quiesce_process_groups(self.cur.device, (getattr(self.buckets, "group", None),))
@@ -211,7 +271,7 @@ class CapturedStep:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 self.static_loss = self._body(self.cur, self.nxt if self.prefetch_at else None, self.lab, self.cur_t,
-                                              self.nxt_t, True)
+                                              self.nxt_t, True, self.nxt2, self.nxt2_t)
             self.graph = graph
             self.launch = "hipGraph replay"
             self._have_next = True                   # `nxt` holds the example batch, its plan was started by the capture run
@@ -227,12 +287,26 @@ class CapturedStep:
             self._capturing = False
 
     # ---- one training step -------------------------------------------------------------------------------------------------
-    def step(self, inputs=None, labels=None, next_inputs=None, teacher_inputs=None, next_teacher_inputs=None):
+    def _sample_head_now(self):
+        """lookahead=2: head of the batch in `nxt`, sampled and handed over on the spot (no head of it is in flight)."""
+        self.net.prefetch_head({"point_clouds": self.nxt}, self.head_rounds, trusted=True, footprint=self.footprint)
+        self.net.hand_over_head()
+        if self.teacher is not None:
+            self.teacher.prefetch_head({"point_clouds": self.nxt_t}, self.head_rounds, trusted=True, footprint=self.footprint)
+            self.teacher.hand_over_head()
+
+    def step(self, inputs=None, labels=None, next_inputs=None, teacher_inputs=None, next_teacher_inputs=None,
+             after_next_inputs=None, after_next_teacher_inputs=None):
         """Forward + loss + backward of `inputs`; returns the loss (graph mode: a static tensor, overwritten by the next
         call).  next_inputs: the batch the NEXT call will run (tensor / dict / callable(dst) filling the static buffer) -- its
         coordinate-only sampling runs underneath this step.  inputs=None or the very object announced as `next_inputs` last
         time: the announced batch is taken as is; any other input is copied in and its sampling plan recomputed up front
-        (correct, and ~5 ms slower for that call at 40 000 points).  next_inputs=None: nothing to announce (last batch)."""
+        (correct, and ~5 ms slower for that call at 40 000 points).  next_inputs=None: nothing to announce (last batch).
+        after_next_inputs (lookahead=2 only): the batch of the call after the next; the head of its sampling runs underneath
+        this step.  A `next_inputs` that was not announced this way one call earlier (the very object) has its head sampled
+        in front of the replay."""
+        if self.lookahead != 2 and (after_next_inputs is not None or after_next_teacher_inputs is not None):
+            raise ValueError("CapturedStep.step: after_next_inputs needs a stepper built with lookahead=2")
         if self.teacher is not None and self.ema is not None:
             self._steps_unaveraged = getattr(self, "_steps_unaveraged", 0) + 1
             if self._steps_unaveraged == 4:
@@ -241,7 +315,8 @@ class CapturedStep:
                               "called for three steps -- the teacher's weights are not being averaged (call it after "
                               "optimizer.step(), where the reference calls update_ema_variables)")
         if self.graph is None:
-            return self._eager_step(inputs, labels, next_inputs, teacher_inputs, next_teacher_inputs)
+            return self._eager_step(inputs, labels, next_inputs, teacher_inputs, next_teacher_inputs, after_next_inputs,
+                                    after_next_teacher_inputs)
         net, teacher = self.net, self.teacher
         pc = None if inputs is None else _cloud(inputs)
         announced = self._have_next and (pc is None or (self._promised is not None and self._promised[0] is pc
@@ -277,6 +352,21 @@ class CapturedStep:
         else:
             self._promised = None
         self._have_next = next_inputs is not None
+        if self.lookahead == 2:
+            t = None if (next_inputs is None or callable(next_inputs)) else _cloud(next_inputs)
+            head_ahead = t is not None and self._promised2 is not None and self._promised2[0] is t \
+                and self._promised2[1] == t._version
+            if next_inputs is not None and not head_ahead:
+                self._sample_head_now()              # the head in the tail state belongs to some other batch
+            self._fill(self.nxt2, after_next_inputs)
+            if teacher is not None:
+                self._fill(self.nxt2_t, after_next_teacher_inputs if after_next_teacher_inputs is not None
+                           else after_next_inputs)
+            if after_next_inputs is not None and not callable(after_next_inputs):
+                t2 = _cloud(after_next_inputs)
+                self._promised2 = (t2, t2._version)
+            else:
+                self._promised2 = None
         self.graph.replay()
         self.replays += 1
         for p, g in self._grads:
@@ -301,7 +391,8 @@ class CapturedStep:
         else:
             dst.copy_(_cloud(src))
 
-    def _eager_step(self, inputs, labels, next_inputs, teacher_inputs, next_teacher_inputs):
+    def _eager_step(self, inputs, labels, next_inputs, teacher_inputs, next_teacher_inputs, after_next_inputs=None,
+                    after_next_teacher_inputs=None):
         """The same sequence launched kernel by kernel (no static buffers: the caller's tensors are used directly)."""
         if inputs is None:
             raise ValueError("CapturedStep.step (eager): pass `inputs`")
@@ -311,7 +402,11 @@ class CapturedStep:
             nxt = _cloud(next_inputs)
         t_cur = _cloud(teacher_inputs) if teacher_inputs is not None else pc
         t_nxt = _cloud(next_teacher_inputs) if next_teacher_inputs is not None else nxt
-        return self._body(pc, nxt, labels, t_cur, t_nxt, False)
+        nxt2 = t_nxt2 = None
+        if self.lookahead == 2 and after_next_inputs is not None and not callable(after_next_inputs):
+            nxt2 = _cloud(after_next_inputs)
+            t_nxt2 = _cloud(after_next_teacher_inputs) if after_next_teacher_inputs is not None else nxt2
+        return self._body(pc, nxt, labels, t_cur, t_nxt, False, nxt2, t_nxt2)
 
 
 def _quiesce_process_groups(device, extra_groups=()):
