@@ -36,7 +36,7 @@ extern "C" {
 #endif
 
 /* 2: round 5's signatures (21 entry points take `const omnipq_row_plan *plan` in front of the stream; omnipq_fps_footprint,
- *    omnipq_sa_row_plan, omnipq_sa_plan_pool_gamma, omnipq_gemm_strip_* removed) + omnipq_plan_aware_entry_points().
+ *    omnipq_sa_row_plan, omnipq_sa_plan_pool_gamma, omnipq_gemm_strip_* removed) + the library's own list of those 21 names.
  * 3: round 6 -- omnipq_row_plan grew { tickets, ticket_words }; omnipq_gemm_nt_e16_bnaffine_pool accepts C == NULL (no store);
  *    new: omnipq_sa_last_bwd_prep, omnipq_gemm_nt_e16_dz_bnbwd, omnipq_gemm_tn_dz, omnipq_sa_last_wgrad_combine,
  *    omnipq_sa_pool_bwd_stats_sel_hot, omnipq_ipc_* (omnipq_sa.h), omnipq_ffn_fused_* (omnipq_decoder.h); timing aids
@@ -44,8 +44,11 @@ extern "C" {
  * 4: omnipq_row_plan lost { tickets, ticket_words } again (the in-GEMM statistics fold was slower and left the library);
  *    omnipq_ffn_fused_* removed (never wired into the model).
  *    Added under 4 (additive: no existing argument list changed): omnipq_furthest_point_sampling_resume.
+ * 5: that list left the library: omnipq_entry_point_signatures() reports the whole signature of every entry point, and the
+ *    binding declares its calls from it (the plan-aware entry points are the ones with a `P`).  omnipq_gemm_nt_e16_splitk,
+ *    exported and called all along, is declared (omnipq_sa.h).
  * A binding must refuse a library whose version it was not written against: the argument lists differ. */
-#define OMNIPQ_ABI_VERSION 4
+#define OMNIPQ_ABI_VERSION 5
 
 #define OMNIPQ_OK 0
 #define OMNIPQ_EINVAL 10001     /* bad shape / null pointer */
@@ -54,9 +57,13 @@ extern "C" {
 
 int omnipq_abi_version(void);
 const char *omnipq_error_string(int code);
-/* space-separated names of the entry points of this build that take `const omnipq_row_plan *plan` (omnipq_sa.h) in front of
- * the stream argument -- a binding asks the library it loaded instead of parsing a header */
-const char *omnipq_plan_aware_entry_points(void);
+/* Every entry point of this build, one line `name <ret> <params>` each, one letter per type:
+ *   parameters  i int, u unsigned, l long long, f float, d double, p any pointer (arrays and struct pointers included),
+ *               P `const omnipq_row_plan *` (omnipq_sa.h; always in front of the stream argument); none for `(void)`
+ *   return      i int, l long long, v void, s const char *
+ * e.g. "omnipq_furthest_point_sampling_resume i iiiiipppup".  Written from these headers when the library is built, so a
+ * binding declares its calls from the library it loaded instead of parsing a header that may belong to another build. */
+const char *omnipq_entry_point_signatures(void);
 /* Measurement helper: dst[0..bytes) = src[0..bytes) (bytes % 16 == 0) with the streaming shape that reaches this chip's
  * highest copy rate -- the "measured copy ceiling" bench.py reports next to the 8 TB/s datasheet peak. */
 int omnipq_copy_probe(const void *src, void *dst, long long bytes, void *stream);

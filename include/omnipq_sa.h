@@ -78,6 +78,10 @@ int omnipq_gemm_nt_e16_bias(int M, int N, int K, const void *A, int lda, const v
 long long omnipq_gemm_nt_workspace_floats(int M, int N, int K);
 int omnipq_gemm_nt_e16_ws(int M, int N, int K, const void *A, int lda, const void *B, int ldb, void *C, int ldc,
                            const float *bias, float *workspace, void *stream);
+/* C[M][N] (f32, ldc == N) = A B^T with the contraction cut into at most `slabs` >= 1 slices that are summed in f32;
+ * workspace: slabs * M * N floats (K % 32 == 0, N % 4 == 0).  The f32 rows' product of split operands (omnipq_f32.h). */
+int omnipq_gemm_nt_e16_splitk(int M, int N, int K, const void *A, int lda, const void *B, int ldb, float *C, int slabs,
+                              float *workspace, void *stream);
 
 /* C = dropout(relu(A B^T + bias)) in one launch (the decoder feed-forward's first layer, transformer.py:222-224): the
  * same decisions as omnipq_relu_dropout (omnipq_decoder.h) applied to the stored matrix -- hash of the seed word, the

@@ -66,24 +66,54 @@ def sources_digest():
     return h.hexdigest()
 
 
-def plan_aware_entry_points():
-    """Names of the entry points whose declaration in include/omnipq_sa.h takes `const omnipq_row_plan *plan` (in front of
-    the stream).  Evaluated at BUILD time and compiled into the library (csrc/capi.hip: omnipq_plan_aware_entry_points), so
+_SCALARS = {"int": "i", "unsigned": "u", "long long": "l", "float": "f", "double": "d"}
+_RETURNS = {"int": "i", "long long": "l", "void": "v", "const char *": "s"}
+
+
+def entry_point_signatures():
+    """Every declaration of include/*.h as one line `name <ret> <params>`, one letter per type: i int, u unsigned, l long long,
+    f float, d double, p any pointer (arrays and struct pointers included), P `const omnipq_row_plan *`; returns i, l, v void,
+    s const char *.  Evaluated at BUILD time and compiled into the library (csrc/capi.hip: omnipq_entry_point_signatures), so
     that a binding asks the library it actually loaded how its entry points are called instead of parsing a header that may
-    belong to another build."""
+    belong to another build.  A type that is not in this list fails the build: it is never guessed."""
     import re
-    with open(os.path.join(REPO, "include", "omnipq_sa.h")) as fh:
-        text = re.sub(r"/\*.*?\*/", " ", fh.read(), flags=re.S)
-    return sorted(m.group(1) for m in re.finditer(r"\b(omnipq_\w+)\s*\(([^;{}()]*)\)\s*;", text)
-                  if "omnipq_row_plan *plan" in m.group(2))
+
+    def words(s):
+        return " ".join(s.replace("*", " * ").split())
+
+    lines = []
+    inc = os.path.join(REPO, "include")
+    for header in sorted(f for f in os.listdir(inc) if f.endswith(".h")):
+        with open(os.path.join(inc, header)) as fh:
+            text = re.sub(r"/\*.*?\*/", " ", fh.read(), flags=re.S)
+        text = re.sub(r"^[ \t]*#.*$", ";", text, flags=re.M)
+        for m in re.finditer(r"([^;{}()]*?)\b(omnipq_\w+)\s*\(([^;{}()]*)\)\s*;", text):
+            name = m.group(2)
+            ret = _RETURNS.get(words(m.group(1)))
+            if ret is None:
+                raise RuntimeError(f"{header}: {name}: return type `{words(m.group(1))}` has no signature letter")
+            letters = ""
+            params = [words(q) for q in m.group(3).split(",")]
+            for q in ([] if params == ["void"] else params):
+                decl = re.sub(r"\s*\w+\s*(\[[^\]]*\]\s*)*$", "", q)       # the type without the parameter's name / [n]
+                if decl == "const omnipq_row_plan *":
+                    letters += "P"
+                elif "*" in q or "[" in q:
+                    letters += "p"
+                elif decl in _SCALARS:
+                    letters += _SCALARS[decl]
+                else:
+                    raise RuntimeError(f"{header}: {name}: parameter `{q}` has no signature letter")
+            lines.append(f"{name} {ret} {letters}".rstrip())
+    return "".join(line + "\n" for line in sorted(lines))
 
 
 def _write_generated():
-    """build/generated/plan_aware.inc: one string literal, rewritten only when its content changes."""
+    """build/generated/entry_points.inc: the text above as C string literals, rewritten only when its content changes."""
     gen = os.path.join(OBJDIR, "generated")
     os.makedirs(gen, exist_ok=True)
-    path = os.path.join(gen, "plan_aware.inc")
-    text = '"' + " ".join(plan_aware_entry_points()) + '"\n'
+    path = os.path.join(gen, "entry_points.inc")
+    text = "".join(f'"{line}\\n"\n' for line in entry_point_signatures().splitlines())
     if not os.path.exists(path) or open(path).read() != text:
         with open(path, "w") as fh:
             fh.write(text)
@@ -104,7 +134,7 @@ def build(force=False, verbose=False):
     inc = os.path.join(REPO, "include")
     headers += [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")]
     gen = _write_generated()
-    headers.append(os.path.join(gen, "plan_aware.inc"))
+    headers.append(os.path.join(gen, "entry_points.inc"))
     procs, links = [], []
     for lib, sub, defines in VARIANTS:
         objdir = os.path.join(OBJDIR, sub)

@@ -3,11 +3,11 @@
 
 extern "C" int omnipq_abi_version(void) { return OMNIPQ_ABI_VERSION; }
 
-// The entry points of THIS build that take `const omnipq_row_plan *plan` in front of the stream: a space-separated list,
-// written by omni-pq_amd/build.py from include/omnipq_sa.h when the library is compiled.
-extern "C" const char *omnipq_plan_aware_entry_points(void) {
+// Every entry point of THIS build with its signature, one line `name <ret> <params>` each (one letter per type, see
+// include/omnipq_pointops.h): written by omni-pq_amd/build.py from include/*.h when the library is compiled.
+extern "C" const char *omnipq_entry_point_signatures(void) {
   return
-#include "plan_aware.inc"
+#include "entry_points.inc"
       ;
 }
 

@@ -8,7 +8,6 @@ instead of two elementwise launches per parameter tensor (~620).  The device-sid
 is built once per model pair and follows in-place parameter updates (addresses do not change); replaced
 parameters rebuild it.
 """
-import ctypes
 import os
 import sys
 import weakref
@@ -64,5 +63,5 @@ def update_ema_variables(model, ema_model, alpha, global_step):
     import sa_fused
     _, table, chunks, nseg = hit
     sa_fused._call(sa_fused._lib.omnipq_ema_update, table, nseg, int(chunks.shape[0]), sa_fused._p(table),
-                   sa_fused._p(chunks), ctypes.c_float(a), ctypes.c_float(1.0 - a))
+                   sa_fused._p(chunks), a, 1.0 - a)
     return a

@@ -21,8 +21,6 @@ import pointnet2_utils
 
 _ext = pointnet2_utils._ext
 _lib0 = _ext._lib0
-_lib0.omnipq_ipc_mailbox_bytes.restype = ctypes.c_longlong
-_lib0.omnipq_ipc_site_granules.restype = ctypes.c_longlong
 
 
 class IpcStats:
@@ -41,7 +39,7 @@ class IpcStats:
         own = ctypes.c_void_p()
         handle = (ctypes.c_ubyte * 64)()
         with torch.cuda.device(self.device):
-            rc = _lib0.omnipq_ipc_mailbox_create(self.world, ctypes.c_longlong(capture_doubles), ctypes.byref(own), handle)
+            rc = _lib0.omnipq_ipc_mailbox_create(self.world, capture_doubles, ctypes.byref(own), handle)
         if rc:
             raise RuntimeError(f"omnipq_ipc_mailbox_create: {_lib0.omnipq_error_string(rc).decode()}")
         self._own = own
@@ -93,7 +91,7 @@ class IpcStats:
                     raise RuntimeError("IpcStats: out of room for captured exchanges (capture_doubles)")
                 rc = _lib0.omnipq_ipc_allreduce_f64(ctypes.c_void_p(flat.data_ptr() + 8 * off), n, self._boxes, self.rank,
                                                     self.world, ctypes.c_void_p(self._site_counters.data_ptr() + 4 * self._sites),
-                                                    gave_up, ctypes.c_longlong(self._site_base), n, stream)
+                                                    gave_up, self._site_base, n, stream)
                 if rc:
                     raise RuntimeError(f"omnipq_ipc_allreduce_f64: {_lib0.omnipq_error_string(rc).decode()}")
                 self._sites += 1
@@ -106,7 +104,7 @@ class IpcStats:
         for off in range(0, flat.numel(), self.MAX_DOUBLES):
             n = min(self.MAX_DOUBLES, flat.numel() - off)
             rc = _lib0.omnipq_ipc_allreduce_f64(ctypes.c_void_p(flat.data_ptr() + 8 * off), n, self._boxes, self.rank, self.world,
-                                                ctypes.c_void_p(self.state.data_ptr()), gave_up, ctypes.c_longlong(0), 0, stream)
+                                                ctypes.c_void_p(self.state.data_ptr()), gave_up, 0, 0, stream)
             if rc:
                 raise RuntimeError(f"omnipq_ipc_allreduce_f64: {_lib0.omnipq_error_string(rc).decode()}")
             self.exchanges += 1

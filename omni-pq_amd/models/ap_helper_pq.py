@@ -54,12 +54,12 @@ def _decode(center, normal, size, scores=None, nms=None):
         out["prob"] = torch.empty((B, K), device=dev, dtype=torch.float32)
     null = ctypes.c_void_p(0)
     _ext._run(_lib.omnipq_parse_quads, c, B, K, _ext._ptr(c), _ext._ptr(n), _ext._ptr(s),
-              null if sc is None else _ext._ptr(sc), ctypes.c_float(LENGTH), _ext._ptr(out["corners8"]),
+              null if sc is None else _ext._ptr(sc), LENGTH, _ext._ptr(out["corners8"]),
               _ext._ptr(out["aabb"]), _ext._ptr(out["verts4"]), null if sc is None else _ext._ptr(out["prob"]))
     if nms is not None:
         out["keep"] = torch.empty((B, K), device=dev, dtype=torch.uint8)
         _ext._run(_lib.omnipq_nms3d, c, B, K, _ext._ptr(out["aabb"]), _ext._ptr(out["prob"]), null,
-                  ctypes.c_double(float(nms[0])), int(bool(nms[1])), _ext._ptr(out["keep"]))
+                  float(nms[0]), int(bool(nms[1])), _ext._ptr(out["keep"]))
     return out
 
 
@@ -173,7 +173,7 @@ def _corners(center, size, heading):
     corners8 = torch.empty((B, K, 8, 3), device=center.device, dtype=torch.float64)
     aabb = torch.empty((B, K, 6), device=center.device, dtype=torch.float64)
     null = ctypes.c_void_p(0)
-    _ext._run(_lib.omnipq_box_corners, center, ctypes.c_longlong(B * K), _ext._ptr(center), _ext._ptr(size),
+    _ext._run(_lib.omnipq_box_corners, center, B * K, _ext._ptr(center), _ext._ptr(size),
               null if heading is None else _ext._ptr(heading), _ext._ptr(corners8), _ext._ptr(aabb))
     return corners8, aabb
 
@@ -219,7 +219,7 @@ def parse_predictions(end_points, config_dict, prefix=""):
     obj_prob_t = torch.sigmoid(end_points[f'{prefix}objectness_scores'].detach().float())[:, :, 1].contiguous()
     keep = torch.empty((B, K), device=dev, dtype=torch.uint8)
     vptr = null if valid is None else _ext._ptr(valid)
-    thr, old = ctypes.c_double(float(config_dict['nms_iou'])), int(bool(config_dict['use_old_type_nms']))
+    thr, old = float(config_dict['nms_iou']), int(bool(config_dict['use_old_type_nms']))
     if not config_dict['use_3d_nms']:
         # bird's-eye-view suppression on (x, z) extents: the 3D kernel with a unit second axis
         flat = aabb.clone()

@@ -28,7 +28,6 @@ import sa_fused
 from sa_fused import E16, _call, _lib, _p, zeros_f32
 from utils import fused_attention
 
-_lib.omnipq_add_dropout_layernorm_bwd_blocks.restype = ctypes.c_longlong
 
 
 class AddToBf16(torch.autograd.Function):
@@ -38,7 +37,7 @@ class AddToBf16(torch.autograd.Function):
     def forward(ctx, a, b):
         ctx.e16 = E16.dtype
         out = torch.empty(a.shape, device=a.device, dtype=E16.dtype)
-        _call(_lib.omnipq_add_to_e16, a, ctypes.c_longlong(a.numel()), _p(a), int(a.dtype == torch.float32), _p(b),
+        _call(_lib.omnipq_add_to_e16, a, a.numel(), _p(a), int(a.dtype == torch.float32), _p(b),
               _p(out))
         ctx.a_dtype = a.dtype
         return out
@@ -80,14 +79,14 @@ class FanOut(torch.autograd.Function):
             if all(r.data_ptr() % 16 == 0 for r in rows):
                 out = torch.empty(rows[0].shape, device=rows[0].device, dtype=dtype)
                 ptrs = (ctypes.c_void_p * len(rows))(*[r.data_ptr() for r in rows])
-                _call(_lib.omnipq_add_n, out, len(rows), ptrs, ctypes.c_longlong(numel), int(dtype == E16.dtype), _p(out))
+                _call(_lib.omnipq_add_n, out, len(rows), ptrs, numel, int(dtype == E16.dtype), _p(out))
                 return out.transpose(1, 2), None
         if dtype in (E16.dtype, torch.float32) and numel % 8 == 0 and len(gs) <= 16 and \
                 all(g.is_cuda and g.dtype == dtype and g.is_contiguous() and g.data_ptr() % 16 == 0 and
                     tuple(g.shape) == shape for g in gs):
             out = torch.empty(shape, device=gs[0].device, dtype=dtype)
             ptrs = (ctypes.c_void_p * len(gs))(*[g.data_ptr() for g in gs])
-            _call(_lib.omnipq_add_n, out, len(gs), ptrs, ctypes.c_longlong(numel), int(dtype == E16.dtype), _p(out))
+            _call(_lib.omnipq_add_n, out, len(gs), ptrs, numel, int(dtype == E16.dtype), _p(out))
             return out, None
         total = gs[0]
         for g in gs[1:]:
@@ -184,8 +183,8 @@ class AddDropoutLayerNorm(torch.autograd.Function):
         seed = dropout_state.seed(dev) if drop else None
         salt = dropout_state.next_salt() if drop else 0
         g32, b32 = gamma.detach().float(), beta.detach().float()
-        _call(_lib.omnipq_add_dropout_layernorm, x, ctypes.c_longlong(R), C, _p(x), _p(y), _p(g32), _p(b32),
-              ctypes.c_float(eps), ctypes.c_float(p if drop else 0.0), _p(seed), salt, _p(out32), _p(out16), _p(pe),
+        _call(_lib.omnipq_add_dropout_layernorm, x, R, C, _p(x), _p(y), _p(g32), _p(b32),
+              eps, p if drop else 0.0, _p(seed), salt, _p(out32), _p(out16), _p(pe),
               _p(out_pe), _p(mean), _p(rstd))
         ctx.save_for_backward(x, y, g32, mean, rstd)
         ctx.set_materialize_grads(False)        # unused outputs (f32 / bf16 / bf16 + pe) arrive as None, not as zero tensors
@@ -209,15 +208,15 @@ class AddDropoutLayerNorm(torch.autograd.Function):
         if dfr is not None and ctx.params is not None:
             # nothing reads dgamma / dbeta before the optimizer: leave per-workgroup partial sums and let the block sum
             # those of all LayerNorms in one launch (the atomics of the immediate path were most of this kernel's time)
-            blocks = int(_lib.omnipq_add_dropout_layernorm_bwd_blocks(ctypes.c_longlong(R)))
+            blocks = int(_lib.omnipq_add_dropout_layernorm_bwd_blocks(R))
             part = torch.empty((blocks, 2 * C), device=x.device, dtype=torch.float32)
-            _call(_lib.omnipq_add_dropout_layernorm_bwd_partials, x, ctypes.c_longlong(R), C, _p(x), _p(y), _p(gamma),
-                  ctypes.c_float(p), _p(seed), salt, _p(mean), _p(rstd), _p(g32), _p(g16), _p(gpe), _p(dx), _p(dy), _p(part))
+            _call(_lib.omnipq_add_dropout_layernorm_bwd_partials, x, R, C, _p(x), _p(y), _p(gamma),
+                  p, _p(seed), salt, _p(mean), _p(rstd), _p(g32), _p(g16), _p(gpe), _p(dx), _p(dy), _p(part))
             dfr.add_layernorm(part, blocks, C, *ctx.params)
             return dx, dy, None, None, None, None, (gpe if has_pe else None), None, None
         dgb = zeros_f32(2 * C, x.device)
-        _call(_lib.omnipq_add_dropout_layernorm_bwd, x, ctypes.c_longlong(R), C, _p(x), _p(y), _p(gamma),
-              ctypes.c_float(p), _p(seed), salt, _p(mean), _p(rstd), _p(g32), _p(g16), _p(gpe), _p(dx), _p(dy), _p(dgb))
+        _call(_lib.omnipq_add_dropout_layernorm_bwd, x, R, C, _p(x), _p(y), _p(gamma),
+              p, _p(seed), salt, _p(mean), _p(rstd), _p(g32), _p(g16), _p(gpe), _p(dx), _p(dy), _p(dgb))
         return dx, dy, dgb[:C], dgb[C:], None, None, (gpe if has_pe else None), None, None
 
 

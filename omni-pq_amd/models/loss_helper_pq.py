@@ -91,7 +91,6 @@ class _PcDesc(ctypes.Structure):
                 ("normal_vector", _P), ("quad_size", _P), ("quad_label", _P), ("not_solid", ctypes.c_ulonglong)]
 
 
-_lib.omnipq_loss_physical_workspace_floats.restype = ctypes.c_longlong
 
 BOX_KEYS = ("objectness_scores", "center", "heading_scores", "heading_residuals_normalized", "size_scores",
             "size_residuals_normalized", "sem_cls_scores")
@@ -148,7 +147,7 @@ def _assign(query, gt, num_gt):
     mask = torch.empty((B, K), device=q.device, dtype=torch.float32)
     counts = torch.empty(2, device=q.device, dtype=torch.float32)
     _ext._run(_lib.omnipq_loss_assign, q, B, K, K2, _ext._ptr(q), _ext._ptr(g), _ext._ptr(n),
-              ctypes.c_float(NEAR_THRESHOLD), ctypes.c_float(FAR_THRESHOLD), _ext._ptr(label), _ext._ptr(mask),
+              NEAR_THRESHOLD, FAR_THRESHOLD, _ext._ptr(label), _ext._ptr(mask),
               _ext._ptr(assignment), _ext._ptr(counts))
     return label, mask, assignment, counts
 

@@ -227,7 +227,7 @@ class HeadDecode(torch.autograd.Function):
         scale = float(np.float32(np.pi / nh))
         ptrs = (ctypes.c_void_p * 10)(*[o.data_ptr() for o in outs])
         sa_fused._call(sa_fused._lib.omnipq_head_decode, y, R, nh, ns, ncls, sa_fused._p(y), y.stride(0),
-                       sa_fused._p(base), sa_fused._p(means), ctypes.c_float(scale), ptrs)
+                       sa_fused._p(base), sa_fused._p(means), scale, ptrs)
         ctx.save_for_backward(y, means)
         ctx.geom = (B, K, nh, ns, ncls, scale)
         return tuple(outs)
@@ -244,7 +244,7 @@ class HeadDecode(torch.autograd.Function):
         dy = torch.empty((R, y.shape[1]), device=y.device, dtype=E16.dtype)
         dbase = torch.empty((B, K, 3), device=y.device, dtype=torch.float32) if ctx.needs_input_grad[1] else None
         sa_fused._call(sa_fused._lib.omnipq_head_decode_bwd, y, R, K, nh, ns, ncls, sa_fused._p(y), y.stride(0),
-                       sa_fused._p(means), ctypes.c_float(scale), (ctypes.c_void_p * 10)(*ptrs),
+                       sa_fused._p(means), scale, (ctypes.c_void_p * 10)(*ptrs),
                        (ctypes.c_int * 40)(*strides), (ctypes.c_int * 10)(*n2), (ctypes.c_int * 10)(*flags),
                        sa_fused._p(dy), dy.stride(0), sa_fused._p(dbase))
         return dy, dbase, None, None, None, None
@@ -346,7 +346,7 @@ class DecodePair(torch.autograd.Function):
         pos = torch.empty((B, K + Kq, 3), **f32) if (want_pos and B == Bq) else None
         scale = float(np.float32(np.pi / nh))
         sa_fused._call(sa_fused._lib.omnipq_decode_pair, yh, B * K, K, nh, ns, ncls, sa_fused._p(yh), yh.stride(0),
-                       sa_fused._p(bh), sa_fused._p(means), ctypes.c_float(scale),
+                       sa_fused._p(bh), sa_fused._p(means), scale,
                        (ctypes.c_void_p * 10)(*[o.data_ptr() for o in outs_h]), Bq * Kq, Kq, sa_fused._p(yq), yq.stride(0),
                        sa_fused._p(bq), (ctypes.c_void_p * 4)(*[o.data_ptr() for o in outs_q]), sa_fused._p(norm),
                        sa_fused._p(pos))
@@ -385,7 +385,7 @@ class DecodePair(torch.autograd.Function):
             dbh = torch.empty((B, K, 3), device=dev, dtype=torch.float32) if ctx.needs_input_grad[1] else None
         dbq = torch.empty((Bq, Kq, 3), device=dev, dtype=torch.float32) if ctx.needs_input_grad[7] else None
         sa_fused._call(sa_fused._lib.omnipq_decode_pair_bwd, yh, B * K, K, nh, ns, ncls, sa_fused._p(yh), yh.stride(0),
-                       sa_fused._p(means), ctypes.c_float(scale), (ctypes.c_void_p * 10)(*ph), (ctypes.c_int * 40)(*sh),
+                       sa_fused._p(means), scale, (ctypes.c_void_p * 10)(*ph), (ctypes.c_int * 40)(*sh),
                        (ctypes.c_int * 10)(*n2), (ctypes.c_int * 10)(*fh), sa_fused._p(dyh), dyh.stride(0),
                        sa_fused._p(dbh), Bq * Kq, Kq, sa_fused._p(yq), yq.stride(0), sa_fused._p(norm),
                        (ctypes.c_void_p * 4)(*pq), (ctypes.c_int * 16)(*sq), (ctypes.c_int * 4)(*fq), sa_fused._p(dyq),

@@ -52,7 +52,7 @@ class FusedAttention(torch.autograd.Function):
         seed = STATE.seed(q.device) if dropout_p > 0 else None
         salt = STATE.next_salt() if dropout_p > 0 else 0
         _call(_lib.omnipq_attn_fwd, q, N, num_heads, L, S, D, _p(q), _p(k), _p(v), _p(o), _strides(q, k, v, o), _p(lse),
-              ctypes.c_float(dropout_p), _p(seed), salt)
+              dropout_p, _p(seed), salt)
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.cfg = (num_heads, dropout_p, seed, salt)
         return o
@@ -74,7 +74,7 @@ class FusedAttention(torch.autograd.Function):
         delta = torch.empty_like(lse)
         _call(_lib.omnipq_attn_bwd, q, N, num_heads, L, S, D, _p(q), _p(k), _p(v), _p(o), _p(d_o),
               _strides(q, k, v, o), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), _strides(dq, dk, dv),
-              ctypes.c_float(dropout_p), _p(seed), salt)
+              dropout_p, _p(seed), salt)
         return dq, dk, dv, None, None
 
 
@@ -85,7 +85,7 @@ def attention(q, k, v, num_heads, dropout_p):
 def dropout_mask(N, H, L, S, dropout_p, seed, salt):
     """(N*H, L, S) uint8 keep mask of the call with this seed tensor and salt (tests)."""
     mask = torch.empty((N * H, L, S), device=seed.device, dtype=torch.uint8)
-    _call(_lib.omnipq_attn_dropout_mask, mask, N, H, L, S, ctypes.c_float(dropout_p), _p(seed), salt, _p(mask))
+    _call(_lib.omnipq_attn_dropout_mask, mask, N, H, L, S, dropout_p, _p(seed), salt, _p(mask))
     return mask
 
 
@@ -116,7 +116,7 @@ class PackedAttention(torch.autograd.Function):
         salt = STATE.next_salt() if dropout_p > 0 else 0
         strides = (ctypes.c_longlong * 8)(*(st + [E, L * E]))
         _call(_lib.omnipq_attn_fwd, a, N, H, L, S, D, ctypes.c_void_p(qp), ctypes.c_void_p(kp), ctypes.c_void_p(vp),
-              _p(o), strides, _p(lse), ctypes.c_float(dropout_p), _p(seed), salt)
+              _p(o), strides, _p(lse), dropout_p, _p(seed), salt)
         ctx.save_for_backward(a, b, o, lse)
         ctx.cfg = (L, S, N, H, dropout_p, seed, salt)
         return o
@@ -138,7 +138,7 @@ class PackedAttention(torch.autograd.Function):
         gstrides = (ctypes.c_longlong * 6)(*gst)
         _call(_lib.omnipq_attn_bwd, a, N, H, L, S, D, ctypes.c_void_p(qp), ctypes.c_void_p(kp), ctypes.c_void_p(vp),
               _p(o), _p(d_o), strides, _p(lse), _p(delta), ctypes.c_void_p(dqp), ctypes.c_void_p(dkp),
-              ctypes.c_void_p(dvp), gstrides, ctypes.c_float(dropout_p), _p(seed), salt)
+              ctypes.c_void_p(dvp), gstrides, dropout_p, _p(seed), salt)
         return da, db, None, None, None, None, None
 
 

@@ -44,7 +44,6 @@ class VoteDecode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, seed_xyz, seed_features):
         ctx.e16 = E16.dtype
-        import ctypes
         import sa_fused
         B, K, _ = seed_xyz.shape
         C = seed_features.shape[1]
@@ -58,7 +57,7 @@ class VoteDecode(torch.autograd.Function):
             # and the (B, C, K) output is a view of the twin
             twin = torch.empty((B, K, C), device=dev, dtype=E16.dtype)
             norm = torch.empty((B, K), device=dev, dtype=torch.float32)
-            sa_fused._call(sa_fused._lib.omnipq_vote_decode_rows, net, ctypes.c_longlong(B * K), C, sa_fused._p(net),
+            sa_fused._call(sa_fused._lib.omnipq_vote_decode_rows, net, B * K, C, sa_fused._p(net),
                            net.stride(0), sa_fused._p(sx), sa_fused._p(sf.transpose(1, 2)), sa_fused._p(vote_xyz),
                            sa_fused._p(twin), sa_fused._p(norm))
             out = twin.transpose(1, 2)
@@ -71,8 +70,8 @@ class VoteDecode(torch.autograd.Function):
         twin = torch.empty((B, K, C), device=dev, dtype=E16.dtype)
         norm = torch.empty((B, K), device=dev, dtype=torch.float32)
         sa_fused._call(sa_fused._lib.omnipq_vote_decode, net, B, K, C, sa_fused._p(net), net.stride(0), sa_fused._p(sx),
-                       sa_fused._p(sf), int(bf), ctypes.c_longlong(sf.stride(0)), ctypes.c_longlong(sf.stride(1)),
-                       ctypes.c_longlong(sf.stride(2)), sa_fused._p(vote_xyz), sa_fused._p(out), sa_fused._p(twin),
+                       sa_fused._p(sf), int(bf), sf.stride(0), sf.stride(1),
+                       sf.stride(2), sa_fused._p(vote_xyz), sa_fused._p(out), sa_fused._p(twin),
                        sa_fused._p(norm))
         ctx.save_for_backward(out, norm, twin)
         ctx.geom = (B, K, C, net.shape[1], bf)
@@ -91,14 +90,13 @@ class VoteDecode(torch.autograd.Function):
                 (g_feat is None or (g_feat.dtype == E16.dtype and tuple(g_feat.shape) == (B, C, K))):
             # everything position-major: the incoming gradient is a (B, C, K) view of rows already (the vote aggregation's
             # backward) or is made one, the seed gradient goes back as such a view (what FanOut adds as rows)
-            import ctypes
             g_rows = None
             if g_feat is not None:
                 g_rows = g_feat.transpose(1, 2)
                 g_rows = g_rows if g_rows.is_contiguous() else g_rows.contiguous()
             dnet = torch.empty((B * K, ld), device=out.device, dtype=E16.dtype)
             dseed = torch.empty((B, K, C), device=out.device, dtype=E16.dtype) if ctx.needs_input_grad[2] else None
-            sa_fused._call(sa_fused._lib.omnipq_vote_decode_bwd_rows, twin, ctypes.c_longlong(B * K), C, sa_fused._p(twin),
+            sa_fused._call(sa_fused._lib.omnipq_vote_decode_bwd_rows, twin, B * K, C, sa_fused._p(twin),
                            sa_fused._p(norm), sa_fused._p(g_xyz), sa_fused._p(g_rows), sa_fused._p(dnet), ld,
                            sa_fused._p(dseed))
             return dnet, (g_xyz if ctx.needs_input_grad[1] else None), (None if dseed is None else dseed.transpose(1, 2))

@@ -42,7 +42,7 @@ class _NNDistance(torch.autograd.Function):
         dist2 = torch.empty((B, M), device=a.device)
         idx1 = torch.empty((B, N), device=a.device, dtype=torch.int64)
         idx2 = torch.empty((B, M), device=a.device, dtype=torch.int64)
-        _ext._run(_lib.omnipq_nn_distance, a, B, N, M, C, mode, ctypes.c_float(delta), _ext._ptr(a), _ext._ptr(b),
+        _ext._run(_lib.omnipq_nn_distance, a, B, N, M, C, mode, delta, _ext._ptr(a), _ext._ptr(b),
                   _ext._ptr(dist1), _ext._ptr(idx1), _ext._ptr(dist2), _ext._ptr(idx2))
         ctx.save_for_backward(a, b, idx1, idx2)
         ctx.cfg = (mode, delta, pc1.dtype, pc2.dtype)
@@ -59,7 +59,7 @@ class _NNDistance(torch.autograd.Function):
         g2 = None if g2 is None else g2.float().contiguous()
         da, db = torch.empty_like(a), torch.empty_like(b)
         null = ctypes.c_void_p(0)
-        _ext._run(_lib.omnipq_nn_distance_grad, a, B, N, M, C, mode, ctypes.c_float(delta), _ext._ptr(a), _ext._ptr(b),
+        _ext._run(_lib.omnipq_nn_distance_grad, a, B, N, M, C, mode, delta, _ext._ptr(a), _ext._ptr(b),
                   _ext._ptr(idx1), _ext._ptr(idx2), null if g1 is None else _ext._ptr(g1),
                   null if g2 is None else _ext._ptr(g2), _ext._ptr(da), _ext._ptr(db))
         return da.to(dt1), db.to(dt2), None, None

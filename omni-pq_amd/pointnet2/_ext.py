@@ -27,26 +27,49 @@ if not os.path.exists(_LIB_PATH):
         f"pointnet2._ext: {_LIB_PATH} not found -- build it with `python omni-pq_amd/build.py` "
         "(hipcc --offload-arch=gfx950).  There is no CPU or PyTorch fallback for these operators.")
 
-ABI_VERSION = 4          # include/omnipq_pointops.h: OMNIPQ_ABI_VERSION
+ABI_VERSION = 5          # include/omnipq_pointops.h: OMNIPQ_ABI_VERSION
+
+# omnipq_entry_point_signatures(): one letter per type (include/omnipq_pointops.h); `P` is `const omnipq_row_plan *`
+_CTYPE = {"i": ctypes.c_int, "u": ctypes.c_uint, "l": ctypes.c_longlong, "f": ctypes.c_float, "d": ctypes.c_double,
+          "p": ctypes.c_void_p, "P": ctypes.c_void_p, "v": None, "s": ctypes.c_char_p}
 
 
 def _load(path):
+    """-> (library, its signature text).  Every entry point the library lists gets its `restype` and `argtypes` here, once:
+    a plain Python number then arrives in the width the C side reads, a mistyped or missing argument raises before anything
+    is launched, and no caller declares anything."""
     lib = ctypes.CDLL(path)
-    lib.omnipq_error_string.restype = ctypes.c_char_p
     lib.omnipq_abi_version.restype = ctypes.c_int
     if lib.omnipq_abi_version() != ABI_VERSION:
         raise ImportError(f"pointnet2._ext: {path} reports ABI version {lib.omnipq_abi_version()}, this binding is written "
                           f"against {ABI_VERSION} (include/omnipq_pointops.h) -- rebuild with `python omni-pq_amd/build.py`")
-    lib.omnipq_plan_aware_entry_points.restype = ctypes.c_char_p
-    return lib
+    lib.omnipq_entry_point_signatures.restype = ctypes.c_char_p
+    text = lib.omnipq_entry_point_signatures().decode()
+    for name, ret, params in _signatures(text):
+        fn = getattr(lib, name)
+        fn.restype = _CTYPE[ret]
+        fn.argtypes = [_CTYPE[c] for c in params]
+    return lib, text
+
+
+def _signatures(text):
+    """(name, return letter, parameter letters) per line of the library's text; `(void)` has no third field"""
+    for line in text.splitlines():
+        name, ret, *params = line.split()
+        yield name, ret, params[0] if params else ""
 
 
 # The library is built once per 16-bit element type (omni-pq_amd/build.py, csrc/common.h: e16_t): bfloat16 in
 # libomnipq_pointops.so -- which also serves every index / f32 operator below -- and IEEE half in its `_f16` twin.
 _LIB_F16_PATH = _LIB_PATH[:-3] + "_f16.so"
-_LIBS = {torch.bfloat16: _load(_LIB_PATH)}
+_lib0, _SIGNATURES = _load(_LIB_PATH)        # element-type independent entry points (index ops, FPS state) always live here
+_LIBS = {torch.bfloat16: _lib0}
 if os.path.exists(_LIB_F16_PATH):
-    _LIBS[torch.float16] = _load(_LIB_F16_PATH)
+    _LIBS[torch.float16], _text = _load(_LIB_F16_PATH)
+    if _text != _SIGNATURES:
+        raise ImportError("pointnet2._ext: the bf16 and f16 libraries were built from different headers")
+# which entry points take a row plan in front of the stream: the loaded libraries say so themselves (build-time text)
+PLAN_AWARE = frozenset(name for name, _, params in _signatures(_SIGNATURES) if "P" in params)
 
 
 class _Elem16(threading.local):
@@ -89,14 +112,20 @@ E16 = _Elem16()
 
 
 class _Entry:
-    """One C-ABI entry point, resolved at call time in the library of the current element type."""
-    __slots__ = ("__name__", "_fns")
+    """One C-ABI entry point, resolved at call time in the library of the current element type.  ctypes itself refuses a
+    call with fewer arguments than `argtypes` but passes extra ones on in silence, so the count is compared here."""
+    __slots__ = ("__name__", "_fns", "_nargs")
 
     def __init__(self, name):
         self.__name__ = name
         self._fns = {dt: getattr(lib, name) for dt, lib in _LIBS.items()}
+        if self.argtypes is None:
+            raise AttributeError(f"pointnet2._ext: the library lists no entry point {name} (include/*.h of its build)")
+        self._nargs = len(self.argtypes)
 
     def __call__(self, *args):
+        if len(args) != self._nargs:
+            raise TypeError(f"{self.__name__} takes {self._nargs} arguments ({len(args)} given)")
         return self._fns[E16.dtype](*args)
 
     @property
@@ -116,6 +145,7 @@ class _Entry:
     def argtypes(self, value):
         for fn in self._fns.values():
             fn.argtypes = value
+        self._nargs = len(value)
 
 
 class _Libs:
@@ -126,13 +156,6 @@ class _Libs:
 
 
 _lib = _Libs()
-# which entry points take a row plan in front of the stream: the loaded libraries say so themselves (build-time list)
-PLAN_AWARE = frozenset(_LIBS[torch.bfloat16].omnipq_plan_aware_entry_points().decode().split())
-for _l in _LIBS.values():
-    if frozenset(_l.omnipq_plan_aware_entry_points().decode().split()) != PLAN_AWARE:
-        raise ImportError("pointnet2._ext: the bf16 and f16 libraries were built from different headers")
-_lib0 = _LIBS[torch.bfloat16]        # element-type independent entry points (index ops, FPS state) always live here
-
 LIB_PATH = _LIB_PATH
 LIB_F16_PATH = _LIB_F16_PATH if torch.float16 in _LIBS else None
 
@@ -280,7 +303,7 @@ def furthest_point_sampling(points, nsamples, out=None, small_footprint=False):
         assert tuple(out.shape) == (b, int(nsamples))
     tmp = torch.full((b, n), 1e10, device=points.device, dtype=torch.float32)
     _run(_lib0.omnipq_furthest_point_sampling_ex, points, b, n, int(nsamples), _ptr(points), _ptr(tmp), _ptr(out),
-         ctypes.c_uint(1 if small_footprint else 0))          # flags: OMNIPQ_FPS_SMALL_FOOTPRINT
+         1 if small_footprint else 0)          # flags: OMNIPQ_FPS_SMALL_FOOTPRINT
     return out
 
 
@@ -304,7 +327,7 @@ def furthest_point_sampling_resume(points, idx, temp, first, count, small_footpr
     if first < 0 or count < 0 or first + count > m:
         raise ValueError(f"furthest_point_sampling_resume: rounds [{first}, {first + count}) outside [0, {m})")
     _run(_lib0.omnipq_furthest_point_sampling_resume, points, b, n, m, first, count, _ptr(points), _ptr(temp), _ptr(idx),
-         ctypes.c_uint(1 if small_footprint else 0))          # flags: OMNIPQ_FPS_SMALL_FOOTPRINT
+         1 if small_footprint else 0)          # flags: OMNIPQ_FPS_SMALL_FOOTPRINT
     return idx
 
 
@@ -369,7 +392,6 @@ def three_interpolate_grad(grad_out, idx, weight, m):
 
 
 _BQ_GRID_MIN = 8192      # points per scene from which the grid pays
-_lib0.omnipq_ball_query_grid_workspace_bytes.restype = ctypes.c_longlong
 
 
 def ball_query(new_xyz, xyz, radius, nsample, out=None):
@@ -390,10 +412,10 @@ def ball_query(new_xyz, xyz, radius, nsample, out=None):
         # large clouds: the same indices through a hash grid (csrc/ball_query.hip) instead of n tests per centre
         ws = torch.empty((int(_lib0.omnipq_ball_query_grid_workspace_bytes(b, n)),), device=new_xyz.device,
                          dtype=torch.uint8)
-        _run(_lib0.omnipq_ball_query_grid, new_xyz, b, n, m, ctypes.c_float(radius), int(nsample), _ptr(new_xyz),
+        _run(_lib0.omnipq_ball_query_grid, new_xyz, b, n, m, float(radius), int(nsample), _ptr(new_xyz),
              _ptr(xyz), _ptr(idx), _ptr(ws))
         return idx
-    _run(_lib0.omnipq_ball_query, new_xyz, b, n, m, ctypes.c_float(radius), int(nsample), _ptr(new_xyz),
+    _run(_lib0.omnipq_ball_query, new_xyz, b, n, m, float(radius), int(nsample), _ptr(new_xyz),
          _ptr(xyz), _ptr(idx))
     return idx
 

@@ -13,15 +13,12 @@ counterpart for CUDA f32 tensors -- it is what the f32 parity tests (1e-4 agains
 Each is one autograd node with a hand-written backward.  `enabled(x)` says whether a tensor takes this path; otherwise
 callers keep PyTorch's own layers (CPU tensors, autocast, HANDWRITTEN_F32 = False).
 """
-import ctypes
-
 import torch
 import torch.nn.functional as F
 
 import sa_fused
 from sa_fused import E16, _allreduce_, _call, _lib, _p, _round_up, _world
 
-_lib.omnipq_gemm_tn_workspace_floats.restype = ctypes.c_longlong
 
 HANDWRITTEN_F32 = True         # False: PyTorch's library kernels in f32 mode (the tests compare the two)
 
@@ -36,7 +33,7 @@ def _split(x2d, cols_pad, side, stacked):
         x2d = x2d.contiguous()
     shape = (6 * rows, cols_pad) if stacked else (rows, 6 * cols_pad)
     out = torch.empty(shape, device=x2d.device, dtype=torch.bfloat16)
-    _call(_lib.omnipq_split3_e16, x2d, ctypes.c_longlong(rows), cols, ctypes.c_longlong(x2d.stride(0)), _p(x2d), cols_pad,
+    _call(_lib.omnipq_split3_e16, x2d, rows, cols, x2d.stride(0), _p(x2d), cols_pad,
           side, int(stacked), _p(out))
     return out
 
@@ -92,7 +89,7 @@ class _Linear(torch.autograd.Function):
         db = None
         if ctx.has_bias and ctx.needs_input_grad[2]:
             sums = torch.zeros((2, g.shape[1]), device=g.device, dtype=torch.float64)
-            _call(_lib.omnipq_colstats_f32, g, ctypes.c_longlong(g.shape[0]), g.shape[1], _p(g), _p(sums))
+            _call(_lib.omnipq_colstats_f32, g, g.shape[0], g.shape[1], _p(g), _p(sums))
             db = sums[0].float()
         return dx, dw, db
 
@@ -178,10 +175,10 @@ class _BNAct(torch.autograd.Function):
         world = (_world() if sync else 1) if training else 1
         if training:
             sums = torch.zeros((2, C), device=dev, dtype=torch.float64)
-            _call(_lib.omnipq_colstats_f32, y, ctypes.c_longlong(P), C, _p(y), _p(sums))
+            _call(_lib.omnipq_colstats_f32, y, P, C, _p(y), _p(sums))
             _allreduce_(sums, world)
-            _call(_lib.omnipq_bn_finalize, y, C, ctypes.c_double(float(P) * world), _p(sums), _p(gamma.detach()),
-                  _p(beta.detach()), ctypes.c_float(eps), ctypes.c_float(momentum), _p(rm), _p(rv), _p(a), _p(b), _p(mean),
+            _call(_lib.omnipq_bn_finalize, y, C, float(P) * world, _p(sums), _p(gamma.detach()),
+                  _p(beta.detach()), eps, momentum, _p(rm), _p(rv), _p(a), _p(b), _p(mean),
                   _p(invstd), _p(conv_bias))
             sa_fused.bump(nbt)
         else:
@@ -190,7 +187,7 @@ class _BNAct(torch.autograd.Function):
             a.copy_(gamma.detach() * invstd)
             b.copy_(beta.detach() - rm * a)
         x = torch.empty_like(y)
-        _call(_lib.omnipq_bn_act_f32, y, ctypes.c_longlong(P), C, _p(y), _p(a), _p(b), int(relu), _p(x))
+        _call(_lib.omnipq_bn_act_f32, y, P, C, _p(y), _p(a), _p(b), int(relu), _p(x))
         ctx.save_for_backward(y, stats)
         ctx.cfg = (training, relu, world)
         return x
@@ -203,17 +200,17 @@ class _BNAct(torch.autograd.Function):
         a, b, mean, invstd = stats[0], stats[1], stats[2], stats[3]
         g = g.contiguous()
         sums = torch.zeros((2, C), device=y.device, dtype=torch.float64)
-        _call(_lib.omnipq_bn_bwd_stats_f32, y, ctypes.c_longlong(P), C, _p(g), _p(y), _p(a), _p(b), _p(mean), _p(invstd),
+        _call(_lib.omnipq_bn_bwd_stats_f32, y, P, C, _p(g), _p(y), _p(a), _p(b), _p(mean), _p(invstd),
               int(relu), _p(sums))
         dbeta, dgamma = sums[0].float(), sums[1].float()              # this rank's share (DDP averages parameters' gradients)
         dy = torch.empty_like(y)
         if training:
             _allreduce_(sums, world)
-            _call(_lib.omnipq_bn_bwd_apply_f32, y, ctypes.c_longlong(P), C, _p(g), _p(y), _p(a), _p(b), _p(mean), _p(invstd),
-                  _p(sums), ctypes.c_double(1.0 / (float(P) * world)), int(relu), _p(dy))
+            _call(_lib.omnipq_bn_bwd_apply_f32, y, P, C, _p(g), _p(y), _p(a), _p(b), _p(mean), _p(invstd),
+                  _p(sums), 1.0 / (float(P) * world), int(relu), _p(dy))
         else:
-            _call(_lib.omnipq_bn_bwd_apply_f32, y, ctypes.c_longlong(P), C, _p(g), _p(y), _p(a), _p(b), _p(mean), _p(invstd),
-                  _p(None), ctypes.c_double(0.0), int(relu), _p(dy))
+            _call(_lib.omnipq_bn_bwd_apply_f32, y, P, C, _p(g), _p(y), _p(a), _p(b), _p(mean), _p(invstd),
+                  _p(None), 0.0, int(relu), _p(dy))
         return dy, dgamma, dbeta, None, None, None, None, None, None, None, None, None
 
 

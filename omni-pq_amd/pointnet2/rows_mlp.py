@@ -16,7 +16,6 @@ mean accounts for it (and its gradient is exactly zero).
 
 Used under `torch.autocast("cuda", dtype=torch.bfloat16)` (or float16: sa_fused.E16); otherwise callers keep PyTorch's f32 layers.
 """
-import ctypes
 import os
 
 import torch
@@ -83,9 +82,6 @@ class _L:
     __slots__ = ("act", "K", "C", "Cp", "Wp", "Wt", "wk", "a", "b", "mean", "invstd", "Y", "X", "has_bn", "has_bias", "fin")
 
 
-_lib.omnipq_pair_hold.restype = None
-_lib.omnipq_pair_flush.restype = ctypes.c_longlong
-_lib.omnipq_pair_held.restype = ctypes.c_int
 
 
 def _hold(lead):
@@ -154,7 +150,7 @@ def _forward_program(ctx, lead, x, spec, training, params):
                 X = x.detach().to(E16.dtype).contiguous()
             elif x.dtype in (torch.float32, E16.dtype) and x.stride(1) == 1:
                 X = torch.empty((N, K), device=x.device, dtype=E16.dtype)          # cast + zero padding in one launch
-                _call(_lib.omnipq_pad_rows_e16, x, ctypes.c_longlong(N), cin, K, ctypes.c_longlong(x.stride(0)), _p(x),
+                _call(_lib.omnipq_pad_rows_e16, x, N, cin, K, x.stride(0), _p(x),
                       int(x.dtype == torch.float32), _p(X))
             else:
                 X = torch.nn.functional.pad(x.detach().to(E16.dtype), (0, K - cin))
@@ -204,7 +200,7 @@ def _forward_program(ctx, lead, x, spec, training, params):
                     # ReLU + dropout in the GEMM's epilogue (same decisions as omnipq_relu_dropout on the stored matrix)
                     _, p_act, seed_act, salt_act = lay.act
                     _call(_lib.omnipq_gemm_nt_e16_relu_dropout, X, N, lay.Cp, K, _p(X), K, _p(lay.Wp), K, _p(Y), lay.Cp,
-                          _p(bp), ctypes.c_float(p_act), _p(seed_act), salt_act)
+                          _p(bp), p_act, _p(seed_act), salt_act)
                     act_fused = True
                 else:
                     sa_fused.gemm_nt_into(X, lay.Wp, Y, N, lay.Cp, K, bias=bp)
@@ -225,8 +221,8 @@ def _forward_program(ctx, lead, x, spec, training, params):
                         lay.X = None
                     else:
                         lay.X = torch.empty_like(Y)
-                        _call(_lib.omnipq_bn_finalize_relu, Y, ctypes.c_longlong(N), cout, ctypes.c_double(float(N) * world),
-                              _p(sums), _p(gamma.detach()), _p(beta.detach()), ctypes.c_float(eps), ctypes.c_float(momentum),
+                        _call(_lib.omnipq_bn_finalize_relu, Y, N, cout, float(N) * world,
+                              _p(sums), _p(gamma.detach()), _p(beta.detach()), eps, momentum,
                               _p(rm), _p(rv), _p(cb), _p(Y), _p(lay.X), _p(lay.a), _p(lay.b), _p(lay.mean), _p(lay.invstd))
                     sa_fused.bump(nbt)
                 else:
@@ -237,12 +233,12 @@ def _forward_program(ctx, lead, x, spec, training, params):
                     lay.b = (beta.detach() - shift * lay.a).contiguous()
                 if not training:
                     lay.X = torch.empty_like(Y)
-                    _call(_lib.omnipq_bnrelu, Y, ctypes.c_longlong(N), cout, _p(Y), _p(lay.a), _p(lay.b), _p(lay.X))
+                    _call(_lib.omnipq_bnrelu, Y, N, cout, _p(Y), _p(lay.a), _p(lay.b), _p(lay.X))
                 X = lay.X
             else:
                 if lay.act is not None and not act_fused:
                     _, p, seed, salt = lay.act
-                    _call(_lib.omnipq_relu_dropout, Y, ctypes.c_longlong(N * lay.Cp), _p(Y), ctypes.c_float(p),
+                    _call(_lib.omnipq_relu_dropout, Y, N * lay.Cp, _p(Y), p,
                           _p(seed), salt)
                 lay.X = Y
                 X = Y
@@ -269,7 +265,7 @@ def _backward_program(ctx, lead, g, needs_input_grad):
         layers = ctx.layers
         L = len(layers)
         dev = g.device
-        total = ctypes.c_double(float(N) * world)
+        total = float(N) * world
         grads = [None] * (4 * L)
         last = layers[-1]
         if last.Cp == last.C or ctx.padded:
@@ -294,7 +290,7 @@ def _backward_program(ctx, lead, g, needs_input_grad):
             if lay.has_bn:
                 if sums is None:
                     sums, slot = sa_fused.pair_sums(lead, 3, lay.C, dev, world)
-                    _call(_lib.omnipq_bn_bwd_stats_z, dcur, ctypes.c_longlong(N), lay.C, _p(dcur), _p(lay.Y),
+                    _call(_lib.omnipq_bn_bwd_stats_z, dcur, N, lay.C, _p(dcur), _p(lay.Y),
                           _p(lay.a), _p(lay.b), _p(lay.mean), _p(lay.invstd), _p(sums))
                     if sa_fused.PairStats.active is not None and (world > 1 or sa_fused._FORCE_COLLECTIVES):
                         yield              # the partner's statistics kernel goes out before the exchange both share
@@ -309,8 +305,8 @@ def _backward_program(ctx, lead, g, needs_input_grad):
             elif lay.act is not None and act_masked != l:
                 # lay.Y holds dropout(relu(.)): positive exactly where the unit was active and kept
                 dst = dcur if owned else torch.empty_like(dcur)
-                _call(_lib.omnipq_relu_dropout_bwd, dcur, ctypes.c_longlong(N * lay.Cp), _p(lay.Y), _p(dcur), _p(dst),
-                      ctypes.c_float(lay.act[1]))
+                _call(_lib.omnipq_relu_dropout_bwd, dcur, N * lay.Cp, _p(lay.Y), _p(dcur), _p(dst),
+                      lay.act[1])
                 dcur, owned = dst, True
             want_bias = not lay.has_bn and lay.has_bias
             wt, bt = ctx.targets[l] if (dfr is not None and ctx.targets is not None) else (None, None)
@@ -338,7 +334,7 @@ def _backward_program(ctx, lead, g, needs_input_grad):
                 if l > 0 and layers[l - 1].act is not None and _FUSE_ACT and lay.Cp < 1024:
                     # the layer below is dropout(relu(.)): its backward mask in this GEMM's epilogue
                     _call(_lib.omnipq_gemm_nt_e16_mask, dcur, N, lay.K, lay.Cp, _p(dcur), lay.Cp, _p(lay.Wt), lay.Cp,
-                          _p(dprev), lay.K, _p(layers[l - 1].Y), ctypes.c_float(layers[l - 1].act[1]))
+                          _p(dprev), lay.K, _p(layers[l - 1].Y), layers[l - 1].act[1])
                     act_masked = l - 1
                 else:
                     sa_fused.gemm_nt_into(dcur, lay.Wt, dprev, N, lay.K, lay.Cp)

@@ -29,11 +29,8 @@ import pointnet2_utils
 _ext = pointnet2_utils._load_ext()      # always the product binding, whatever pointnet2_utils._ext is
 _lib = _ext._lib
 E16 = _ext.E16                         # the 16-bit element type the hand-written kernels run in (bfloat16 / float16)
-_lib.omnipq_gemm_tn_workspace_floats.restype = ctypes.c_longlong
 if os.environ.get("OMNIPQ_TN_DEBUG"):          # A/B runs only: bit 0 = the register-prefetch program of the weight-gradient kernels
     _lib.omnipq_tn_debug(int(os.environ["OMNIPQ_TN_DEBUG"]))
-_lib.omnipq_gemm_nt_stats_workspace_floats.restype = ctypes.c_longlong
-_lib.omnipq_gemm_nt_workspace_floats.restype = ctypes.c_longlong
 
 
 def _p(t):
@@ -55,7 +52,7 @@ class RowPlanArg(ctypes.Structure):
                 ("rows", ctypes.c_longlong), ("gs", ctypes.c_int), ("pool_gamma", ctypes.c_void_p)]
 
 
-PLAN_AWARE = _ext.PLAN_AWARE      # asked of the loaded library (omnipq_plan_aware_entry_points), not parsed from a header
+PLAN_AWARE = _ext.PLAN_AWARE      # asked of the loaded library (omnipq_entry_point_signatures), not parsed from a header
 
 
 # Measuring the SA stages INSIDE the replayed step.  A hipGraph replay cannot host timing events
@@ -340,7 +337,7 @@ def make_row_plan(idx, P, into=None):
     else:
         plan.goff, plan.rows_dev, plan.unit_src, plan.row_w = plan_views(into, B, M, P)
     plan.scratch = torch.empty((B * M,), device=dev, dtype=torch.int32)
-    _call(_lib.omnipq_sa_ball_plan_src, idx, ctypes.c_longlong(B * M), S, plan.gs, _p(idx), _p(plan.goff), _p(plan.rows_dev),
+    _call(_lib.omnipq_sa_ball_plan_src, idx, B * M, S, plan.gs, _p(idx), _p(plan.goff), _p(plan.rows_dev),
           _p(plan.row_w), _p(plan.unit_src), _p(plan.scratch))
     if KEEP_LAST_PLANS:
         row_plan_last[P] = plan
@@ -440,13 +437,13 @@ def gemm_nt_affine(Y, below, Bw, M, N, K, sums=None, bias=None, out=None, pool=N
         below.fin = None
         if pool is not None:
             S, ymax, ymin, amax, amin = pool
-            _call(_lib.omnipq_gemm_nt_e16_bnaffine_pool, Y, M, N, K, _p(Y), K, _p(fsums), ctypes.c_double(count),
-                  _p(gamma), _p(beta), ctypes.c_float(eps), ctypes.c_float(momentum), _p(rm), _p(rv), _p(cb), _p(below.a),
+            _call(_lib.omnipq_gemm_nt_e16_bnaffine_pool, Y, M, N, K, _p(Y), K, _p(fsums), count,
+                  _p(gamma), _p(beta), eps, momentum, _p(rm), _p(rv), _p(cb), _p(below.a),
                   _p(below.b), _p(below.mean), _p(below.invstd), _p(Bw), K, _p(C), N, _p(bias), _p(sums), _p(ws), S,
                   _p(ymax), _p(ymin), _p(amax), _p(amin))
             return C
-        _call(_lib.omnipq_gemm_nt_e16_bnaffine, Y, M, N, K, _p(Y), K, _p(fsums), ctypes.c_double(count), _p(gamma),
-              _p(beta), ctypes.c_float(eps), ctypes.c_float(momentum), _p(rm), _p(rv), _p(cb), _p(below.a), _p(below.b),
+        _call(_lib.omnipq_gemm_nt_e16_bnaffine, Y, M, N, K, _p(Y), K, _p(fsums), count, _p(gamma),
+              _p(beta), eps, momentum, _p(rm), _p(rv), _p(cb), _p(below.a), _p(below.b),
               _p(below.mean), _p(below.invstd), _p(Bw), K, _p(C), N, _p(bias), _p(sums), _p(ws))
         return C
     if pool is not None:
@@ -463,8 +460,6 @@ def gemm_nt_affine(Y, below, Bw, M, N, K, sums=None, bias=None, out=None, pool=N
 # XYZGEN = False restores the stored first layer (tests compare the two).
 XYZGEN = True
 xyzgen_uses = 0            # forwards that took the path (tests check that it is the one that ran)
-_lib.omnipq_gemm_nt_xyz_workspace_floats.restype = ctypes.c_longlong
-_lib.omnipq_sa_l1_rows_workspace_bytes.restype = ctypes.c_longlong
 
 
 def xyzgen_ok(P, L, c0, needs_input_grad):
@@ -501,7 +496,6 @@ LAST_NO_DY_MAX_C3 = 256         # ... for last layers up to this width: sa1 (128
                                 # 30-90 us (per-stage split of the bench line: sa2 0.69 -> 0.78 ms with it); 1 << 30 = every planned stage
 LAST_X2 = True                  # ... and its weight gradient contracts X2 as the data-gradient launch left it (no affine per fragment)
 last_no_dy_uses = 0
-_lib.omnipq_gemm_tn_dz_workspace_floats.restype = ctypes.c_longlong
 
 
 def last_no_dy_ok(plan, L, P, c2, c3, S, below_keeps_y_only):
@@ -544,7 +538,7 @@ def gemm_nt_xyz(X0c, below, Bw, M, N, K, sums):
     fsums, count, gamma, beta, eps, momentum, rm, rv, _ = below.fin
     below.fin = None
     _call(_lib.omnipq_gemm_nt_e16_xyz_bnaffine, X0c, M, N, K, _p(X0c), X0c.shape[1], _p(below.Wp), below.Wp.shape[1],
-          _p(fsums), ctypes.c_double(count), _p(gamma), _p(beta), ctypes.c_float(eps), ctypes.c_float(momentum), _p(rm),
+          _p(fsums), count, _p(gamma), _p(beta), eps, momentum, _p(rm),
           _p(rv), _p(below.a), _p(below.b), _p(below.mean), _p(below.invstd), _p(Bw), K, _p(C), N, _p(sums), _p(ws))
     return C
 
@@ -584,7 +578,6 @@ class _TnProblem(ctypes.Structure):
                 ("rows_dev", ctypes.c_void_p)]
 
 
-_lib.omnipq_gemm_tn_grouped_workspace_floats.restype = ctypes.c_longlong
 
 
 _ZERO_TAILS = {}
@@ -1244,7 +1237,7 @@ def bn_backward_apply(d, lay, P, C, total, sums, world, out=None, pair=None):
     else:
         gb = torch.empty((2, C), device=d.device, dtype=torch.float32)
         dgamma, dbeta = gb[1], gb[0]
-    _call(_lib.omnipq_bn_bwd_apply_fused, d, ctypes.c_longlong(P), C, total, _p(d), _p(lay.Y), _p(lay.a), _p(lay.b),
+    _call(_lib.omnipq_bn_bwd_apply_fused, d, P, C, total, _p(d), _p(lay.Y), _p(lay.a), _p(lay.b),
           _p(lay.mean), _p(lay.invstd), _p(sums), _p(d if out is None else out), _p(gb))
     return dgamma, dbeta
 
@@ -1337,7 +1330,7 @@ class FusedSAStage(torch.autograd.Function):
         with _row_plan(plan, P):
             # (with a plan: the gather writes the compact row space, every launch below works on the rows in use)
             if not hoist:
-                _call(_lib.omnipq_sa_gather, xyz_c, B, N, M, S, cin, xpad, ctypes.c_float(inv_r), _p(xyz_c), _p(cen_c),
+                _call(_lib.omnipq_sa_gather, xyz_c, B, N, M, S, cin, xpad, inv_r, _p(xyz_c), _p(cen_c),
                       _p(idx), _p(feat_pm), _p(X))
             X0 = X
             layers, pool, X = FusedSAStage._forward_layers(ctx, params, bn_cfg, L, X, X0, P, B, M, S, cin, cin_raw, kpad,
@@ -1383,7 +1376,7 @@ class FusedSAStage(torch.autograd.Function):
                 if xgen and l == 0:
                     # never materialised (see XYZGEN): statistics from the moments of the grouped coordinates
                     lay.mom = torch.empty((12,), device=dev, dtype=torch.float64)
-                    _call(_lib.omnipq_sa_xyz_moments, X, ctypes.c_longlong(P), _p(X), xpad, _p(lay.mom))
+                    _call(_lib.omnipq_sa_xyz_moments, X, P, _p(X), xpad, _p(lay.mom))
                     _call(_lib.omnipq_sa_xyz_stats, X, cout, _p(lay.Wp), K, _p(lay.mom), _p(sums))
                     lay.Y = None
                 elif l == 0 and getattr(ctx, "hoist", None) is not None:
@@ -1396,7 +1389,7 @@ class FusedSAStage(torch.autograd.Function):
                     nws = int(_lib.omnipq_sa_l1_rows_workspace_bytes(B, hM, hS, cout))
                     ws_ = torch.empty((nws // 4,), device=dev, dtype=torch.float32)
                     tk_ = zeros_f32(nws // (8 * cout * 16) + 1, dev)          # one zero word per 16 workgroups
-                    _call(_lib.omnipq_sa_l1_rows, Z, B, hN, hM, hS, cout, ctypes.c_float(hinv), _p(hx), _p(hc), _p(hidx), _p(Z),
+                    _call(_lib.omnipq_sa_l1_rows, Z, B, hN, hM, hS, cout, hinv, _p(hx), _p(hc), _p(hidx), _p(Z),
                           ctypes.c_void_p(lay.Wp.data_ptr() + cin * lay.Wp.element_size()), K,
                           _p(plan.rows_dev if plan is not None else None), _p(plan.unit_src if plan is not None else None),
                           _p(plan.row_w if plan is not None else None), _p(lay.Y), _p(Xrel), _p(sums), _p(ws_), _p(tk_))
@@ -1427,16 +1420,16 @@ class FusedSAStage(torch.autograd.Function):
                 elif fused_relu:
                     # finalize + normalise + ReLU in one launch
                     lay.X = torch.empty_like(lay.Y)
-                    _call(_lib.omnipq_bn_finalize_relu, lay.Y, ctypes.c_longlong(P), cout, ctypes.c_double(float(P) * world),
-                          _p(sums), _p(gamma.detach()), _p(beta.detach()), ctypes.c_float(eps), ctypes.c_float(momentum),
+                    _call(_lib.omnipq_bn_finalize_relu, lay.Y, P, cout, float(P) * world,
+                          _p(sums), _p(gamma.detach()), _p(beta.detach()), eps, momentum,
                           _p(rm), _p(rv), _p(None), _p(lay.Y), _p(lay.X), _p(lay.a), _p(lay.b), _p(lay.mean),
                           _p(lay.invstd))
                 elif _FOLD_SMALL and l == L - 1 and pool is not None and cout <= 1024:
                     # the last layer: finalised inside omnipq_sa_pool_select_finalize below
                     lay.fin = (sums, float(P) * world, gamma.detach(), beta.detach(), eps, momentum, rm, rv, None)
                 else:
-                    _call(_lib.omnipq_bn_finalize, sums, cout, ctypes.c_double(float(P) * world), _p(sums),
-                          _p(gamma.detach()), _p(beta.detach()), ctypes.c_float(eps), ctypes.c_float(momentum),
+                    _call(_lib.omnipq_bn_finalize, sums, cout, float(P) * world, _p(sums),
+                          _p(gamma.detach()), _p(beta.detach()), eps, momentum,
                           _p(rm), _p(rv), _p(lay.a), _p(lay.b), _p(lay.mean), _p(lay.invstd), _p(None))
                 bump(nbt)
             else:
@@ -1451,7 +1444,7 @@ class FusedSAStage(torch.autograd.Function):
             elif l < L - 1:
                 if not fused_relu:
                     lay.X = torch.empty_like(lay.Y)
-                    _call(_lib.omnipq_bnrelu, lay.Y, ctypes.c_longlong(P), cout, _p(lay.Y), _p(lay.a), _p(lay.b),
+                    _call(_lib.omnipq_bnrelu, lay.Y, P, cout, _p(lay.Y), _p(lay.a), _p(lay.b),
                           _p(lay.X))
                 X = lay.X
             else:
@@ -1472,12 +1465,12 @@ class FusedSAStage(torch.autograd.Function):
             if last.fin is not None:
                 fsums, count, pg, pb, peps, pmom, prm, prv, _ = last.fin
                 last.fin = None
-                _call(_lib.omnipq_sa_pool_select_finalize, out_pm, ctypes.c_longlong(B * M), last.C, _p(pool[1]), _p(pool[2]),
-                      _p(pool[3]), _p(pool[4]), _p(fsums), ctypes.c_double(count), _p(pg), _p(pb), ctypes.c_float(peps),
-                      ctypes.c_float(pmom), _p(prm), _p(prv), _p(last.a), _p(last.b), _p(last.mean), _p(last.invstd),
+                _call(_lib.omnipq_sa_pool_select_finalize, out_pm, B * M, last.C, _p(pool[1]), _p(pool[2]),
+                      _p(pool[3]), _p(pool[4]), _p(fsums), count, _p(pg), _p(pb), peps,
+                      pmom, _p(prm), _p(prv), _p(last.a), _p(last.b), _p(last.mean), _p(last.invstd),
                       _p(out_f32), _p(out_pm), _p(arg), _p(ysel))
             else:
-                _call(_lib.omnipq_sa_pool_select, out_pm, ctypes.c_longlong(B * M), last.C, _p(pool[1]), _p(pool[2]),
+                _call(_lib.omnipq_sa_pool_select, out_pm, B * M, last.C, _p(pool[1]), _p(pool[2]),
                       _p(pool[3]), _p(pool[4]), _p(last.a), _p(last.b), _p(out_f32), _p(out_pm), _p(arg), _p(ysel))
         else:
             _call(_lib.omnipq_sa_pool, last.Y, B, M, S, last.C, _p(last.Y), _p(last.a), _p(last.b), _p(out_f32),
@@ -1521,7 +1514,7 @@ class FusedSAStage(torch.autograd.Function):
         L = len(layers)
         dev = g_out.device
         g_out = g_out.float().transpose(1, 2).contiguous()      # position-major [B*M][C] (no-op for a view)
-        total = ctypes.c_double(float(P) * world)
+        total = float(P) * world
         grads = [None] * (3 * L)
 
         last = layers[-1]
@@ -1530,11 +1523,11 @@ class FusedSAStage(torch.autograd.Function):
             # ... and the one-hot operand of the backward without dY (LAST_NO_DY), from the values this pass reads anyway
             sums = zeros_f64(3, last.C, dev)
             hot = torch.empty((B * M, last.C), device=dev, dtype=torch.int32)
-            _call(_lib.omnipq_sa_pool_bwd_stats_sel_hot, g_out, ctypes.c_longlong(B * M), last.C, _p(ctx.ysel), _p(last.mean),
+            _call(_lib.omnipq_sa_pool_bwd_stats_sel_hot, g_out, B * M, last.C, _p(ctx.ysel), _p(last.mean),
                   _p(last.invstd), _p(g_out), _p(ctx.out_pm), _p(sums), 1, _p(last.a), _p(ctx.arg), _p(hot))
         elif ctx.ysel is not None:
             sums = zeros_f64(3, last.C, dev)                                     # [S | T | scratch], zero from the arena
-            _call(_lib.omnipq_sa_pool_bwd_stats_sel, g_out, ctypes.c_longlong(B * M), last.C, _p(ctx.ysel), _p(last.mean),
+            _call(_lib.omnipq_sa_pool_bwd_stats_sel, g_out, B * M, last.C, _p(ctx.ysel), _p(last.mean),
                   _p(last.invstd), _p(g_out), _p(ctx.out_pm), _p(sums), 1)
         else:
             sums = torch.empty((3, last.C), device=dev, dtype=torch.float64)
@@ -1556,7 +1549,7 @@ class FusedSAStage(torch.autograd.Function):
                 grads[3 * (L - 1) + 1], grads[3 * (L - 1) + 2] = gb3[1], gb3[0]
             B1 = torch.empty((C2, C2 + 32), device=dev, dtype=E16.dtype)
             ab = torch.empty((2, C3), device=dev, dtype=torch.float32)          # alpha | beta
-            _call(_lib.omnipq_sa_last_bwd_prep, g_out, ctypes.c_longlong(B * M), C3, C2, _p(sums), total, _p(last.a),
+            _call(_lib.omnipq_sa_last_bwd_prep, g_out, B * M, C3, C2, _p(sums), total, _p(last.a),
                   _p(last.mean), _p(last.invstd), _p(None), _p(None), _p(None), _p(last.Wt), last.Wt.stride(0),
                   _p(None), _p(B1), C2 + 32, _p(ab[0]), _p(ab[1]), _p(gb3))
             # the data gradient + the BatchNorm-backward sums of the layer below; X2 = relu(bn2(Y2)) as its first phase forms
@@ -1625,7 +1618,7 @@ class FusedSAStage(torch.autograd.Function):
                 _allreduce_(sums5[:2], world)
                 dW0 = torch.empty((prev.C, 3, 1, 1), device=dev, dtype=torch.float32)
                 _call(_lib.omnipq_sa_xyz_bwd, dY, prev.C, _p(prev.Wp), prev.Wp.shape[1], _p(prev.mom), _p(sums5), _p(prev.a),
-                      _p(prev.mean), _p(prev.invstd), ctypes.c_double(1.0 / (float(P) * world)), _p(dW0))
+                      _p(prev.mean), _p(prev.invstd), 1.0 / (float(P) * world), _p(dW0))
                 grads[0] = dW0
                 break
             if l == 0 and getattr(ctx, "hoist", None) is not None:
@@ -1665,7 +1658,7 @@ class FusedSAStage(torch.autograd.Function):
                 # bucket the positions by source point, then every (point, 8-channel piece) sums its
                 # own bucket: no atomics, each dX row is read exactly once
                 offsets, order = _csr_of(ctx.idx, B, N, M, S, getattr(ctx, "plan", None), dX)
-                _call(_lib.omnipq_sa_scatter_csr, dX, B, N, M, S, cin, kpad, ctypes.c_float(inv_r), _p(offsets),
+                _call(_lib.omnipq_sa_scatter_csr, dX, B, N, M, S, cin, kpad, inv_r, _p(offsets),
                       _p(order), _p(dX), _p(dfeat_pm), _p(d_xyz), _p(d_cen))
                 if dfeat_pm is not None:
                     d_feat = dfeat_pm[..., :ctx.cin_raw].transpose(1, 2).to(ctx.feat_dtype)      # (B, cin, N) view, see forward
@@ -1698,7 +1691,7 @@ def _backward_hoisted(ctx, dY, lay, grads, dfr, dev):
         d_xyz = torch.empty((B, N, 3), device=dev)
         d_cen = torch.empty((B, M, 3), device=dev)
     dZ = torch.empty((B * N, C1), device=dev, dtype=E16.dtype)
-    _call(_lib.omnipq_sa_scatter_rows_csr, dY, B, N, M, S, C1, ctypes.c_float(inv_r), _p(offsets), _p(order), _p(dY), _p(dXr),
+    _call(_lib.omnipq_sa_scatter_rows_csr, dY, B, N, M, S, C1, inv_r, _p(offsets), _p(order), _p(dY), _p(dXr),
           _p(plan.goff if plan is not None else None), plan.gs if plan is not None else 16, _p(None), _p(dZ), _p(d_xyz),
           _p(d_cen))
     if want_w:
@@ -1826,7 +1819,7 @@ class FPGatherRows(torch.autograd.Function):
         rows = torch.empty((B * n, C2 + C1), device=idx.device, dtype=E16.dtype)
         _call(_lib.omnipq_interp_rows, rows, B, n, m, C2, _p(known_pm), _p(idx), _p(weight), _p(rows), C2 + C1, 0)
         if C1:
-            _call(_lib.omnipq_place_rows, rows, ctypes.c_longlong(B * n), C1, _p(skip_pm), _p(rows), C2 + C1, C2)
+            _call(_lib.omnipq_place_rows, rows, B * n, C1, _p(skip_pm), _p(rows), C2 + C1, C2)
         ctx.save_for_backward(idx, weight)
         ctx.pre_csr = getattr(idx, "omnipq_csr3", None)     # (offsets (B, m+1), order (B, 3n)) made ahead of the module, or None
         ctx.geom = (B, n, m, C2, C1, known_feats.dtype, None if skip_feats is None else skip_feats.dtype)

@@ -22,6 +22,52 @@ def declared_symbols():
     return sorted(names)
 
 
+def declared_signatures():
+    """{name: (return letter, parameter letters)} of every function the public headers declare, in the letters of
+    omnipq_entry_point_signatures() (include/omnipq_pointops.h).  The tests' OWN reading of the headers, statement by
+    statement -- not the function omni-pq_amd/build.py compiles into the library."""
+    scalars = {("int",): "i", ("unsigned",): "u", ("unsigned", "int"): "u", ("long", "long"): "l", ("float",): "f",
+               ("double",): "d"}
+    returns = {("int",): "i", ("long", "long"): "l", ("void",): "v", ("const", "char", "*"): "s"}
+    out = {}
+    for fn in sorted(os.listdir(INCLUDE)):
+        if not fn.endswith(".h"):
+            continue
+        text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(INCLUDE, fn)).read(), flags=re.S)
+        text = "\n".join(ln for ln in text.splitlines() if not ln.lstrip().startswith("#"))
+        text = text.replace('extern "C" {', " ")
+        text = re.sub(r"\{[^{}]*\}", " ", text)                    # struct bodies: their fields end in `;` too
+        for stmt in text.split(";"):
+            if "(" not in stmt:
+                continue
+            head, _, rest = stmt.partition("(")
+            params = rest[:rest.rindex(")")]
+            *ret, name = head.replace("*", " * ").split()
+            assert name.startswith("omnipq_") and name not in out, (fn, stmt)
+            letters = ""
+            for prm in ([] if params.split() == ["void"] else params.split(",")):
+                toks = prm.replace("*", " * ").split()
+                if toks[:3] == ["const", "omnipq_row_plan", "*"]:
+                    letters += "P"
+                elif "*" in toks or "[" in prm:
+                    letters += "p"
+                else:
+                    letters += scalars[tuple(toks[:-1])]          # KeyError: a type the signature letters do not cover
+            out[name] = (returns[tuple(ret)], letters)
+    return out
+
+
+def reported_signatures(lib_handle):
+    """{name: (return letter, parameter letters)} as the loaded library reports them; every line must be well-formed"""
+    lib_handle.omnipq_entry_point_signatures.restype = ctypes.c_char_p
+    out = {}
+    for line in lib_handle.omnipq_entry_point_signatures().decode().splitlines():
+        fields = line.split()
+        assert len(fields) in (2, 3) and fields[0] not in out, line
+        out[fields[0]] = (fields[1], fields[2] if len(fields) == 3 else "")
+    return out
+
+
 _lib = None
 
 

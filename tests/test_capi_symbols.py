@@ -45,25 +45,96 @@ def test_libraries_have_gfx950_code_objects_with_their_mfma_opcode(built_lib, tm
 
 
 def test_library_names_its_plan_aware_entry_points(built_lib):
-    """the binding takes the set of plan-aware entry points from the LIBRARY it loaded (a build-time constant),
-    and refuses a library of another ABI version; here: that constant equals what the header of this tree declares, in
-    both element-type libraries, and the binding's set is the library's."""
-    import sys
+    """the binding takes the set of plan-aware entry points from the LIBRARY it loaded (a build-time constant: the
+    names whose reported signature has a `P`), and refuses a library of another ABI version; here: that set equals what the
+    header of this tree declares, in both element-type libraries, and the binding's set is the library's."""
     for path in both(built_lib):
         lib = ctypes.CDLL(path)
-        lib.omnipq_plan_aware_entry_points.restype = ctypes.c_char_p
-        names = frozenset(lib.omnipq_plan_aware_entry_points().decode().split())
+        names = frozenset(n for n, (_, params) in capi.reported_signatures(lib).items() if "P" in params)
         assert names == capi.plan_aware() and len(names) >= 20, sorted(names ^ capi.plan_aware())
         assert all(hasattr(lib, n) for n in names)
     import pointnet2_utils
     assert pointnet2_utils._ext.PLAN_AWARE == capi.plan_aware()
-    assert pointnet2_utils._ext.ABI_VERSION == lib.omnipq_abi_version() == 4
+    assert pointnet2_utils._ext.ABI_VERSION == lib.omnipq_abi_version() == 5
+
+
+_CTYPE = {"i": ctypes.c_int, "u": ctypes.c_uint, "l": ctypes.c_longlong, "f": ctypes.c_float, "d": ctypes.c_double,
+          "p": ctypes.c_void_p, "P": ctypes.c_void_p, "v": None, "s": ctypes.c_char_p}
+
+
+def test_library_reports_the_signatures_its_headers_declare(built_lib):
+    """Every function include/*.h declares is reported by both libraries with the header's return type, parameter count and
+    letter per parameter (the headers read by tests/capi.py, not by the build), nothing else is reported, and the functions
+    the binding loaded carry exactly these `restype` / `argtypes`."""
+    want = capi.declared_signatures()
+    assert sorted(want) == capi.declared_symbols() and len(want) >= 158
+    assert want["omnipq_furthest_point_sampling_resume"] == ("i", "iiiiipppup")
+    assert want["omnipq_copy_probe"] == ("i", "pplp") and want["omnipq_pair_hold"] == ("v", "")
+    assert want["omnipq_error_string"] == ("s", "i") and want["omnipq_gemm_nt_workspace_floats"] == ("l", "iii")
+    for path in both(built_lib):
+        got = capi.reported_signatures(ctypes.CDLL(path))
+        assert sorted(set(got) ^ set(want)) == [], path
+        assert {n: got[n] for n in want if got[n] != want[n]} == {}, path
+    import pointnet2_utils
+    ext = pointnet2_utils._load_ext()
+    assert len(ext._LIBS) == 2
+    for lib in ext._LIBS.values():
+        for name, (ret, params) in want.items():
+            fn = getattr(lib, name)
+            assert fn.restype is _CTYPE[ret] and list(fn.argtypes) == [_CTYPE[c] for c in params], name
+
+
+def test_build_refuses_a_type_without_a_signature_letter(built_lib, tmp_path, monkeypatch):
+    """omni-pq_amd/build.py writes the reported text from the headers; a parameter or return type outside its list fails the
+    build with the declaration's name instead of being guessed."""
+    import pytest
+    import build as omnipq_build
+    inc = tmp_path / "include"
+    inc.mkdir()
+    monkeypatch.setattr(omnipq_build, "REPO", str(tmp_path))
+    (inc / "a.h").write_text("/* x */\n#define N 3\nint omnipq_ok(int a, const float *b, long long v[N], unsigned f, void *stream);\n"
+                             "void omnipq_none(void);\n")
+    assert omnipq_build.entry_point_signatures() == "omnipq_none v\nomnipq_ok i ippup\n"
+    (inc / "b.h").write_text("int omnipq_bad(int a, short b, void *stream);\n")
+    with pytest.raises(RuntimeError, match="omnipq_bad"):
+        omnipq_build.entry_point_signatures()
+    (inc / "b.h").write_text("short omnipq_worse(int a);\n")
+    with pytest.raises(RuntimeError, match="omnipq_worse"):
+        omnipq_build.entry_point_signatures()
+
+
+def test_binding_refuses_miscounted_and_mistyped_calls(built_lib):
+    """Through the binding a call one argument short or one long raises TypeError, a pointer where the header says `int`
+    raises ctypes.ArgumentError, and a plain Python int arrives whole in a `long long` parameter -- through an untyped handle
+    it is cut to a C int (1 << 45 -> 0) and omnipq_copy_probe answers OMNIPQ_OK.  Nothing here reaches a device: every call
+    is refused by ctypes or by the entry point's own validation."""
+    import pytest
+    import pointnet2_utils
+    ext = pointnet2_utils._load_ext()
+    EINVAL = 10001
+    p = ctypes.c_void_p(0x1000)                       # never dereferenced
+    good = (0, 128, 32, p, 32, p, 32, p, 128, None, None)      # omnipq_gemm_nt_e16 on zero rows: a no-op that succeeds
+    assert ext._lib.omnipq_gemm_nt_e16(*good) == 0
+    with pytest.raises(TypeError, match="omnipq_gemm_nt_e16"):
+        ext._lib.omnipq_gemm_nt_e16(*good[:-1])
+    with pytest.raises(TypeError, match="omnipq_gemm_nt_e16"):
+        ext._lib.omnipq_gemm_nt_e16(*good, None)
+    with pytest.raises(TypeError):
+        ext._lib0.omnipq_copy_probe(p, p, 16)                   # a bare library function: ctypes counts the missing one
+    with pytest.raises(ctypes.ArgumentError):
+        ext._lib.omnipq_gemm_nt_e16(p, 128, 32, p, 32, p, 32, p, 128, None, None)
+    with pytest.raises(ctypes.ArgumentError):
+        ext._lib0.omnipq_ball_query(1, 16, 4, 0.2, p, p, p, p, None)          # nsample is an int
+    assert capi.lib().omnipq_copy_probe(p, p, 1 << 45, None) == 0                # the bug class: bytes arrived as 0
+    assert ext._lib.omnipq_copy_probe(p, p, 1 << 45, None) == EINVAL
+    assert ext._lib0.omnipq_copy_probe(p, p, 1 << 45, None) == EINVAL
+    assert ext._lib0.omnipq_copy_probe(p, p, ctypes.c_longlong(1 << 45), None) == EINVAL     # a wrapped scalar still works
 
 
 def test_host_helpers_without_gpu(built_lib):
     from oracle import oracle_ext
     lib = capi.lib()
-    assert lib.omnipq_abi_version() == 4
+    assert lib.omnipq_abi_version() == 5
     assert b"invalid" in lib.omnipq_error_string(10001)
     # the FPS tie geometry must agree between library, oracle and the reference's formula
     for n in list(range(1, 70)) + [100, 127, 128, 255, 256, 511, 512, 513, 1000, 1024, 2048, 4096, 8192,

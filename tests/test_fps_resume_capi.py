@@ -1,4 +1,4 @@
-"""CPU: omnipq_furthest_point_sampling_resume is exported by both element-type libraries, leaves the ABI version at 4, and
+"""CPU: omnipq_furthest_point_sampling_resume is exported by both element-type libraries, at the ABI version the binding asks for, and
 validates its arguments before it touches the device.  No kernel is launched here; pointers are never dereferenced."""
 import ctypes
 
@@ -13,9 +13,9 @@ def test_resume_is_declared_and_exported_by_both_libraries(built_lib):
     for path in (built_lib, built_lib[:-3] + "_f16.so"):
         lib = ctypes.CDLL(path)
         assert hasattr(lib, NAME), path
-        assert lib.omnipq_abi_version() == 4          # additive: no existing argument list changed
+        assert lib.omnipq_abi_version() == 5
     import pointnet2_utils
-    assert pointnet2_utils._ext.ABI_VERSION == 4
+    assert pointnet2_utils._ext.ABI_VERSION == 5
     assert callable(pointnet2_utils._ext.furthest_point_sampling_resume)
 
 
