@@ -1069,6 +1069,39 @@ __global__ __launch_bounds__(256) void splitk_reduce_bf16_kernel(long long n4, i
 
 }  // namespace omnipq
 
+// ---- host side: one descriptor (NtCall) and one dispatcher (gemm_nt_dispatch) behind the extern "C" entry points ----------
+
+// M-tile count up to which the statistics go straight to f64 atomics (<= 64 adds per address); above it every row tile
+// writes a partial row into a workspace and partial_reduce_kernel sums them
+static constexpr int kStatsDirectTiles = 64;      // (256 / 512 / 2048 measured in round 3: no difference in step time)
+
+static void gemm_nt_tile(omnipq::GemmArgs &g, int T) {
+  g.m_tiles = (g.M + T - 1) / T;
+  g.n_tiles = (g.N + T - 1) / T;
+}
+
+static omnipq::GemmArgs gemm_nt_args(int M, int N, int K, int lda, int ldb, int ldc, int T) {
+  omnipq::GemmArgs g{M, N, K, lda, ldb, ldc, K};
+  gemm_nt_tile(g, T);
+  return g;
+}
+
+// (slices: blockIdx.z, the split-K launches)
+static dim3 gemm_nt_grid(const omnipq::GemmArgs &g, int slices = 1) {
+  return dim3(((g.m_tiles + 7) / 8) * 8 * g.n_tiles, 1, slices);
+}
+
+// What the entry points check first.  OMNIPQ_EINVAL: negative sizes; OMNIPQ_OK: an empty problem, nothing to launch;
+// OMNIPQ_EINVAL again: a missing operand (`operands`: the caller's own pointers) or a broken divisibility rule (K % 32, N and
+// ldc % `mult`, lda and ldb % 8); kNtGo: go on.
+static constexpr int kNtGo = -1;
+static int gemm_nt_check(int M, int N, int K, int lda, int ldb, int ldc, bool operands, int mult = 8) {
+  if (M < 0 || N < 0 || K < 0) return OMNIPQ_EINVAL;
+  if (M == 0 || N == 0) return OMNIPQ_OK;
+  if (!operands || (K % omnipq::GBK) || (N % mult) || (lda % 8) || (ldb % 8) || (ldc % mult)) return OMNIPQ_EINVAL;
+  return kNtGo;
+}
+
 // Long contractions over few tiles (the decoder's 2048-wide feed-forward: 96 tiles, 64 K-steps each) are
 // latency bound: split K over `slabs` workgroups per tile into f32 partials (workspace: slabs * M * N floats),
 // then one pass sums them, adds the bias and rounds to bf16.
@@ -1092,10 +1125,9 @@ static SplitPlan gemm_nt_split_plan(int M, int N, int K) {
   if (slabs > 8) slabs = 8;
   return SplitPlan{slabs < 2 ? 1 : slabs, 128};
 }
-static int gemm_nt_splitk_slabs(int M, int N, int K) { return gemm_nt_split_plan(M, N, K).slabs; }
 
 extern "C" long long omnipq_gemm_nt_workspace_floats(int M, int N, int K) {
-  const int slabs = gemm_nt_splitk_slabs(M, N, K);
+  const int slabs = gemm_nt_split_plan(M, N, K).slabs;
   return slabs > 1 ? (long long)slabs * M * N : 0;
 }
 
@@ -1103,18 +1135,15 @@ static int gemm_nt_splitk_bf16(int M, int N, int K, const void *A, int lda, cons
                                const float *bias, float *workspace, SplitPlan plan, void *stream) {
   using namespace omnipq;
   if (ldc != N || (N % 4)) return OMNIPQ_EINVAL;
-  const int slabs = plan.slabs, T = plan.T;
-  int k_chunk = ((K / GBK + slabs - 1) / slabs) * GBK;
-  const int used = (K + k_chunk - 1) / k_chunk;
-  GemmArgs g{M, N, K, lda, ldb, N, k_chunk, (M + T - 1) / T, (N + T - 1) / T};
-  const int groups = (g.m_tiles + 7) / 8;
-  dim3 grid(groups * 8 * g.n_tiles, 1, used);
-  if (T == 64)
-    gemm_nt_kernel<true, 0, false, 64><<<grid, 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B,
-                                                                             workspace, nullptr);
+  GemmArgs g = gemm_nt_args(M, N, K, lda, ldb, N, plan.T);
+  g.k_chunk = ((K / GBK + plan.slabs - 1) / plan.slabs) * GBK;
+  const int used = (K + g.k_chunk - 1) / g.k_chunk;
+  if (plan.T == 64)
+    gemm_nt_kernel<true, 0, false, 64><<<gemm_nt_grid(g, used), 256, 0, (hipStream_t)stream>>>(
+        g, (const e16_t *)A, (const e16_t *)B, workspace, nullptr);
   else
-    gemm_nt_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B, workspace,
-                                                             nullptr);
+    gemm_nt_kernel<true><<<gemm_nt_grid(g, used), 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B,
+                                                                               workspace, nullptr);
   OMNIPQ_LAUNCH_CHECK();
   const long long n4 = (long long)M * N / 4;
   splitk_reduce_bf16_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, (hipStream_t)stream>>>(
@@ -1131,17 +1160,17 @@ static bool gemm_nt_small_tiles(int M, int N) {
   return (long long)((M + 127) / 128) * ((N + 127) / 128) <= g_small_tile_limit;
 }
 
-// the calling thread's row plan (common.h: RowPlan), if it was made for this many rows
+// the calling thread's row plan (common.h: RowPlan), if it was made for this many rows; the partial-sum paths only
 static void plan_rows(omnipq::GemmArgs &g) {
   const omnipq::RowPlan &rp = omnipq::row_plan();
-  if (rp.rows_dev && rp.rows == g.M && g.m_tiles > 64) {      // (> kStatsDirectTiles: the partial-sum paths)
+  if (rp.rows_dev && rp.rows == g.M && g.m_tiles > kStatsDirectTiles) {
     g.rows_dev = rp.rows_dev;
     g.row_w = rp.row_w;
   }
 }
 
 static int stats_reduce(const omnipq::GemmArgs &g, int ns, float *workspace, double *sums, void *stream) {
-  int slabs = g.m_tiles / 64;
+  int slabs = g.m_tiles / 64;                     // (row tiles per slab of the reduction: not kStatsDirectTiles)
   if (slabs > 128) slabs = 128;
   if (slabs < 1) slabs = 1;
   omnipq::partial_reduce_kernel<<<dim3((ns * g.N + 255) / 256, slabs), 256, 0, (hipStream_t)stream>>>(
@@ -1149,12 +1178,6 @@ static int stats_reduce(const omnipq::GemmArgs &g, int ns, float *workspace, dou
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }
-
-static omnipq::GemmArgs gemm_nt_args(int M, int N, int K, int lda, int ldb, int ldc, int T) {
-  return omnipq::GemmArgs{M, N, K, lda, ldb, ldc, K, (M + T - 1) / T, (N + T - 1) / T};
-}
-
-static dim3 gemm_nt_grid(const omnipq::GemmArgs &g) { return dim3(((g.m_tiles + 7) / 8) * 8 * g.n_tiles, 1, 1); }
 
 // 64 x 64-tile launches: the K-resident variant (see KRES) whenever the contraction fits
 static bool gemm_nt_kres(int K) { return K <= omnipq::kResMaxSteps * omnipq::GBK; }
@@ -1174,6 +1197,15 @@ struct HeldSmallBlob {
   omnipq::SmallProblem p;
   int lds;
 };
+
+// sends a held launch out on its own
+static void flush_held() {
+  omnipq::HeldLaunch &h = t_held;
+  if (h.full) {
+    h.full = h.armed = false;
+    h.single(h);
+  }
+}
 
 template <int STATS, bool AFF>
 static void launch_small_single(const omnipq::SmallProblem &p, int lds, hipStream_t stream) {
@@ -1213,11 +1245,7 @@ static void launch_small(const omnipq::GemmArgs &g, const void *A, const void *B
         });
     if (!consumed) launch_small_single<STATS, AFF>(q.p, lds, (hipStream_t)stream);
   } else {
-    HeldLaunch &h = held_launch();
-    if (h.full) {
-      h.full = h.armed = false;
-      h.single(h);
-    }
+    flush_held();
     gemm_nt_kernel<false, STATS, AFF, 64><<<gemm_nt_grid(g), 256, 0, (hipStream_t)stream>>>(
         g, (const e16_t *)A, (const e16_t *)B, C, bias, stats, bn, aff, PoolOut(), XyzGen());
   }
@@ -1231,39 +1259,125 @@ extern "C" int omnipq_pair_held(void) { return t_held.full ? 1 : 0; }
 
 // Sends out a held launch that found no partner and disarms; returns the number of pair launches made so far (diagnostic).
 extern "C" long long omnipq_pair_flush(void) {
-  omnipq::HeldLaunch &h = t_held;
-  if (h.full) h.single(h);
-  h.full = h.armed = false;
+  flush_held();
+  t_held.armed = false;
   return t_pairs_launched;
 }
 
-// C[M][N] (bf16) = A[M][K] * B[N][K]^T.   K % 32 == 0, N % 8 == 0, ld* % 8 == 0, 16-byte aligned.
-extern "C" int omnipq_gemm_nt_e16(int M, int N, int K, const void *A, int lda, const void *B, int ldb,
-                                   void *C, int ldc, const omnipq_row_plan *plan, void *stream) {
-  omnipq::PlanScope plan_scope_(plan);            // the row plan is an ARGUMENT of the call (no ambient state)
+// ---- the dispatcher -----------------------------------------------------------------------------------------------------
+// Everything one NT GEMM launch needs, filled by an entry point after its own argument checks.
+struct NtCall {
+  omnipq::GemmArgs g;                     // M, N, K, lda, ldb, ldc and the extras an entry point sets (relu / dropout,
+                                          // no_store); the tile geometry and the row plan are the dispatcher's
+  const void *A, *B;
+  void *C;
+  const float *bias;
+  bool planned = false;                   // the entry point takes a row plan (it has opened its PlanScope)
+  double *sums = nullptr;                 // statistics kinds: the destination, double[n_sums][N] ...
+  float *workspace = nullptr;             // ... and the partial sums of more than kStatsDirectTiles row tiles
+  int n_sums = 2;                         // (5: XG = 2)
+  omnipq::BnBwdEpilogue bn{};
+  omnipq::AffineIn aff{};
+  omnipq::PoolOut pool{};
+  omnipq::XyzGen xg{};
+  omnipq::DzGen dz{};
+
+  NtCall(int M, int N, int K, const void *A_, int lda, const void *B_, int ldb, void *C_, int ldc,
+         const float *bias_ = nullptr)
+      : g(gemm_nt_args(M, N, K, lda, ldb, ldc, 128)), A(A_), B(B_), C(C_), bias(bias_) {}
+};
+
+// the epilogue family; with AFF / XG / DZ it names the kernel variant
+enum NtKind {
+  kNtPlain,       // bf16 C (+ bias, relu / dropout)                            STATS = 0
+  kNtStats,       // ... and the BatchNorm statistics of C                      STATS = 1 (f64 atomics) / 2 (partial sums)
+  kNtBnBwd,       // ... and the BatchNorm-backward sums of the layer below     STATS = 3 / 4
+  kNtMask,        // C masked by the sign of bn.Y                               STATS = 5
+  kNtF32          // f32 C
+};
+
+// one launch of T x T tiles: every kernel parameter comes from the descriptor
+template <bool OUT_F32, int STATS, bool AFF, int XG = 0, bool PLAN = false, bool DZ = false, int T = 128>
+static void nt_launch(const omnipq::GemmArgs &g, const NtCall &c, void *stats, void *stream) {
   using namespace omnipq;
-  if (M < 0 || N < 0 || K < 0) return OMNIPQ_EINVAL;
-  if (M == 0 || N == 0) return OMNIPQ_OK;
-  if (!A || !B || !C || (K % GBK) || (N % 8) || (lda % 8) || (ldb % 8) || (ldc % 8)) return OMNIPQ_EINVAL;
-  if (gemm_nt_small_tiles(M, N)) {
-    const GemmArgs g = gemm_nt_args(M, N, K, lda, ldb, ldc, 64);
-    launch_small<0, false>(g, A, B, C, nullptr, nullptr, BnBwdEpilogue(), AffineIn(), stream);
-  } else {
-    GemmArgs g = gemm_nt_args(M, N, K, lda, ldb, ldc, 128);
-    plan_rows(g);
-    if (g.rows_dev)
-      gemm_nt_kernel<false, 0, false, 128, 0, false, true><<<gemm_nt_grid(g), 256, 0, (hipStream_t)stream>>>(
-          g, (const e16_t *)A, (const e16_t *)B, C, nullptr);
+  gemm_nt_kernel<OUT_F32, STATS, AFF, T, XG, false, PLAN, DZ><<<gemm_nt_grid(g), 256, 0, (hipStream_t)stream>>>(
+      g, (const e16_t *)c.A, (const e16_t *)c.B, c.C, c.bias, stats, c.bn, c.aff, c.pool, c.xg, c.dz);
+}
+
+// the PLAN instantiation iff plan_rows found the thread's plan made for this call (DZ exists with a plan only)
+template <int STATS, bool AFF, int XG, bool DZ>
+static void nt_launch_planned(const omnipq::GemmArgs &g, const NtCall &c, void *stats, void *stream) {
+  if (g.rows_dev)
+    nt_launch<false, STATS, AFF, XG, true, DZ>(g, c, stats, stream);
+  else if constexpr (!DZ)
+    nt_launch<false, STATS, AFF, XG>(g, c, stats, stream);
+}
+
+// Picks the instantiation for `c` and launches it:
+//   * 64 x 64 tiles (launch_small: K-resident / pair launches) when gemm_nt_small_tiles says so -- never with ball extrema,
+//     never on the partial-sum path, never for the XG / DZ variants, which exist for that path only;
+//   * statistics: f64 atomics up to kStatsDirectTiles row tiles, else partial sums + stats_reduce;
+//   * PLAN instantiations exist for the partial-sum paths and the plain GEMM.
+// Only the combinations an entry point can reach are instantiated (tests/test_capi_symbols.py lists them).
+template <NtKind KIND, bool AFF = false, int XG = 0, bool DZ = false>
+static int gemm_nt_dispatch(const NtCall &c, void *stream) {
+  using namespace omnipq;
+  constexpr bool SUMS = KIND == kNtStats || KIND == kNtBnBwd;
+  constexpr int DIRECT = KIND == kNtStats ? 1 : KIND == kNtBnBwd ? 3 : KIND == kNtMask ? 5 : 0;      // the kernel's STATS
+  constexpr int PARTIAL = DIRECT + 1;
+  constexpr bool PARTIAL_ONLY = XG != 0 || DZ;
+  GemmArgs g = c.g;
+  if (c.planned) plan_rows(g);
+  const bool direct = g.m_tiles <= kStatsDirectTiles;
+  if (SUMS && direct && (PARTIAL_ONLY || g.no_store)) return OMNIPQ_EINVAL;
+  if (DZ && (!g.rows_dev || !g.row_w)) return OMNIPQ_EINVAL;
+  if constexpr (KIND == kNtF32) flush_held();
+  if constexpr (!PARTIAL_ONLY) {
+    if (c.pool.s == 0 && (!SUMS || direct) && gemm_nt_small_tiles(g.M, g.N)) {
+      GemmArgs gs = c.g;                          // (no plan)
+      gemm_nt_tile(gs, 64);
+      if constexpr (KIND == kNtF32)
+        nt_launch<true, 0, false, 0, false, false, 64>(gs, c, nullptr, stream);
+      else
+        launch_small<DIRECT, AFF>(gs, c.A, c.B, c.C, c.bias, c.sums, c.bn, c.aff, stream);
+      OMNIPQ_LAUNCH_CHECK();
+      return OMNIPQ_OK;
+    }
+  }
+  if constexpr (!SUMS) {
+    if constexpr (KIND == kNtPlain && !AFF)
+      nt_launch_planned<0, false, 0, false>(g, c, nullptr, stream);
     else
-      gemm_nt_kernel<false><<<gemm_nt_grid(g), 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B, C,
-                                                                            nullptr);
+      nt_launch<KIND == kNtF32, DIRECT, AFF>(g, c, nullptr, stream);
+  } else {
+    if constexpr (!PARTIAL_ONLY) {
+      if (direct) {
+        nt_launch<false, DIRECT, AFF>(g, c, c.sums, stream);
+        OMNIPQ_LAUNCH_CHECK();
+        return OMNIPQ_OK;
+      }
+    }
+    if (!c.workspace) return OMNIPQ_EINVAL;
+    nt_launch_planned<PARTIAL, AFF, XG, DZ>(g, c, c.workspace, stream);
+    OMNIPQ_LAUNCH_CHECK();
+    return stats_reduce(g, c.n_sums, c.workspace, c.sums, stream);
   }
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }
 
-// M-tile count up to which the statistics go straight to f64 atomics (<= 64 adds per address)
-static constexpr int kStatsDirectTiles = 64;      // (256 / 512 / 2048 measured in round 3: no difference in step time)
+// ---- entry points: validate, fill, dispatch -------------------------------------------------------------------------
+
+// C[M][N] (bf16) = A[M][K] * B[N][K]^T.   K % 32 == 0, N % 8 == 0, ld* % 8 == 0, 16-byte aligned.
+extern "C" int omnipq_gemm_nt_e16(int M, int N, int K, const void *A, int lda, const void *B, int ldb,
+                                   void *C, int ldc, const omnipq_row_plan *plan, void *stream) {
+  omnipq::PlanScope plan_scope_(plan);            // the row plan is an ARGUMENT of the call (no ambient state)
+  const int rc = gemm_nt_check(M, N, K, lda, ldb, ldc, A && B && C);
+  if (rc != kNtGo) return rc;
+  NtCall c(M, N, K, A, lda, B, ldb, C, ldc);
+  c.planned = true;
+  return gemm_nt_dispatch<kNtPlain>(c, stream);
+}
 
 extern "C" long long omnipq_gemm_nt_stats_workspace_floats(int M, int N) {
   const long long m_tiles = (M + omnipq::GBM - 1) / omnipq::GBM;
@@ -1277,85 +1391,33 @@ extern "C" int omnipq_gemm_nt_e16_stats(int M, int N, int K, const void *A, int 
                                          void *C, int ldc, const float *bias, double *sums, float *workspace,
                                          const omnipq_row_plan *plan, void *stream) {
   omnipq::PlanScope plan_scope_(plan);            // the row plan is an ARGUMENT of the call (no ambient state)
-  using namespace omnipq;
-  if (M < 0 || N < 0 || K < 0) return OMNIPQ_EINVAL;
-  if (M == 0 || N == 0) return OMNIPQ_OK;
-  if (!A || !B || !C || !sums || (K % GBK) || (N % 8) || (lda % 8) || (ldb % 8) || (ldc % 8)) return OMNIPQ_EINVAL;
-  GemmArgs g{M, N, K, lda, ldb, ldc, K, (M + GBM - 1) / GBM, (N + GBN - 1) / GBN};
-  plan_rows(g);
-  const int groups = (g.m_tiles + 7) / 8;
-  dim3 grid(groups * 8 * g.n_tiles, 1, 1);
-  if (g.m_tiles <= kStatsDirectTiles) {
-    if (gemm_nt_small_tiles(M, N)) {
-      const GemmArgs gs = gemm_nt_args(M, N, K, lda, ldb, ldc, 64);
-      launch_small<1, false>(gs, A, B, C, bias, sums, BnBwdEpilogue(), AffineIn(), stream);
-    } else {
-      gemm_nt_kernel<false, 1><<<grid, 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B, C, bias,
-                                                                  sums);
-    }
-    OMNIPQ_LAUNCH_CHECK();
-    return OMNIPQ_OK;
-  }
-  if (!workspace) return OMNIPQ_EINVAL;
-  if (g.rows_dev)
-    gemm_nt_kernel<false, 2, false, 128, 0, false, true><<<grid, 256, 0, (hipStream_t)stream>>>(
-        g, (const e16_t *)A, (const e16_t *)B, C, bias, workspace);
-  else
-    gemm_nt_kernel<false, 2><<<grid, 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B, C, bias,
-                                                                workspace);
-  OMNIPQ_LAUNCH_CHECK();
-  return stats_reduce(g, 2, workspace, sums, stream);
+  const int rc = gemm_nt_check(M, N, K, lda, ldb, ldc, A && B && C && sums);
+  if (rc != kNtGo) return rc;
+  NtCall c(M, N, K, A, lda, B, ldb, C, ldc, bias);
+  c.planned = true;
+  c.sums = sums;
+  c.workspace = workspace;
+  return gemm_nt_dispatch<kNtStats>(c, stream);
 }
 
+// The affine forms after their own checks.  C == NULL with ball extrema: the tile is not stored (GemmArgs::no_store) --
+// statistics and extrema only; the partial-sum path (more than kStatsDirectTiles row tiles) only
 static int gemm_nt_affine_impl(int M, int N, int K, const void *A, int lda, const omnipq::AffineIn &aff, const void *B,
                                int ldb, void *C, int ldc, const float *bias, double *sums, float *workspace,
                                void *stream, const omnipq::PoolOut &pool = omnipq::PoolOut()) {
-  using namespace omnipq;
-  if (M < 0 || N < 0 || K < 0) return OMNIPQ_EINVAL;
-  if (M == 0 || N == 0) return OMNIPQ_OK;
-  // C == NULL with ball extrema: the tile is not stored (GemmArgs::no_store) -- statistics and extrema only; the
-  // partial-sum path (more than kStatsDirectTiles row tiles) only
   const bool nostore = !C && pool.s > 0 && sums;
-  if (!A || !B || (!C && !nostore) || (K % GBK) || (N % 8) || (lda % 8) || (ldb % 8) || (ldc % 8) || K > kAffMaxK) return OMNIPQ_EINVAL;
-  GemmArgs g{M, N, K, lda, ldb, ldc, K, (M + GBM - 1) / GBM, (N + GBN - 1) / GBN};
-  plan_rows(g);
-  if (nostore) {
-    if (g.m_tiles <= kStatsDirectTiles) return OMNIPQ_EINVAL;
-    g.no_store = 1;
-  }
-  const int groups = (g.m_tiles + 7) / 8;
-  dim3 grid(groups * 8 * g.n_tiles, 1, 1);
-  const bool small = pool.s == 0 && gemm_nt_small_tiles(M, N);
-  const GemmArgs gs = gemm_nt_args(M, N, K, lda, ldb, ldc, 64);
-  if (!sums) {
-    if (small)
-      launch_small<0, true>(gs, A, B, C, bias, nullptr, BnBwdEpilogue(), aff, stream);
-    else
-      gemm_nt_kernel<false, 0, true><<<grid, 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B, C,
-                                                                        bias, nullptr, BnBwdEpilogue(), aff);
-    OMNIPQ_LAUNCH_CHECK();
-    return OMNIPQ_OK;
-  }
-  if (g.m_tiles <= kStatsDirectTiles && small) {
-    launch_small<1, true>(gs, A, B, C, bias, sums, BnBwdEpilogue(), aff, stream);
-    OMNIPQ_LAUNCH_CHECK();
-    return OMNIPQ_OK;
-  }
-  if (g.m_tiles <= kStatsDirectTiles) {
-    gemm_nt_kernel<false, 1, true><<<grid, 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B, C,
-                                                                      bias, sums, BnBwdEpilogue(), aff, pool);
-    OMNIPQ_LAUNCH_CHECK();
-    return OMNIPQ_OK;
-  }
-  if (!workspace) return OMNIPQ_EINVAL;
-  if (g.rows_dev)
-    gemm_nt_kernel<false, 2, true, 128, 0, false, true><<<grid, 256, 0, (hipStream_t)stream>>>(
-        g, (const e16_t *)A, (const e16_t *)B, C, bias, workspace, BnBwdEpilogue(), aff, pool);
-  else
-    gemm_nt_kernel<false, 2, true><<<grid, 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B, C, bias,
-                                                                      workspace, BnBwdEpilogue(), aff, pool);
-  OMNIPQ_LAUNCH_CHECK();
-  return stats_reduce(g, 2, workspace, sums, stream);
+  const int rc = gemm_nt_check(M, N, K, lda, ldb, ldc, A && B && (C || nostore));
+  if (rc != kNtGo) return rc;
+  if (K > omnipq::kAffMaxK) return OMNIPQ_EINVAL;
+  NtCall c(M, N, K, A, lda, B, ldb, C, ldc, bias);
+  c.planned = true;
+  c.g.no_store = nostore;
+  c.aff = aff;
+  c.pool = pool;
+  c.sums = sums;
+  c.workspace = workspace;
+  if (!sums) return gemm_nt_dispatch<kNtPlain, true>(c, stream);
+  return gemm_nt_dispatch<kNtStats, true>(c, stream);
 }
 
 // C = relu(a_in .* A + b_in) B^T (+ bias), the A operand transformed on the fly (see AffineIn); with `sums`
@@ -1371,30 +1433,42 @@ extern "C" int omnipq_gemm_nt_e16_affine(int M, int N, int K, const void *A, int
   return gemm_nt_affine_impl(M, N, K, A, lda, aff, B, ldb, C, ldc, bias, sums, workspace, stream);
 }
 
+// The BatchNorm-finalize arguments of the ..._bnaffine forms, checked and put into *aff
+static int bn_finalize_in(const double *fin_sums, double count, const float *gamma, const float *beta, float eps,
+                          float momentum, float *running_mean, float *running_var, const float *conv_bias, float *a_out,
+                          float *b_out, float *mean_out, float *invstd_out, omnipq::AffineIn *aff) {
+  if (!fin_sums || !gamma || !beta || !a_out || !b_out || !mean_out || !invstd_out || !(count > 0)) return OMNIPQ_EINVAL;
+  if ((running_mean == nullptr) != (running_var == nullptr)) return OMNIPQ_EINVAL;
+  *aff = omnipq::AffineIn{};
+  aff->sums = fin_sums;
+  aff->gamma = gamma;
+  aff->beta = beta;
+  aff->conv_bias = conv_bias;
+  aff->running_mean = running_mean;
+  aff->running_var = running_var;
+  aff->a_out = a_out;
+  aff->b_out = b_out;
+  aff->mean_out = mean_out;
+  aff->invstd_out = invstd_out;
+  aff->count = count;
+  aff->eps = eps;
+  aff->momentum = momentum;
+  return OMNIPQ_OK;
+}
+
+static int pool_out_check(int M, int s, void *ymax, void *ymin, unsigned char *amax, unsigned char *amin,
+                          omnipq::PoolOut *out) {
+  if (s <= 0 || (128 % s) || (M % s) || !ymax || !ymin || !amax || !amin) return OMNIPQ_EINVAL;
+  *out = omnipq::PoolOut{s, (omnipq::e16_t *)ymax, (omnipq::e16_t *)ymin, amax, amin};
+  const omnipq::RowPlan &rp = omnipq::row_plan();
+  if (rp.rows_dev && rp.rows == M && s == 8 && rp.gs == 8) out->gamma = rp.pool_gamma;
+  return OMNIPQ_OK;
+}
+
 // The same with the BatchNorm finalize of the layer that produced A folded in: a / b are DERIVED here from that
 // layer's totals fin_sums (double[2][K] over `count` rows; all-reduced by the caller under SyncBatchNorm), gamma,
 // beta -- and stored, with mean / invstd, into a_out .. invstd_out for the backward pass; running_mean / running_var
 // (may be NULL) get the momentum update, conv_bias (may be NULL) as in omnipq_bn_finalize.
-static int pool_out_check(int M, int N, int s, void *ymax, void *ymin, unsigned char *amax, unsigned char *amin,
-                          omnipq::PoolOut *out) {
-  if (s <= 0 || (128 % s) || (M % s) || !ymax || !ymin || !amax || !amin) return OMNIPQ_EINVAL;
-  *out = omnipq::PoolOut{s, (omnipq::e16_t *)ymax, (omnipq::e16_t *)ymin, amax, amin};
-  {
-    const omnipq::RowPlan &rp = omnipq::row_plan();
-    if (rp.rows_dev && rp.rows == M && s == 8 && rp.gs == 8) out->gamma = rp.pool_gamma;
-  }
-  (void)N;
-  return OMNIPQ_OK;
-}
-
-extern "C" int omnipq_gemm_nt_e16_bnaffine_pool(int M, int N, int K, const void *A, int lda, const double *fin_sums,
-                                                 double count, const float *gamma, const float *beta, float eps,
-                                                 float momentum, float *running_mean, float *running_var,
-                                                 const float *conv_bias, float *a_out, float *b_out, float *mean_out,
-                                                 float *invstd_out, const void *B, int ldb, void *C, int ldc,
-                                                 const float *bias, double *sums, float *workspace, int s, void *ymax,
-                                                 void *ymin, unsigned char *amax, unsigned char *amin, const omnipq_row_plan *plan, void *stream);
-
 extern "C" int omnipq_gemm_nt_e16_bnaffine(int M, int N, int K, const void *A, int lda, const double *fin_sums,
                                             double count, const float *gamma, const float *beta, float eps,
                                             float momentum, float *running_mean, float *running_var,
@@ -1402,22 +1476,10 @@ extern "C" int omnipq_gemm_nt_e16_bnaffine(int M, int N, int K, const void *A, i
                                             float *invstd_out, const void *B, int ldb, void *C, int ldc,
                                             const float *bias, double *sums, float *workspace, const omnipq_row_plan *plan, void *stream) {
   omnipq::PlanScope plan_scope_(plan);            // the row plan is an ARGUMENT of the call (no ambient state)
-  if (!fin_sums || !gamma || !beta || !a_out || !b_out || !mean_out || !invstd_out || !(count > 0)) return OMNIPQ_EINVAL;
-  if ((running_mean == nullptr) != (running_var == nullptr)) return OMNIPQ_EINVAL;
-  omnipq::AffineIn aff{};
-  aff.sums = fin_sums;
-  aff.gamma = gamma;
-  aff.beta = beta;
-  aff.conv_bias = conv_bias;
-  aff.running_mean = running_mean;
-  aff.running_var = running_var;
-  aff.a_out = a_out;
-  aff.b_out = b_out;
-  aff.mean_out = mean_out;
-  aff.invstd_out = invstd_out;
-  aff.count = count;
-  aff.eps = eps;
-  aff.momentum = momentum;
+  omnipq::AffineIn aff;
+  const int rc = bn_finalize_in(fin_sums, count, gamma, beta, eps, momentum, running_mean, running_var, conv_bias, a_out,
+                                b_out, mean_out, invstd_out, &aff);
+  if (rc) return rc;
   return gemm_nt_affine_impl(M, N, K, A, lda, aff, B, ldb, C, ldc, bias, sums, workspace, stream);
 }
 
@@ -1431,26 +1493,14 @@ extern "C" int omnipq_gemm_nt_e16_bnaffine_pool(int M, int N, int K, const void 
                                                  const float *bias, double *sums, float *workspace, int s, void *ymax,
                                                  void *ymin, unsigned char *amax, unsigned char *amin, const omnipq_row_plan *plan, void *stream) {
   omnipq::PlanScope plan_scope_(plan);            // the row plan is an ARGUMENT of the call (no ambient state)
-  if (!fin_sums || !gamma || !beta || !a_out || !b_out || !mean_out || !invstd_out || !(count > 0) || !sums)
-    return OMNIPQ_EINVAL;
-  if ((running_mean == nullptr) != (running_var == nullptr)) return OMNIPQ_EINVAL;
-  omnipq::PoolOut pool;
-  const int rc = pool_out_check(M, N, s, ymax, ymin, amax, amin, &pool);
+  if (!sums) return OMNIPQ_EINVAL;
+  omnipq::AffineIn aff;
+  int rc = bn_finalize_in(fin_sums, count, gamma, beta, eps, momentum, running_mean, running_var, conv_bias, a_out, b_out,
+                          mean_out, invstd_out, &aff);
   if (rc) return rc;
-  omnipq::AffineIn aff{};
-  aff.sums = fin_sums;
-  aff.gamma = gamma;
-  aff.beta = beta;
-  aff.conv_bias = conv_bias;
-  aff.running_mean = running_mean;
-  aff.running_var = running_var;
-  aff.a_out = a_out;
-  aff.b_out = b_out;
-  aff.mean_out = mean_out;
-  aff.invstd_out = invstd_out;
-  aff.count = count;
-  aff.eps = eps;
-  aff.momentum = momentum;
+  omnipq::PoolOut pool;
+  rc = pool_out_check(M, s, ymax, ymin, amax, amin, &pool);
+  if (rc) return rc;
   return gemm_nt_affine_impl(M, N, K, A, lda, aff, B, ldb, C, ldc, bias, sums, workspace, stream, pool);
 }
 
@@ -1460,32 +1510,15 @@ extern "C" int omnipq_gemm_nt_e16_stats_pool(int M, int N, int K, const void *A,
                                               int s, void *ymax, void *ymin, unsigned char *amax, unsigned char *amin,
                                               const omnipq_row_plan *plan, void *stream) {
   omnipq::PlanScope plan_scope_(plan);            // the row plan is an ARGUMENT of the call (no ambient state)
-  using namespace omnipq;
-  if (M < 0 || N < 0 || K < 0) return OMNIPQ_EINVAL;
-  if (M == 0 || N == 0) return OMNIPQ_OK;
-  if (!A || !B || !C || !sums || (K % GBK) || (N % 8) || (lda % 8) || (ldb % 8) || (ldc % 8)) return OMNIPQ_EINVAL;
-  PoolOut pool;
-  const int rc = pool_out_check(M, N, s, ymax, ymin, amax, amin, &pool);
+  int rc = gemm_nt_check(M, N, K, lda, ldb, ldc, A && B && C && sums);
+  if (rc != kNtGo) return rc;
+  NtCall c(M, N, K, A, lda, B, ldb, C, ldc, bias);
+  rc = pool_out_check(M, s, ymax, ymin, amax, amin, &c.pool);
   if (rc) return rc;
-  GemmArgs g{M, N, K, lda, ldb, ldc, K, (M + GBM - 1) / GBM, (N + GBN - 1) / GBN};
-  plan_rows(g);
-  const int groups = (g.m_tiles + 7) / 8;
-  dim3 grid(groups * 8 * g.n_tiles, 1, 1);
-  if (g.m_tiles <= kStatsDirectTiles) {
-    gemm_nt_kernel<false, 1><<<grid, 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B, C, bias,
-                                                                sums, BnBwdEpilogue(), AffineIn(), pool);
-    OMNIPQ_LAUNCH_CHECK();
-    return OMNIPQ_OK;
-  }
-  if (!workspace) return OMNIPQ_EINVAL;
-  if (g.rows_dev)
-    gemm_nt_kernel<false, 2, false, 128, 0, false, true><<<grid, 256, 0, (hipStream_t)stream>>>(
-        g, (const e16_t *)A, (const e16_t *)B, C, bias, workspace, BnBwdEpilogue(), AffineIn(), pool);
-  else
-    gemm_nt_kernel<false, 2><<<grid, 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B, C, bias,
-                                                                workspace, BnBwdEpilogue(), AffineIn(), pool);
-  OMNIPQ_LAUNCH_CHECK();
-  return stats_reduce(g, 2, workspace, sums, stream);
+  c.planned = true;
+  c.sums = sums;
+  c.workspace = workspace;
+  return gemm_nt_dispatch<kNtStats>(c, stream);
 }
 
 // Data-gradient GEMM of a conv+BN+ReLU stack with the BatchNorm-backward sums of the layer BELOW folded in:
@@ -1498,36 +1531,14 @@ extern "C" int omnipq_gemm_nt_e16_bnbwd(int M, int N, int K, const void *A, int 
                                          const float *mean, const float *invstd, double *sums, float *workspace,
                                          const omnipq_row_plan *plan, void *stream) {
   omnipq::PlanScope plan_scope_(plan);            // the row plan is an ARGUMENT of the call (no ambient state)
-  using namespace omnipq;
-  if (M < 0 || N < 0 || K < 0) return OMNIPQ_EINVAL;
-  if (M == 0 || N == 0) return OMNIPQ_OK;
-  if (!A || !B || !C || !sums || !Y || !a || !b || !mean || !invstd) return OMNIPQ_EINVAL;
-  if ((K % GBK) || (N % 8) || (lda % 8) || (ldb % 8) || (ldc % 8)) return OMNIPQ_EINVAL;
-  GemmArgs g{M, N, K, lda, ldb, ldc, K, (M + GBM - 1) / GBM, (N + GBN - 1) / GBN};
-  plan_rows(g);
-  const int groups = (g.m_tiles + 7) / 8;
-  dim3 grid(groups * 8 * g.n_tiles, 1, 1);
-  BnBwdEpilogue bn{(const e16_t *)Y, a, b, mean, invstd};
-  if (g.m_tiles <= kStatsDirectTiles) {
-    if (gemm_nt_small_tiles(M, N)) {
-      const GemmArgs gs = gemm_nt_args(M, N, K, lda, ldb, ldc, 64);
-      launch_small<3, false>(gs, A, B, C, nullptr, sums, bn, AffineIn(), stream);
-    } else {
-      gemm_nt_kernel<false, 3><<<grid, 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B, C,
-                                                                  nullptr, sums, bn);
-    }
-    OMNIPQ_LAUNCH_CHECK();
-    return OMNIPQ_OK;
-  }
-  if (!workspace) return OMNIPQ_EINVAL;
-  if (g.rows_dev)
-    gemm_nt_kernel<false, 4, false, 128, 0, false, true><<<grid, 256, 0, (hipStream_t)stream>>>(
-        g, (const e16_t *)A, (const e16_t *)B, C, nullptr, workspace, bn);
-  else
-    gemm_nt_kernel<false, 4><<<grid, 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B, C, nullptr,
-                                                                workspace, bn);
-  OMNIPQ_LAUNCH_CHECK();
-  return stats_reduce(g, 2, workspace, sums, stream);
+  const int rc = gemm_nt_check(M, N, K, lda, ldb, ldc, A && B && C && sums && Y && a && b && mean && invstd);
+  if (rc != kNtGo) return rc;
+  NtCall c(M, N, K, A, lda, B, ldb, C, ldc);
+  c.planned = true;
+  c.bn = omnipq::BnBwdEpilogue{(const omnipq::e16_t *)Y, a, b, mean, invstd};
+  c.sums = sums;
+  c.workspace = workspace;
+  return gemm_nt_dispatch<kNtBnBwd>(c, stream);
 }
 
 
@@ -1549,28 +1560,23 @@ extern "C" int omnipq_gemm_nt_e16_dz_bnbwd(int M, int N, int C3, const void *Y2,
   if ((N % 128) || (C3 % 128) || (lda % 8) || (ldb1 % 8) || (ldb2 % 8) || (ldc % 8) || lda != ldc || lda < N || ldb1 < N + GBK ||
       ldb2 < C3 || N + GBK > kAffMaxK || nsample < 8 || (nsample & (nsample - 1)))
     return OMNIPQ_EINVAL;
-  const int K = N + GBK;
-  GemmArgs g{M, N, K, lda, ldb1, ldc, K, (M + GBM - 1) / GBM, (N + GBN - 1) / GBN};
-  plan_rows(g);
-  if (!g.rows_dev || !g.row_w || g.m_tiles <= kStatsDirectTiles) return OMNIPQ_EINVAL;
+  NtCall c(M, N, N + GBK, Y2, lda, B1, ldb1, C, ldc);
+  c.planned = true;
   int sh = 0;
   while ((1 << sh) < nsample) ++sh;
-  DzGen dz;
-  dz.hot = hot;
-  dz.B2 = (const e16_t *)B2;
-  dz.unit_src = unit_src;
-  dz.C3 = C3;
-  dz.ldb2 = ldb2;
-  dz.s_shift = sh;
-  dz.X2out = (e16_t *)X2out;
-  BnBwdEpilogue bn{(const e16_t *)Y2, a, b, mean, invstd};
-  AffineIn aff{};
-  aff.a = a;
-  aff.b = b;
-  gemm_nt_kernel<false, 4, true, 128, 0, false, true, true><<<gemm_nt_grid(g), 256, 0, (hipStream_t)stream>>>(
-      g, (const e16_t *)Y2, (const e16_t *)B1, C, nullptr, workspace, bn, aff, PoolOut(), XyzGen(), dz);
-  OMNIPQ_LAUNCH_CHECK();
-  return stats_reduce(g, 2, workspace, sums, stream);
+  c.dz.hot = hot;
+  c.dz.B2 = (const e16_t *)B2;
+  c.dz.unit_src = unit_src;
+  c.dz.C3 = C3;
+  c.dz.ldb2 = ldb2;
+  c.dz.s_shift = sh;
+  c.dz.X2out = (e16_t *)X2out;
+  c.bn = BnBwdEpilogue{(const e16_t *)Y2, a, b, mean, invstd};
+  c.aff.a = a;
+  c.aff.b = b;
+  c.sums = sums;
+  c.workspace = workspace;
+  return gemm_nt_dispatch<kNtBnBwd, true, 0, true>(c, stream);
 }
 
 
@@ -1591,40 +1597,18 @@ extern "C" int omnipq_gemm_nt_e16_xyz_bnaffine(int M, int N, int K, const void *
                                                 float *workspace, const omnipq_row_plan *plan, void *stream) {
   omnipq::PlanScope plan_scope_(plan);            // the row plan is an ARGUMENT of the call (no ambient state)
   using namespace omnipq;
-  if (M < 0 || N < 0 || K < 0) return OMNIPQ_EINVAL;
-  if (M == 0 || N == 0) return OMNIPQ_OK;
-  if (!X0 || !W0 || !B || !C || !sums || !workspace || (K % GBK) || (N % 8) || (ldb % 8) || (ldc % 8) || K > kXgMaxC ||
-      (ldx % 4) || (ldw0 % 4) || ldx < 3 || ldw0 < 3)
-    return OMNIPQ_EINVAL;
-  if (!fin_sums || !gamma || !beta || !a_out || !b_out || !mean_out || !invstd_out || !(count > 0)) return OMNIPQ_EINVAL;
-  if ((running_mean == nullptr) != (running_var == nullptr)) return OMNIPQ_EINVAL;
-  GemmArgs g{M, N, K, 0, ldb, ldc, K, (M + GBM - 1) / GBM, (N + GBN - 1) / GBN};
-  plan_rows(g);
-  if (g.m_tiles <= kStatsDirectTiles) return OMNIPQ_EINVAL;
-  AffineIn aff{};
-  aff.sums = fin_sums;
-  aff.gamma = gamma;
-  aff.beta = beta;
-  aff.running_mean = running_mean;
-  aff.running_var = running_var;
-  aff.a_out = a_out;
-  aff.b_out = b_out;
-  aff.mean_out = mean_out;
-  aff.invstd_out = invstd_out;
-  aff.count = count;
-  aff.eps = eps;
-  aff.momentum = momentum;
-  const XyzGen xg{(const e16_t *)X0, ldx, (const e16_t *)W0, ldw0};
-  const int groups = (g.m_tiles + 7) / 8;
-  dim3 grid(groups * 8 * g.n_tiles, 1, 1);
-  if (g.rows_dev)
-    gemm_nt_kernel<false, 2, true, 128, 1, false, true><<<grid, 256, 0, (hipStream_t)stream>>>(
-        g, (const e16_t *)B, (const e16_t *)B, C, nullptr, workspace, BnBwdEpilogue(), aff, PoolOut(), xg);
-  else
-    gemm_nt_kernel<false, 2, true, 128, 1><<<grid, 256, 0, (hipStream_t)stream>>>(
-        g, (const e16_t *)B, (const e16_t *)B, C, nullptr, workspace, BnBwdEpilogue(), aff, PoolOut(), xg);
-  OMNIPQ_LAUNCH_CHECK();
-  return stats_reduce(g, 2, workspace, sums, stream);
+  int rc = gemm_nt_check(M, N, K, 0, ldb, ldc, X0 && W0 && B && C && sums && workspace);
+  if (rc != kNtGo) return rc;
+  if (K > kXgMaxC || (ldx % 4) || (ldw0 % 4) || ldx < 3 || ldw0 < 3) return OMNIPQ_EINVAL;
+  NtCall c(M, N, K, B, 0, B, ldb, C, ldc);        // (the A operand is generated: never read)
+  rc = bn_finalize_in(fin_sums, count, gamma, beta, eps, momentum, running_mean, running_var, nullptr, a_out, b_out,
+                      mean_out, invstd_out, &c.aff);
+  if (rc) return rc;
+  c.planned = true;
+  c.xg = XyzGen{(const e16_t *)X0, ldx, (const e16_t *)W0, ldw0};
+  c.sums = sums;
+  c.workspace = workspace;
+  return gemm_nt_dispatch<kNtStats, true, 1>(c, stream);
 }
 
 // The data-gradient GEMM into that first layer, reduced to what is needed of it: with dX = A B^T (A = dY of the layer
@@ -1637,45 +1621,25 @@ extern "C" int omnipq_gemm_nt_e16_xyz_bnbwd(int M, int N, int K, const void *A, 
                                              float *workspace, const omnipq_row_plan *plan, void *stream) {
   omnipq::PlanScope plan_scope_(plan);            // the row plan is an ARGUMENT of the call (no ambient state)
   using namespace omnipq;
-  if (M < 0 || N < 0 || K < 0) return OMNIPQ_EINVAL;
-  if (M == 0 || N == 0) return OMNIPQ_OK;
-  if (!A || !B || !X0 || !W0 || !sums5 || !workspace || !a || !b || !mean || !invstd) return OMNIPQ_EINVAL;
-  if ((K % GBK) || (N % 8) || (lda % 8) || (ldb % 8) || N > kXgMaxC || (ldx % 4) || (ldw0 % 4) || ldx < 3 || ldw0 < 3)
-    return OMNIPQ_EINVAL;
-  GemmArgs g{M, N, K, lda, ldb, N, K, (M + GBM - 1) / GBM, (N + GBN - 1) / GBN};
-  plan_rows(g);
-  if (g.m_tiles <= kStatsDirectTiles) return OMNIPQ_EINVAL;
-  const XyzGen xg{(const e16_t *)X0, ldx, (const e16_t *)W0, ldw0};
-  const BnBwdEpilogue bn{nullptr, a, b, mean, invstd};
-  const int groups = (g.m_tiles + 7) / 8;
-  dim3 grid(groups * 8 * g.n_tiles, 1, 1);
-  if (g.rows_dev)
-    gemm_nt_kernel<false, 4, false, 128, 2, false, true><<<grid, 256, 0, (hipStream_t)stream>>>(
-        g, (const e16_t *)A, (const e16_t *)B, nullptr, nullptr, workspace, bn, AffineIn(), PoolOut(), xg);
-  else
-    gemm_nt_kernel<false, 4, false, 128, 2><<<grid, 256, 0, (hipStream_t)stream>>>(
-        g, (const e16_t *)A, (const e16_t *)B, nullptr, nullptr, workspace, bn, AffineIn(), PoolOut(), xg);
-  OMNIPQ_LAUNCH_CHECK();
-  return stats_reduce(g, 5, workspace, sums5, stream);
+  const int rc = gemm_nt_check(M, N, K, lda, ldb, N, A && B && X0 && W0 && sums5 && workspace && a && b && mean && invstd);
+  if (rc != kNtGo) return rc;
+  if (N > kXgMaxC || (ldx % 4) || (ldw0 % 4) || ldx < 3 || ldw0 < 3) return OMNIPQ_EINVAL;
+  NtCall c(M, N, K, A, lda, B, ldb, nullptr, N);
+  c.planned = true;
+  c.xg = XyzGen{(const e16_t *)X0, ldx, (const e16_t *)W0, ldw0};
+  c.bn = BnBwdEpilogue{nullptr, a, b, mean, invstd};
+  c.sums = sums5;
+  c.workspace = workspace;
+  c.n_sums = 5;
+  return gemm_nt_dispatch<kNtBnBwd, false, 2>(c, stream);
 }
 
 // Same with a per-column f32 bias added to the accumulators before rounding:  C = A B^T + bias[n].
 extern "C" int omnipq_gemm_nt_e16_bias(int M, int N, int K, const void *A, int lda, const void *B, int ldb,
                                         void *C, int ldc, const float *bias, void *stream) {
-  using namespace omnipq;
-  if (M < 0 || N < 0 || K < 0) return OMNIPQ_EINVAL;
-  if (M == 0 || N == 0) return OMNIPQ_OK;
-  if (!A || !B || !C || (K % GBK) || (N % 8) || (lda % 8) || (ldb % 8) || (ldc % 8)) return OMNIPQ_EINVAL;
-  if (gemm_nt_small_tiles(M, N)) {
-    const GemmArgs g = gemm_nt_args(M, N, K, lda, ldb, ldc, 64);
-    launch_small<0, false>(g, A, B, C, bias, nullptr, BnBwdEpilogue(), AffineIn(), stream);
-  } else {
-    const GemmArgs g = gemm_nt_args(M, N, K, lda, ldb, ldc, 128);
-    gemm_nt_kernel<false><<<gemm_nt_grid(g), 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B, C,
-                                                                          bias);
-  }
-  OMNIPQ_LAUNCH_CHECK();
-  return OMNIPQ_OK;
+  const int rc = gemm_nt_check(M, N, K, lda, ldb, ldc, A && B && C);
+  if (rc != kNtGo) return rc;
+  return gemm_nt_dispatch<kNtPlain>(NtCall(M, N, K, A, lda, B, ldb, C, ldc, bias), stream);
 }
 
 // C = dropout(relu(A B^T + bias)): the decoder feed-forward's first linear layer with its activation pass in the epilogue.
@@ -1684,28 +1648,20 @@ extern "C" int omnipq_gemm_nt_e16_bias(int M, int N, int K, const void *A, int l
 extern "C" int omnipq_gemm_nt_e16_relu_dropout(int M, int N, int K, const void *A, int lda, const void *B, int ldb,
                                                 void *C, int ldc, const float *bias, float dropout_p,
                                                 const unsigned long long *seed_ptr, unsigned salt, void *stream) {
-  using namespace omnipq;
-  if (M < 0 || N < 0 || K < 0) return OMNIPQ_EINVAL;
-  if (M == 0 || N == 0) return OMNIPQ_OK;
-  if (!A || !B || !C || (K % GBK) || (N % 8) || (lda % 8) || (ldb % 8) || (ldc % 8)) return OMNIPQ_EINVAL;
+  const int rc = gemm_nt_check(M, N, K, lda, ldb, ldc, A && B && C);
+  if (rc != kNtGo) return rc;
   if (!(dropout_p >= 0.f) || dropout_p >= 1.f || (dropout_p > 0.f && !seed_ptr)) return OMNIPQ_EINVAL;
   if ((long long)M * ldc >= (1ll << 32)) return OMNIPQ_ETOOLARGE;
-  const bool small = gemm_nt_small_tiles(M, N);
-  GemmArgs g = gemm_nt_args(M, N, K, lda, ldb, ldc, small ? 64 : 128);
-  g.relu = 1;
+  NtCall c(M, N, K, A, lda, B, ldb, C, ldc, bias);
+  c.g.relu = 1;
   if (dropout_p > 0.f) {
     const double th = (double)dropout_p * 4294967296.0;                     // as decoder_ops.hip: drop_params
-    g.drop_thresh = (unsigned)(th < 1.0 ? 1.0 : (th > 4294967295.0 ? 4294967295.0 : th));
-    g.drop_keep_inv = 1.0f / (1.0f - dropout_p);
-    g.drop_seed = seed_ptr;
-    g.drop_salt = salt;
+    c.g.drop_thresh = (unsigned)(th < 1.0 ? 1.0 : (th > 4294967295.0 ? 4294967295.0 : th));
+    c.g.drop_keep_inv = 1.0f / (1.0f - dropout_p);
+    c.g.drop_seed = seed_ptr;
+    c.g.drop_salt = salt;
   }
-  if (small)
-    launch_small<0, false>(g, A, B, C, bias, nullptr, BnBwdEpilogue(), AffineIn(), stream);
-  else
-    gemm_nt_kernel<false><<<gemm_nt_grid(g), 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B, C, bias);
-  OMNIPQ_LAUNCH_CHECK();
-  return OMNIPQ_OK;
+  return gemm_nt_dispatch<kNtPlain>(c, stream);
 }
 
 // C = (H > 0) ? (A B^T) / (1 - p) : 0: a data-gradient GEMM whose result passes backwards through dropout(relu(.)), H
@@ -1713,22 +1669,13 @@ extern "C" int omnipq_gemm_nt_e16_relu_dropout(int M, int N, int K, const void *
 // omnipq_relu_dropout_bwd does to the stored product, in the epilogue (same bits: the product is rounded to bf16 first).
 extern "C" int omnipq_gemm_nt_e16_mask(int M, int N, int K, const void *A, int lda, const void *B, int ldb, void *C,
                                         int ldc, const void *H, float dropout_p, void *stream) {
-  using namespace omnipq;
-  if (M < 0 || N < 0 || K < 0) return OMNIPQ_EINVAL;
-  if (M == 0 || N == 0) return OMNIPQ_OK;
-  if (!A || !B || !C || !H || (K % GBK) || (N % 8) || (lda % 8) || (ldb % 8) || (ldc % 8)) return OMNIPQ_EINVAL;
+  const int rc = gemm_nt_check(M, N, K, lda, ldb, ldc, A && B && C && H);
+  if (rc != kNtGo) return rc;
   if (!(dropout_p >= 0.f) || dropout_p >= 1.f) return OMNIPQ_EINVAL;
-  const bool small = gemm_nt_small_tiles(M, N);
-  GemmArgs g = gemm_nt_args(M, N, K, lda, ldb, ldc, small ? 64 : 128);
-  g.drop_keep_inv = 1.0f / (1.0f - dropout_p);
-  const BnBwdEpilogue bn{(const e16_t *)H, nullptr, nullptr, nullptr, nullptr};
-  if (small)
-    launch_small<5, false>(g, A, B, C, nullptr, nullptr, bn, AffineIn(), stream);
-  else
-    gemm_nt_kernel<false, 5><<<gemm_nt_grid(g), 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B, C,
-                                                                            nullptr, nullptr, bn);
-  OMNIPQ_LAUNCH_CHECK();
-  return OMNIPQ_OK;
+  NtCall c(M, N, K, A, lda, B, ldb, C, ldc);
+  c.g.drop_keep_inv = 1.0f / (1.0f - dropout_p);
+  c.bn.Y = (const omnipq::e16_t *)H;
+  return gemm_nt_dispatch<kNtMask>(c, stream);
 }
 
 // C = A B^T + bias (bias may be NULL) with an optional workspace of omnipq_gemm_nt_workspace_floats(M, N, K)
@@ -1736,50 +1683,22 @@ extern "C" int omnipq_gemm_nt_e16_mask(int M, int N, int K, const void *A, int l
 // per tile (same result up to f32 summation order, one rounding to bf16 at the end).
 extern "C" int omnipq_gemm_nt_e16_ws(int M, int N, int K, const void *A, int lda, const void *B, int ldb, void *C,
                                       int ldc, const float *bias, float *workspace, void *stream) {
-  using namespace omnipq;
-  if (M < 0 || N < 0 || K < 0) return OMNIPQ_EINVAL;
-  if (M == 0 || N == 0) return OMNIPQ_OK;
-  if (!A || !B || !C || (K % GBK) || (N % 8) || (lda % 8) || (ldb % 8) || (ldc % 8)) return OMNIPQ_EINVAL;
+  const int rc = gemm_nt_check(M, N, K, lda, ldb, ldc, A && B && C);
+  if (rc != kNtGo) return rc;
   const SplitPlan plan = gemm_nt_split_plan(M, N, K);
   if (plan.slabs > 1 && workspace && ldc == N)
     return gemm_nt_splitk_bf16(M, N, K, A, lda, B, ldb, C, ldc, bias, workspace, plan, stream);
-  if (gemm_nt_small_tiles(M, N)) {
-    const GemmArgs g = gemm_nt_args(M, N, K, lda, ldb, ldc, 64);
-    launch_small<0, false>(g, A, B, C, bias, nullptr, BnBwdEpilogue(), AffineIn(), stream);
-  } else {
-    const GemmArgs g = gemm_nt_args(M, N, K, lda, ldb, ldc, 128);
-    gemm_nt_kernel<false><<<gemm_nt_grid(g), 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B, C,
-                                                                          bias);
-  }
-  OMNIPQ_LAUNCH_CHECK();
-  return OMNIPQ_OK;
+  return gemm_nt_dispatch<kNtPlain>(NtCall(M, N, K, A, lda, B, ldb, C, ldc, bias), stream);
 }
 
 // C (f32 [M][ldc]) = A[M][K] B[N][K]^T, one workgroup per tile over the whole contraction (no split): the per-point first
 // layer of a set-abstraction stage (csrc/sa_stage.hip: sa_l1_rows_kernel) and the data gradient that leaves it.  N % 4 == 0.
 extern "C" int omnipq_gemm_nt_e16_f32(int M, int N, int K, const void *A, int lda, const void *B, int ldb, float *C, int ldc,
                                        void *stream) {
-  using namespace omnipq;
-  if (M < 0 || N < 0 || K < 0) return OMNIPQ_EINVAL;
-  if (M == 0 || N == 0) return OMNIPQ_OK;
-  if (!A || !B || !C || (K % GBK) || (N % 4) || (lda % 8) || (ldb % 8) || (ldc % 4) || ldc < N) return OMNIPQ_EINVAL;
-  {
-    HeldLaunch &h = held_launch();
-    if (h.full) {
-      h.full = h.armed = false;
-      h.single(h);
-    }
-  }
-  if (gemm_nt_small_tiles(M, N)) {
-    const GemmArgs g = gemm_nt_args(M, N, K, lda, ldb, ldc, 64);
-    gemm_nt_kernel<true, 0, false, 64><<<gemm_nt_grid(g), 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B,
-                                                                                        C, nullptr);
-  } else {
-    const GemmArgs g = gemm_nt_args(M, N, K, lda, ldb, ldc, 128);
-    gemm_nt_kernel<true><<<gemm_nt_grid(g), 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B, C, nullptr);
-  }
-  OMNIPQ_LAUNCH_CHECK();
-  return OMNIPQ_OK;
+  const int rc = gemm_nt_check(M, N, K, lda, ldb, ldc, A && B && C, 4);
+  if (rc != kNtGo) return rc;
+  if (ldc < N) return OMNIPQ_EINVAL;
+  return gemm_nt_dispatch<kNtF32>(NtCall(M, N, K, A, lda, B, ldb, C, ldc), stream);
 }
 
 // C[M][N] (f32) = A[M][K] * B[N][K]^T with K split into `slabs` slices; `workspace` holds
@@ -1787,17 +1706,15 @@ extern "C" int omnipq_gemm_nt_e16_f32(int M, int N, int K, const void *A, int ld
 extern "C" int omnipq_gemm_nt_e16_splitk(int M, int N, int K, const void *A, int lda, const void *B, int ldb,
                                           float *C, int slabs, float *workspace, void *stream) {
   using namespace omnipq;
-  if (M < 0 || N < 0 || K < 0 || slabs < 1) return OMNIPQ_EINVAL;
-  if (M == 0 || N == 0) return OMNIPQ_OK;
-  if (!A || !B || !C || !workspace || (K % GBK) || (N % 4) || (lda % 8) || (ldb % 8)) return OMNIPQ_EINVAL;
-  int k_chunk = ((K / GBK + slabs - 1) / slabs) * GBK;
-  if (k_chunk < GBK) k_chunk = GBK;
-  const int used = (K + k_chunk - 1) / k_chunk;
-  GemmArgs g{M, N, K, lda, ldb, N, k_chunk, (M + GBM - 1) / GBM, (N + GBN - 1) / GBN};
-  const int groups = (g.m_tiles + 7) / 8;
-  dim3 grid(groups * 8 * g.n_tiles, 1, used);
-  gemm_nt_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B, workspace,
-                                                           nullptr);
+  if (slabs < 1) return OMNIPQ_EINVAL;
+  const int rc = gemm_nt_check(M, N, K, lda, ldb, N, A && B && C && workspace, 4);
+  if (rc != kNtGo) return rc;
+  GemmArgs g = gemm_nt_args(M, N, K, lda, ldb, N, 128);
+  g.k_chunk = ((K / GBK + slabs - 1) / slabs) * GBK;
+  if (g.k_chunk < GBK) g.k_chunk = GBK;
+  const int used = (K + g.k_chunk - 1) / g.k_chunk;
+  gemm_nt_kernel<true><<<gemm_nt_grid(g, used), 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B,
+                                                                             workspace, nullptr);
   OMNIPQ_LAUNCH_CHECK();
   const int n = M * N;
   splitk_reduce_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(n, used, workspace, C);

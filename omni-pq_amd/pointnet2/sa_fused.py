@@ -17,6 +17,7 @@ statistics are f32 per block / f64 across blocks.  This is the `bf16` compute mo
 parity mode keeps the reference's op-by-op composition (pointnet2_modules.py).
 """
 import ctypes
+import functools
 import os
 import threading
 import weakref
@@ -227,12 +228,25 @@ def gemm_nt_into(A, B, C, M, N, K, bias=None):
     _call(_lib.omnipq_gemm_nt_e16_ws, A, M, N, K, _p(A), K, _p(B), K, _p(C), N, _p(bias), _p(ws))
 
 
+def _stats_workspace(M, N, device):
+    """the partial-sum workspace of a statistics GEMM over M rows (omnipq_gemm_nt_stats_workspace_floats); None for the row
+    counts whose statistics go straight to f64 atomics"""
+    n_ws = int(_lib.omnipq_gemm_nt_stats_workspace_floats(M, N))
+    return torch.empty((n_ws,), device=device, dtype=torch.float32) if n_ws else None
+
+
+@functools.lru_cache(maxsize=None)
+def _partial_sum_rows(P):
+    """P rows take the statistics GEMMs' partial-sum path (the threshold is the library's: csrc/gemm_bf16.hip,
+    kStatsDirectTiles); cached: the eager step asks once per row count, not once per stage"""
+    return int(_lib.omnipq_gemm_nt_stats_workspace_floats(P, 8)) > 0
+
+
 def _gemm_nt_stats(A, B, M, N, K, sums, bias=None, pool=None):
     """bf16 C = A B^T and, in the same pass, sums (f64 [2][N], zero on entry) += column sum / sum of squares;
     pool = (S, ymax, ymin, amax, amin): also the extrema of every ball of S rows (csrc/gemm_bf16.hip: PoolOut)."""
     C = torch.empty((M, N), device=A.device, dtype=E16.dtype)
-    n_ws = int(_lib.omnipq_gemm_nt_stats_workspace_floats(M, N))
-    ws = torch.empty((n_ws,), device=A.device, dtype=torch.float32) if n_ws else None
+    ws = _stats_workspace(M, N, A.device)
     if pool is not None:
         S, ymax, ymin, amax, amin = pool
         _call(_lib.omnipq_gemm_nt_e16_stats_pool, A, M, N, K, _p(A), K, _p(B), K, _p(C), N, _p(bias), _p(sums), _p(ws),
@@ -425,10 +439,7 @@ def gemm_nt_affine(Y, below, Bw, M, N, K, sums=None, bias=None, out=None, pool=N
     """bf16 C = relu(below.a * Y + below.b) Bw^T (+ bias); sums (f64 [2][N], zero on entry): also C's statistics.
     store=False (with pool, on a plan): C is not written -- statistics and ball extrema only; returns None."""
     C = (torch.empty((M, N), device=Y.device, dtype=E16.dtype) if out is None else out) if store else None
-    ws = None
-    if sums is not None:
-        n_ws = int(_lib.omnipq_gemm_nt_stats_workspace_floats(M, N))
-        ws = torch.empty((n_ws,), device=Y.device, dtype=torch.float32) if n_ws else None
+    ws = _stats_workspace(M, N, Y.device) if sums is not None else None
     fin = getattr(below, "fin", None)
     if fin is not None:
         # the layer below has not been finalised yet: this GEMM's prologue derives a / b from its totals (and stores
@@ -464,8 +475,8 @@ xyzgen_uses = 0            # forwards that took the path (tests check that it is
 
 def xyzgen_ok(P, L, c0, needs_input_grad):
     """first layer generated from coordinates: training, no features, at least three layers (the second is not the pooled
-    one), more than 64 row tiles (the kernels' partial-sum path), no gradient into the coordinates"""
-    return XYZGEN and L >= 3 and P > 64 * 128 and c0 <= 256 and c0 % 8 == 0 and not needs_input_grad
+    one), the row counts of the kernels' partial-sum path, no gradient into the coordinates"""
+    return XYZGEN and L >= 3 and _partial_sum_rows(P) and c0 <= 256 and c0 % 8 == 0 and not needs_input_grad
 
 
 # The first layer of a stage WITH features on the SOURCE points (round 5; include/omnipq_sa.h: omnipq_sa_l1_rows).  The first
@@ -500,10 +511,10 @@ last_no_dy_uses = 0
 
 def last_no_dy_ok(plan, L, P, c2, c3, S, below_keeps_y_only):
     """a plan with its unit map, the layer below consumed as (Y, a, b), whole 128-column tiles on both sides, and more
-    row tiles than the statistics take straight to f64 atomics (P rows: ceil(P / 128) > 64, as omnipq_gemm_nt_e16_dz_bnbwd
+    row tiles than the statistics take straight to f64 atomics (P rows on the partial-sum path, as omnipq_gemm_nt_e16_dz_bnbwd
     and the no-store omnipq_gemm_nt_e16_bnaffine_pool require)"""
     return LAST_NO_DY and c3 <= LAST_NO_DY_MAX_C3 and plan is not None and getattr(plan, "unit_src", None) is not None and L >= 2 and \
-        (P + 127) // 128 > 64 and below_keeps_y_only and c2 % 128 == 0 and c3 % 128 == 0 and c2 + 32 <= 1024 and S >= 8 and \
+        _partial_sum_rows(P) and below_keeps_y_only and c2 % 128 == 0 and c3 % 128 == 0 and c2 + 32 <= 1024 and S >= 8 and \
         (S & (S - 1)) == 0 and AFFINE_OPERANDS and POOL_EPILOGUE and _FOLD_SMALL
 
 
@@ -534,7 +545,7 @@ def gemm_nt_f32(A, B, M, N, K, lda, ldb):
 def gemm_nt_xyz(X0c, below, Bw, M, N, K, sums):
     """bf16 C = relu(bn(X0c W0^T)) Bw^T + its statistics: `below` is the never-materialised first layer (Wp, fin)."""
     C = torch.empty((M, N), device=X0c.device, dtype=E16.dtype)
-    ws = torch.empty((int(_lib.omnipq_gemm_nt_stats_workspace_floats(M, N)),), device=X0c.device, dtype=torch.float32)
+    ws = _stats_workspace(M, N, X0c.device)
     fsums, count, gamma, beta, eps, momentum, rm, rv, _ = below.fin
     below.fin = None
     _call(_lib.omnipq_gemm_nt_e16_xyz_bnaffine, X0c, M, N, K, _p(X0c), X0c.shape[1], _p(below.Wp), below.Wp.shape[1],
@@ -547,8 +558,7 @@ def _gemm_nt_bnbwd(dY, Wt, M, N, K, below, sums):
     """dX = dY Wt^T (bf16 [M][N]) and, in the same pass, the BatchNorm-backward sums of the layer `below`
     (its pre-BN output Y and constants a, b, mean, invstd) into sums (f64 [>=2][N], zero on entry)."""
     C = torch.empty((M, N), device=dY.device, dtype=E16.dtype)
-    n_ws = int(_lib.omnipq_gemm_nt_stats_workspace_floats(M, N))
-    ws = torch.empty((n_ws,), device=dY.device, dtype=torch.float32) if n_ws else None
+    ws = _stats_workspace(M, N, dY.device)
     _call(_lib.omnipq_gemm_nt_e16_bnbwd, dY, M, N, K, _p(dY), K, _p(Wt), K, _p(C), N, _p(below.Y), _p(below.a),
           _p(below.b), _p(below.mean), _p(below.invstd), _p(sums), _p(ws))
     return C
@@ -1558,8 +1568,7 @@ class FusedSAStage(torch.autograd.Function):
             X2 = torch.empty((P, C2), device=dev, dtype=E16.dtype) if (want_w and LAST_X2) else None
             pend0 = zeros_f64(3, below.C, dev)
             dX2 = torch.empty((P, C2), device=dev, dtype=E16.dtype)
-            n_ws = int(_lib.omnipq_gemm_nt_stats_workspace_floats(P, C2))
-            ws = torch.empty((n_ws,), device=dev, dtype=torch.float32)
+            ws = _stats_workspace(P, C2, dev)
             _call(_lib.omnipq_gemm_nt_e16_dz_bnbwd, dX2, P, C2, C3, _p(below.Y), C2, _p(B1), C2 + 32, _p(last.Wt),
                   last.Wt.stride(0), _p(hot), _p(plan.unit_src), S, _p(dX2), C2, _p(below.a), _p(below.b), _p(below.mean),
                   _p(below.invstd), _p(pend0), _p(ws), _p(X2))

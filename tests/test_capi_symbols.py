@@ -44,6 +44,50 @@ def test_libraries_have_gfx950_code_objects_with_their_mfma_opcode(built_lib, tm
         assert asm.count(opcode) >= 100 and other not in asm, (path, asm.count(opcode), asm.count(other))
 
 
+# gemm_nt_kernel<OUT_F32, STATS, AFF, T, XG, KRES, PLAN, DZ> and gemm_nt_pair_kernel<STATS, AFF> as the entry points of
+# csrc/gemm_bf16.hip reach them (the list of the build before they were put behind one dispatcher).  Every instantiation
+# costs about a second of compile time per element type: one that nothing can reach must not appear silently.
+_F, _T = "false", "true"
+_NT_KERNELS = {(_T, 0, _F, 64, 0, _F, _F, _F), (_T, 0, _F, 128, 0, _F, _F, _F)}                 # f32 out (and split-K)
+_NT_KERNELS |= {(_F, st, aff, 64, 0, kres, _F, _F)                                              # 64 x 64 tiles
+                for st, aff in ((0, _F), (1, _F), (0, _T), (1, _T), (3, _F), (5, _F)) for kres in (_T, _F)}
+_NT_KERNELS |= {(_F, st, aff, 128, 0, _F, _F, _F)                                               # 128 x 128 tiles, every row
+                for st, aff in ((0, _F), (1, _F), (2, _F), (0, _T), (1, _T), (2, _T), (3, _F), (4, _F), (5, _F))}
+_NT_KERNELS |= {(_F, st, aff, 128, 0, _F, _T, _F) for st, aff in ((0, _F), (2, _F), (2, _T), (4, _F))}     # ... on a row plan
+_NT_KERNELS |= {(_F, 4, _T, 128, 0, _F, _T, _T)}                                                # DZ: with a plan only
+_NT_KERNELS |= {(_F, 2, _T, 128, 1, _F, plan, _F) for plan in (_T, _F)}                         # XG = 1
+_NT_KERNELS |= {(_F, 4, _F, 128, 2, _F, plan, _F) for plan in (_T, _F)}                         # XG = 2
+_NT_PAIR_KERNELS = {(0, _F), (1, _F), (0, _T), (1, _T), (3, _F), (5, _F)}
+
+
+def test_nt_gemm_instantiations_are_the_listed_ones(built_lib, tmp_path):
+    """The bf16 library holds exactly the 32 gemm_nt_kernel and 6 gemm_nt_pair_kernel instantiations written out above
+    (demangled symbol tables of the bundled code objects)."""
+    import glob
+    import os
+    import re
+    import shutil
+    import subprocess
+    assert len(_NT_KERNELS) == 32 and len(_NT_PAIR_KERNELS) == 6
+    objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
+    if not os.path.exists(objdump):
+        return
+    shutil.copy(built_lib, tmp_path)
+    subprocess.run([objdump, "--offloading", os.path.basename(built_lib)], cwd=tmp_path, capture_output=True)
+    syms = "".join(subprocess.run([objdump, "-t", "-C", f], capture_output=True, text=True).stdout
+                   for f in glob.glob(str(tmp_path / "*gfx950")))
+    if "omnipq::" not in syms:
+        return                                        # this objdump could not open the bundles: nothing to check
+
+    def word(w):
+        return w if w in (_F, _T) else int(w)
+
+    found = {(m.group(1), tuple(word(w.strip()) for w in m.group(2).split(",")))
+             for m in re.finditer(r"omnipq::(gemm_nt_kernel|gemm_nt_pair_kernel)<([^<>]*)>", syms)}
+    want = {("gemm_nt_kernel", t) for t in _NT_KERNELS} | {("gemm_nt_pair_kernel", t) for t in _NT_PAIR_KERNELS}
+    assert sorted(found - want) == [] and sorted(want - found) == [], (sorted(found - want), sorted(want - found))
+
+
 def test_library_names_its_plan_aware_entry_points(built_lib):
     """the binding takes the set of plan-aware entry points from the LIBRARY it loaded (a build-time constant: the
     names whose reported signature has a `P`), and refuses a library of another ABI version; here: that set equals what the
