@@ -1,0 +1,72 @@
+/*
+ * omnipq_optim.h -- C ABI of the fused gradient clipping + AdamW step (libomnipq_pointops.so).
+ *
+ * The three lines of the reference's training step that change the weights (train.py:562-566)
+ *     grad_total_norm = clip_grad_norm_(model.parameters(), config.clip_norm)
+ *     optimizer.step()          AdamW over two parameter groups, train.py:364-374
+ * as three launches over ALL parameter tensors: squared-norm partials, finalise, update.  No launch takes a
+ * hyper-parameter as a kernel argument: learning rates, betas, eps, weight decay, max_norm and grad_scale are read from
+ * device memory, and so are the step count and the bias corrections -- a launch captured into a hipGraph follows a
+ * learning-rate schedule when it is replayed.
+ *
+ * Device data (all pointers below are device pointers unless a name ends in _host):
+ *   records   nrec packed 48-byte records
+ *                 { float *param; const float *grad; float *exp_avg; float *exp_avg_sq; int64_t numel; int32_t group;
+ *                   int32_t reserved; }
+ *             contiguous f32 tensors at ANY 4-byte-aligned address (parameters may be views into joint matrices): a chunk whose
+ *             tensors share one phase modulo 16 bytes moves as 16-byte vectors around a peeled head and tail, any other chunk
+ *             element by element.
+ *   chunks    nchunks x int32[2] = { record, chunk of `chunk_elems` elements of it }; chunk_elems is a multiple of 1024.
+ *   hyper     (ngroups + 1) rows of 8 doubles.  Row g < ngroups: { lr, beta1, beta2, eps, weight_decay, 0, 0, 0 } of
+ *             parameter group g; row ngroups: { max_norm, grad_scale, 0, ... }.  Doubles, because torch.optim.AdamW
+ *             evaluates 1 - beta2, 1 - lr * weight_decay, lr / (1 - beta1^t) and sqrt(1 - beta2^t) in double precision
+ *             before it rounds them to the tensors' f32.
+ *   partials  nchunks doubles (scratch).
+ *   counters  int64[2] = { t, skipped }: optimiser steps taken, steps skipped for a non-finite gradient norm.
+ *   result    float[4] = { total_norm, clip_coef, found_nonfinite (0 or 1), grad_scale * clip_coef }.
+ *   coef      ngroups rows of 8 floats, written by the finalise launch for the update launch:
+ *             { 1 - lr * wd, beta1, 1 - beta1, beta2, 1 - beta2, lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t), eps }.
+ *
+ * `.grad` is READ-ONLY here: the clipped (and un-scaled) gradient g' = grad_scale * clip_coef * g exists in registers
+ * only and is never written back.  Nothing in the reference reads the gradients after train.py:564; a caller that wants the
+ * clipped gradients in memory must keep torch.nn.utils.clip_grad_norm_.
+ *
+ * Every entry point validates its host arguments (null tables, negative counts, ngroups < 1, a chunk size that is not a
+ * positive multiple of 1024) and returns OMNIPQ_EINVAL before anything is launched.  What a DEVICE table holds cannot be seen
+ * from the host: omnipq_adamw_check_table validates the host copy a binding is about to upload.
+ */
+#ifndef OMNIPQ_OPTIM_H
+#define OMNIPQ_OPTIM_H
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* HOST arrays, nothing is launched: OMNIPQ_EINVAL for a record with a null pointer, a negative numel or a `group` outside
+ * [0, ngroups), and for a chunk entry that names no record or lies past its record's last element. */
+int omnipq_adamw_check_table(int nrec, const void *records_host, int nchunks, const int *chunks_host, int ngroups,
+                             int chunk_elems);
+
+/* clip_grad_norm_, first half (train.py:562; torch/nn/utils/clip_grad.py: the 2-norm over all gradients):
+ * partials[c] = sum over chunk c of (grad_scale * g)^2, accumulated in f64 in a fixed order.  No atomics: the same
+ * gradients give the same bits. */
+int omnipq_adamw_grad_sqnorm(int nrec, int nchunks, const void *records, const int *chunks, int chunk_elems,
+                             const double *hyper, int ngroups, double *partials, void *stream);
+
+/* clip_grad_norm_, second half, and the scalar part of AdamW.step (train.py:562-563), one workgroup:
+ *   total_norm = sqrt(sum of partials)  (f64, rounded once to f32)    clip_coef = min(1, max_norm / (total_norm + 1e-6)),
+ *   1 when max_norm <= 0;  found_nonfinite = !isfinite(total_norm).  Finite: t += 1 and the bias corrections 1 - beta^t in
+ *   f64 -> coef.  Otherwise skipped += 1 (the skip rule of torch.amp.GradScaler.step). */
+int omnipq_adamw_finalize(int nchunks, const double *partials, const double *hyper, int ngroups, long long *counters,
+                          float *result, float *coef, void *stream);
+
+/* AdamW.step (train.py:563; torch/optim/adamw.py) over all chunks with g' = grad_scale * clip_coef * g:
+ *   p *= 1 - lr * wd;  m = beta1 * m + (1 - beta1) * g';  v = beta2 * v + (1 - beta2) * g'^2;
+ *   p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps).
+ * A no-op for every element when result[2] (found_nonfinite) is set. */
+int omnipq_adamw_update(int nrec, int nchunks, const void *records, const int *chunks, int chunk_elems,
+                        const float *coef, const float *result, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* OMNIPQ_OPTIM_H */

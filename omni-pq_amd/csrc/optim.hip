@@ -1,0 +1,306 @@
+// Fused gradient clipping + AdamW step (include/omnipq_optim.h; reference train.py:562-566 with the optimiser of
+// train.py:364-374): squared-norm partials -> finalise -> update, three launches over a device table of ALL parameter
+// tensors.  Every hyper-parameter, the step count and the bias corrections are read from device memory, so a captured
+// launch follows a learning-rate schedule on replay.  HBM-bound: the norm pass reads 4 bytes per parameter, the update
+// reads 16 and writes 12.
+#include <math.h>
+
+#include "common.h"
+#include "omnipq_optim.h"
+
+namespace omnipq {
+
+struct AdamRec {
+  float *param;
+  const float *grad;
+  float *exp_avg;
+  float *exp_avg_sq;
+  long long numel;
+  int group;
+  int reserved;
+};
+
+typedef float adam_f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kAdamThreads = 256;
+constexpr int kAdamQuantum = 4 * kAdamThreads;        // elements one pass of 16-byte vectors covers: chunk sizes are multiples
+
+__device__ __forceinline__ unsigned phase16(const void *p) { return (unsigned)(((uintptr_t)p >> 2) & 3u); }
+
+// sum over the workgroup in a fixed order (lane tree inside each wave, then the four wave totals left to right); valid in
+// thread 0
+__device__ __forceinline__ double block_sum_f64(double v) {
+  __shared__ double waves[kAdamThreads / 64];
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+  if (lane_id() == 0) waves[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 0; w < kAdamThreads / 64; ++w) s += waves[w];
+  }
+  return s;
+}
+
+__device__ __forceinline__ double sq_acc(double acc, float g, float gs) {
+  const double x = (double)(gs * g);
+  return __builtin_fma(x, x, acc);
+}
+
+__global__ __launch_bounds__(kAdamThreads) void adamw_grad_sqnorm_kernel(const AdamRec *__restrict__ recs,
+                                                                        const int *__restrict__ chunks, int chunk,
+                                                                        const double *__restrict__ hyper, int ngroups,
+                                                                        double *__restrict__ partials) {
+  const int *ck = chunks + 2 * (size_t)blockIdx.x;
+  const AdamRec r = recs[ck[0]];
+  const float gs = (float)hyper[8 * (size_t)ngroups + 1];
+  const long long base = (long long)ck[1] * chunk;
+  const long long left = r.numel - base;
+  const int len = left < (long long)chunk ? (int)left : chunk;
+  const int tid = (int)threadIdx.x;
+  double acc = 0.0;
+  if (len > 0) {
+    const float *g = r.grad + base;
+    int head = (int)((4u - phase16(g)) & 3u);
+    head = head < len ? head : len;
+    const int nvec = (len - head) >> 2;
+    const int tail0 = head + 4 * nvec;
+    if (tid < head) acc = sq_acc(acc, g[tid], gs);
+    if (tid >= 64 && tid < 64 + (len - tail0)) acc = sq_acc(acc, g[tail0 + tid - 64], gs);
+    const adam_f32x4 *gv = (const adam_f32x4 *)(g + head);
+    for (int j0 = 0; j0 < nvec; j0 += 4 * kAdamThreads) {
+      adam_f32x4 x[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int j = j0 + u * kAdamThreads + tid;
+        x[u] = j < nvec ? gv[j] : adam_f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        acc = sq_acc(acc, x[u][0], gs);
+        acc = sq_acc(acc, x[u][1], gs);
+        acc = sq_acc(acc, x[u][2], gs);
+        acc = sq_acc(acc, x[u][3], gs);
+      }
+    }
+  }
+  const double s = block_sum_f64(acc);
+  if (tid == 0) partials[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(kAdamThreads) void adamw_finalize_kernel(int nchunks, const double *__restrict__ partials,
+                                                                     const double *__restrict__ hyper, int ngroups,
+                                                                     long long *__restrict__ counters,
+                                                                     float *__restrict__ result, float *__restrict__ coef) {
+  double acc = 0.0;
+  for (int i = (int)threadIdx.x; i < nchunks; i += kAdamThreads) acc += partials[i];
+  const double sum = block_sum_f64(acc);
+  if (threadIdx.x != 0) return;
+  const double *last = hyper + 8 * (size_t)ngroups;
+  const float max_norm = (float)last[0];
+  const float gs = (float)last[1];
+  const float total_norm = (float)sqrt(sum);
+  const bool finite = isfinite(total_norm);
+  // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1, in the norm's f32
+  float clip = 1.f;
+  if (max_norm > 0.f && finite) clip = fminf(1.f, max_norm / (total_norm + 1e-6f));
+  result[0] = total_norm;
+  result[1] = clip;
+  result[2] = finite ? 0.f : 1.f;
+  result[3] = gs * clip;
+  if (!finite) {
+    counters[1] += 1;
+    return;
+  }
+  const long long t = counters[0] + 1;
+  counters[0] = t;
+  for (int g = 0; g < ngroups; ++g) {
+    const double *h = hyper + 8 * (size_t)g;
+    const double lr = h[0], beta1 = h[1], beta2 = h[2], eps = h[3], wd = h[4];
+    const double bc1 = 1.0 - pow(beta1, (double)t);
+    const double bc2 = 1.0 - pow(beta2, (double)t);
+    float *c = coef + 8 * (size_t)g;
+    c[0] = (float)(1.0 - lr * wd);
+    c[1] = (float)beta1;
+    c[2] = (float)(1.0 - beta1);
+    c[3] = (float)beta2;
+    c[4] = (float)(1.0 - beta2);
+    c[5] = (float)(lr / bc1);
+    c[6] = (float)(1.0 / sqrt(bc2));
+    c[7] = (float)eps;
+  }
+}
+
+struct AdamCoef {
+  float decay, beta1, omb1, beta2, omb2, step, rbc2s, eps, gc;
+};
+
+// one element of torch.optim.AdamW's update in f32 (fused multiply-adds written out: the library is built with
+// -ffp-contract=off)
+__device__ __forceinline__ void adam1(float &p, float g, float &m, float &v, const AdamCoef &c) {
+  const float gp = c.gc * g;
+  const float pd = p * c.decay;
+  m = __builtin_fmaf(c.beta1, m, c.omb1 * gp);
+  v = __builtin_fmaf(c.beta2, v, (c.omb2 * gp) * gp);
+  const float denom = __builtin_fmaf(sqrtf(v), c.rbc2s, c.eps);
+  p = __builtin_fmaf(-c.step, m / denom, pd);
+}
+
+__global__ __launch_bounds__(kAdamThreads) void adamw_update_kernel(const AdamRec *__restrict__ recs,
+                                                                   const int *__restrict__ chunks, int chunk,
+                                                                   const float *__restrict__ coef,
+                                                                   const float *__restrict__ result) {
+  if (result[2] != 0.f) return;                  // non-finite gradient norm: the whole step is skipped
+  const int *ck = chunks + 2 * (size_t)blockIdx.x;
+  const AdamRec r = recs[ck[0]];
+  const long long base = (long long)ck[1] * chunk;
+  const long long left = r.numel - base;
+  const int len = left < (long long)chunk ? (int)left : chunk;
+  if (len <= 0) return;
+  const float *cf = coef + 8 * (size_t)r.group;
+  const AdamCoef c = {cf[0], cf[1], cf[2], cf[3], cf[4], cf[5], cf[6], cf[7], result[3]};
+  float *p = r.param + base;
+  const float *g = r.grad + base;
+  float *m = r.exp_avg + base;
+  float *v = r.exp_avg_sq + base;
+  const int tid = (int)threadIdx.x;
+  const unsigned ph = phase16(p);
+  if (phase16(g) != ph || phase16(m) != ph || phase16(v) != ph) {
+    // the four tensors do not share a phase modulo 16 bytes: element by element (still one coalesced dword per lane)
+    for (int i0 = 0; i0 < len; i0 += 4 * kAdamThreads) {
+      float pp[4], gg[4], mm[4], vv[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = i0 + u * kAdamThreads + tid;
+        if (i < len) {
+          pp[u] = p[i];
+          gg[u] = g[i];
+          mm[u] = m[i];
+          vv[u] = v[i];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = i0 + u * kAdamThreads + tid;
+        if (i < len) {
+          adam1(pp[u], gg[u], mm[u], vv[u], c);
+          p[i] = pp[u];
+          m[i] = mm[u];
+          v[i] = vv[u];
+        }
+      }
+    }
+    return;
+  }
+  int head = (int)((4u - ph) & 3u);
+  head = head < len ? head : len;
+  const int nvec = (len - head) >> 2;
+  const int tail0 = head + 4 * nvec;
+  {
+    // the peeled head (lanes of wave 0) and tail (lanes of wave 1): at most three elements each
+    int i = -1;
+    if (tid < head) i = tid;
+    if (tid >= 64 && tid < 64 + (len - tail0)) i = tail0 + tid - 64;
+    if (i >= 0) {
+      float pp = p[i], mm = m[i], vv = v[i];
+      adam1(pp, g[i], mm, vv, c);
+      p[i] = pp;
+      m[i] = mm;
+      v[i] = vv;
+    }
+  }
+  adam_f32x4 *pv = (adam_f32x4 *)(p + head);
+  const adam_f32x4 *gv = (const adam_f32x4 *)(g + head);
+  adam_f32x4 *mv = (adam_f32x4 *)(m + head);
+  adam_f32x4 *vv4 = (adam_f32x4 *)(v + head);
+  for (int j0 = 0; j0 < nvec; j0 += 4 * kAdamThreads) {
+    adam_f32x4 P[4], G[4], M[4], V[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int j = j0 + u * kAdamThreads + tid;
+      if (j < nvec) {
+        P[u] = pv[j];
+        G[u] = gv[j];
+        M[u] = mv[j];
+        V[u] = vv4[j];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int j = j0 + u * kAdamThreads + tid;
+      if (j < nvec) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float pe = P[u][e], me = M[u][e], ve = V[u][e];
+          adam1(pe, G[u][e], me, ve, c);
+          P[u][e] = pe;
+          M[u][e] = me;
+          V[u][e] = ve;
+        }
+        pv[j] = P[u];
+        mv[j] = M[u];
+        vv4[j] = V[u];
+      }
+    }
+  }
+}
+
+static bool bad_chunk(int chunk_elems) { return chunk_elems <= 0 || (chunk_elems % kAdamQuantum) != 0; }
+
+}  // namespace omnipq
+
+using namespace omnipq;
+
+extern "C" int omnipq_adamw_check_table(int nrec, const void *records_host, int nchunks, const int *chunks_host,
+                                        int ngroups, int chunk_elems) {
+  static_assert(sizeof(AdamRec) == 48, "AdamRec layout is part of the C ABI");
+  if (nrec < 0 || nchunks < 0 || ngroups < 1 || bad_chunk(chunk_elems)) return OMNIPQ_EINVAL;
+  if ((nrec > 0 && !records_host) || (nchunks > 0 && !chunks_host)) return OMNIPQ_EINVAL;
+  const AdamRec *recs = (const AdamRec *)records_host;
+  for (int i = 0; i < nrec; ++i) {
+    const AdamRec &r = recs[i];
+    if (!r.param || !r.grad || !r.exp_avg || !r.exp_avg_sq || r.numel < 0) return OMNIPQ_EINVAL;
+    if (r.group < 0 || r.group >= ngroups) return OMNIPQ_EINVAL;
+    if ((((uintptr_t)r.param | (uintptr_t)r.grad | (uintptr_t)r.exp_avg | (uintptr_t)r.exp_avg_sq) & 3u) != 0) return OMNIPQ_EINVAL;
+  }
+  for (int i = 0; i < nchunks; ++i) {
+    const int rec = chunks_host[2 * (size_t)i], c = chunks_host[2 * (size_t)i + 1];
+    if (rec < 0 || rec >= nrec || c < 0) return OMNIPQ_EINVAL;
+    if ((long long)c * chunk_elems >= recs[rec].numel) return OMNIPQ_EINVAL;
+  }
+  return OMNIPQ_OK;
+}
+
+extern "C" int omnipq_adamw_grad_sqnorm(int nrec, int nchunks, const void *records, const int *chunks, int chunk_elems,
+                                        const double *hyper, int ngroups, double *partials, void *stream) {
+  if (nrec < 0 || nchunks < 0 || ngroups < 1 || bad_chunk(chunk_elems)) return OMNIPQ_EINVAL;
+  if (!hyper) return OMNIPQ_EINVAL;
+  if (nrec == 0 || nchunks == 0) return OMNIPQ_OK;
+  if (!records || !chunks || !partials) return OMNIPQ_EINVAL;
+  adamw_grad_sqnorm_kernel<<<nchunks, kAdamThreads, 0, (hipStream_t)stream>>>((const AdamRec *)records, chunks, chunk_elems,
+                                                                             hyper, ngroups, partials);
+  OMNIPQ_LAUNCH_CHECK();
+  return OMNIPQ_OK;
+}
+
+extern "C" int omnipq_adamw_finalize(int nchunks, const double *partials, const double *hyper, int ngroups,
+                                     long long *counters, float *result, float *coef, void *stream) {
+  if (nchunks < 0 || ngroups < 1) return OMNIPQ_EINVAL;
+  if (!hyper || !counters || !result || !coef || (nchunks > 0 && !partials)) return OMNIPQ_EINVAL;
+  adamw_finalize_kernel<<<1, kAdamThreads, 0, (hipStream_t)stream>>>(nchunks, partials, hyper, ngroups, counters, result, coef);
+  OMNIPQ_LAUNCH_CHECK();
+  return OMNIPQ_OK;
+}
+
+extern "C" int omnipq_adamw_update(int nrec, int nchunks, const void *records, const int *chunks, int chunk_elems,
+                                   const float *coef, const float *result, void *stream) {
+  if (nrec < 0 || nchunks < 0 || bad_chunk(chunk_elems)) return OMNIPQ_EINVAL;
+  if (!coef || !result) return OMNIPQ_EINVAL;
+  if (nrec == 0 || nchunks == 0) return OMNIPQ_OK;
+  if (!records || !chunks) return OMNIPQ_EINVAL;
+  adamw_update_kernel<<<nchunks, kAdamThreads, 0, (hipStream_t)stream>>>((const AdamRec *)records, chunks, chunk_elems, coef,
+                                                                        result);
+  OMNIPQ_LAUNCH_CHECK();
+  return OMNIPQ_OK;
+}

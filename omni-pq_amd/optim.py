@@ -1,0 +1,295 @@
+"""The three lines of the reference's training step that change the weights (train.py:562-566), as this project's own HIP:
+
+    grad_total_norm = clip_grad_norm_(model.parameters(), config.clip_norm)
+    optimizer.step()                      # AdamW over two parameter groups (train.py:364-374)
+
+`FusedAdamW` takes torch.optim.AdamW's arguments plus `max_norm` (the clip, fused in) and `grad_scale` (the inverse of a
+static fp16 loss scale).  One step is three launches over a device table of all parameter tensors (include/omnipq_optim.h:
+squared-norm partials, finalise, update) instead of several dozen multi-tensor launches driven from the host.  Learning
+rates, betas, eps, weight decay, max_norm, grad_scale, the step count and the bias corrections all live in device memory:
+no launch takes one as an argument, so the launches can be captured into `train_step.CapturedStep`'s graph and a replay
+follows whatever an LR scheduler wrote into `param_groups` (`sync_hyperparameters()` stages the rows).
+
+What differs from torch.optim.AdamW, all of it stated rather than hidden:
+  * ONE step counter for the whole optimiser (device memory).  `state[p]['step']` is materialised from it by
+    `state_dict()`; a loaded state whose parameters disagree on `step` is refused.
+  * a step whose gradient norm is not finite changes nothing and counts as `skipped` (torch.amp.GradScaler's rule);
+  * `.grad` is read-only: the clipped gradient is never written back (nothing in the reference reads it afterwards);
+  * `exp_avg` / `exp_avg_sq` of all parameters are two flat f32 buffers, `state[p]` holds views into them.
+`state_dict()` / `load_state_dict()` are interchangeable with torch.optim.AdamW's in both directions.
+"""
+import ctypes
+import os
+import sys
+
+import numpy as np
+import torch
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+for _p in (_HERE, os.path.join(_HERE, "pointnet2")):
+    if _p not in sys.path:
+        sys.path.append(_p)
+
+RECORD = np.dtype([("param", "<u8"), ("grad", "<u8"), ("exp_avg", "<u8"), ("exp_avg_sq", "<u8"), ("numel", "<i8"),
+                   ("group", "<i4"), ("reserved", "<i4")])          # include/omnipq_optim.h: 48 bytes
+ROW = 8                  # doubles per hyper-parameter row, floats per coefficient row
+CHUNK = 4096             # elements per workgroup (a multiple of 1024); tools/bench_optimizer.py --chunks measures others
+_STAGES = 4              # pinned staging rows in rotation: a row is rewritten only after its own copy has completed
+
+
+def _ext():
+    import pointnet2_utils
+    return pointnet2_utils._load_ext()
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+
+
+class _Table:
+    """The device tables of one (parameter, gradient) address set."""
+    __slots__ = ("key", "shape_key", "records", "chunks", "partials", "nrec", "nchunks")
+
+
+class FusedAdamW(torch.optim.Optimizer):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
+                 max_norm=0.0, grad_scale=1.0, chunk_elems=CHUNK):
+        if amsgrad:
+            raise NotImplementedError("FusedAdamW: amsgrad is not implemented (the reference does not use it)")
+        if maximize:
+            raise NotImplementedError("FusedAdamW: maximize is not implemented (the reference does not use it)")
+        if chunk_elems <= 0 or chunk_elems % 1024:
+            raise ValueError("FusedAdamW: chunk_elems must be a positive multiple of 1024")
+        # torch.optim.AdamW validates the values and knows which keys a param_group of THIS torch carries: its defaults are
+        # taken over as they are, so that a state_dict of either optimiser has the other's param_groups keys
+        probe = torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        if torch.is_tensor(lr) or any(torch.is_tensor(b) for b in betas):
+            raise ValueError("FusedAdamW: lr and betas are Python numbers (they are staged to the device by sync_hyperparameters)")
+        super().__init__(params, dict(probe.defaults))
+        self.max_norm, self.grad_scale = float(max_norm), float(grad_scale)
+        self.chunk_elems = int(chunk_elems)
+        plist = [p for g in self.param_groups for p in g["params"]]
+        if not plist:
+            raise ValueError("FusedAdamW: no parameters")
+        dev = plist[0].device
+        for p in plist:
+            if p.dtype != torch.float32 or p.device != dev or not p.is_contiguous():
+                raise ValueError("FusedAdamW: parameters must be contiguous float32 tensors on one device")
+        self.device = dev
+        # the moments: two flat buffers.  A parameter's segment starts at the parameter's own phase modulo 16 bytes, so that
+        # p, m and v of a chunk move as 16-byte vectors together even where p is a view at an odd offset of a joint matrix
+        self._offset, total = {}, 0
+        for p in plist:
+            total += ((p.data_ptr() >> 2) - total) % 4
+            self._offset[p] = total
+            total += p.numel()
+        self.exp_avg = torch.zeros(total + 4, dtype=torch.float32, device=dev)
+        self.exp_avg_sq = torch.zeros(total + 4, dtype=torch.float32, device=dev)
+        ngroups = len(self.param_groups)
+        self.counters = torch.zeros(2, dtype=torch.int64, device=dev)             # t, skipped
+        self.result = torch.zeros(4, dtype=torch.float32, device=dev)             # total_norm, clip_coef, found_nonfinite, g coefficient
+        self.grad_total_norm = self.result[0]                                      # what step() returns: rewritten by every step
+        self._coef = torch.zeros(ngroups * ROW, dtype=torch.float32, device=dev)
+        self._hyper = torch.zeros((ngroups + 1, ROW), dtype=torch.float64, device=dev)
+        self._stages = [torch.zeros((ngroups + 1, ROW), dtype=torch.float64, pin_memory=dev.type == "cuda")
+                        for _ in range(_STAGES if dev.type == "cuda" else 1)]
+        self._stage_events = [None] * len(self._stages)
+        self._stage_next = 0
+        self.staging = self._stages[0]          # the rows staged last
+        self._sent = None
+        self._table_hit = None
+        self.table_builds = 0
+        self.sync_hyperparameters()
+
+    def add_param_group(self, param_group):
+        if hasattr(self, "_offset"):
+            raise NotImplementedError("FusedAdamW: parameter groups are fixed at construction (the moments are two flat "
+                                      "buffers laid out over them)")
+        super().add_param_group(param_group)
+
+    # ---- moments and state ---------------------------------------------------------------------------------------------------
+    def _views(self, p):
+        o = self._offset[p]
+        return self.exp_avg[o:o + p.numel()].view_as(p), self.exp_avg_sq[o:o + p.numel()].view_as(p)
+
+    def _ensure_state(self, p):
+        st = self.state[p]
+        if "exp_avg" not in st:
+            m, v = self._views(p)
+            st["step"] = torch.tensor(0.0, dtype=torch.get_default_dtype())
+            st["exp_avg"], st["exp_avg_sq"] = m, v
+        return st
+
+    @property
+    def t(self):
+        """optimiser steps taken (reads the device)"""
+        return int(self.counters[0])
+
+    @property
+    def skipped(self):
+        """steps skipped because the gradient norm was not finite (reads the device)"""
+        return int(self.counters[1])
+
+    def state_dict(self):
+        t = float(self.t)                          # the one host read of the device counter
+        for st in self.state.values():
+            if "step" in st:
+                st["step"] = torch.tensor(t, dtype=torch.get_default_dtype())
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        steps = {float(s["step"]) for s in state_dict["state"].values() if "step" in s}
+        if len(steps) > 1:
+            raise ValueError(f"FusedAdamW.load_state_dict: the parameters disagree on `step` ({sorted(steps)}); this optimiser "
+                             "keeps one step count for all of them")
+        for s in state_dict["state"].values():
+            if s.get("max_exp_avg_sq") is not None:
+                raise NotImplementedError("FusedAdamW.load_state_dict: the state was written with amsgrad=True")
+        super().load_state_dict(state_dict)
+        for g in self.param_groups:
+            if g.get("amsgrad") or g.get("maximize"):
+                raise NotImplementedError("FusedAdamW.load_state_dict: amsgrad / maximize are not implemented")
+        with torch.no_grad():
+            self.exp_avg.zero_()
+            self.exp_avg_sq.zero_()
+            for g in self.param_groups:
+                for p in g["params"]:
+                    st = self.state.get(p)
+                    if not st:
+                        continue
+                    m, v = self._views(p)
+                    m.copy_(st["exp_avg"])
+                    v.copy_(st["exp_avg_sq"])
+                    st["exp_avg"], st["exp_avg_sq"] = m, v
+            self.counters[0] = int(steps.pop()) if steps else 0
+        self._sent = None
+        self.sync_hyperparameters()
+
+    # ---- hyper-parameters ----------------------------------------------------------------------------------------------------
+    def _rows(self):
+        rows = np.zeros((len(self.param_groups) + 1, ROW), dtype=np.float64)
+        for i, g in enumerate(self.param_groups):
+            rows[i, :5] = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
+        rows[-1, :2] = (self.max_norm, self.grad_scale)
+        return rows
+
+    def sync_hyperparameters(self):
+        """Stage the rows {lr, beta1, beta2, eps, weight_decay} of every param_group and {max_norm, grad_scale} to the device
+        when a host value has changed since the last call: pinned staging tensor, non-blocking copy on the current stream, no
+        host read of the device.  An LR scheduler keeps working on `param_groups`; step() calls this, and so does
+        CapturedStep.step() in front of its replay.  -> True when rows were sent."""
+        rows = self._rows()
+        if self._sent is not None and np.array_equal(rows, self._sent):
+            return False
+        i = self._stage_next
+        self._stage_next = (i + 1) % len(self._stages)
+        if self._stage_events[i] is not None:
+            self._stage_events[i].synchronize()          # the copy that last read this staging tensor (_STAGES syncs ago)
+        stage = self._stages[i]
+        stage.copy_(torch.from_numpy(rows))
+        self._hyper.copy_(stage, non_blocking=True)
+        if self.device.type == "cuda":
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+            self._stage_events[i] = ev
+        self.staging = stage
+        self._sent = rows
+        return True
+
+    # ---- the device table ----------------------------------------------------------------------------------------------------
+    def _active(self):
+        return [(gi, p) for gi, g in enumerate(self.param_groups) for p in g["params"] if p.grad is not None]
+
+    def _host_tables(self, active):
+        ext = _ext()
+        rec = np.zeros(len(active), dtype=RECORD)
+        chunks = []
+        for i, (gi, p) in enumerate(active):
+            g = p.grad
+            if g.dtype != torch.float32 or not g.is_contiguous() or g.device != p.device or g.shape != p.shape \
+                    or not p.is_contiguous():
+                raise RuntimeError("FusedAdamW: parameters and gradients must be contiguous float32 tensors of equal shapes")
+            m, v = self._ensure_state(p)["exp_avg"], self.state[p]["exp_avg_sq"]
+            rec[i] = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), gi, 0)
+            chunks += [(i, c) for c in range((p.numel() + self.chunk_elems - 1) // self.chunk_elems)]
+        chunks = np.asarray(chunks, dtype=np.int32).reshape(-1, 2)
+        rc = ext._lib0.omnipq_adamw_check_table(len(active), rec.ctypes.data_as(ctypes.c_void_p), int(chunks.shape[0]),
+                                                chunks.ctypes.data_as(ctypes.c_void_p), len(self.param_groups), self.chunk_elems)
+        if rc != 0:
+            raise RuntimeError(f"omnipq_adamw_check_table failed: {ext._lib0.omnipq_error_string(rc).decode()} ({rc})")
+        return rec, chunks
+
+    def _table(self, capturing=False):
+        """The device table, cached and keyed on the (parameter, gradient) addresses (like ema._table).  capturing: nothing may
+        be uploaded now -- the launches are recorded against the table buffers of the last eager step, which must cover the same
+        parameters, and `retarget()` writes the addresses of the captured gradients into them once the capture has ended."""
+        active = self._active()
+        key = tuple((p.data_ptr(), p.grad.data_ptr(), p.numel()) for _, p in active)
+        hit = self._table_hit
+        if hit is not None and hit.key == key:
+            return hit
+        shape_key = tuple((p.data_ptr(), p.numel(), gi) for gi, p in active)
+        if hit is not None and hit.shape_key == shape_key:
+            if capturing:
+                hit.key = None                       # stale until retarget()
+                return hit
+            rec, _ = self._host_tables(active)
+            hit.records.copy_(torch.from_numpy(rec.view(np.uint8)))      # same buffers: captured launches keep pointing at them
+            hit.key = key
+            self.table_builds += 1
+            return hit
+        if capturing:
+            raise RuntimeError("FusedAdamW: the parameters with gradients differ from those of the step before the capture")
+        rec, chunks = self._host_tables(active)
+        hit = _Table()
+        hit.key, hit.shape_key = key, shape_key
+        hit.nrec, hit.nchunks = len(active), int(chunks.shape[0])
+        hit.records = torch.from_numpy(rec.view(np.uint8).copy()).to(self.device)
+        hit.chunks = torch.from_numpy(chunks.copy()).to(self.device)
+        hit.partials = torch.zeros(max(hit.nchunks, 1), dtype=torch.float64, device=self.device)
+        self._table_hit = hit
+        self.table_builds += 1
+        return hit
+
+    def retarget(self):
+        """After a capture: point the table the captured launches read at the gradients the capture allocated."""
+        self._table(capturing=False)
+
+    # ---- the step ------------------------------------------------------------------------------------------------------------
+    def launch(self):
+        """The three launches on the current stream, hyper-parameters as they are on the device (no staging, no host read):
+        what CapturedStep records into its graph.  -> the device tensor grad_total_norm."""
+        if self.device.type != "cuda":
+            raise RuntimeError("CPU not supported")      # like the native ops: no CPU path in the product
+        ext = _ext()
+        tab = self._table(torch.cuda.is_current_stream_capturing())
+        if tab.nrec == 0:
+            return self.grad_total_norm
+        lib, ng = ext._lib0, len(self.param_groups)
+        ext._run(lib.omnipq_adamw_grad_sqnorm, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.chunks),
+                 self.chunk_elems, _ptr(self._hyper), ng, _ptr(tab.partials))
+        ext._run(lib.omnipq_adamw_finalize, self.result, tab.nchunks, _ptr(tab.partials), _ptr(self._hyper), ng,
+                 _ptr(self.counters), _ptr(self.result), _ptr(self._coef))
+        ext._run(lib.omnipq_adamw_update, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.chunks),
+                 self.chunk_elems, _ptr(self._coef), _ptr(self.result))
+        return self.grad_total_norm
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        """clip_grad_norm_(max_norm) + AdamW.step() in three launches.  -> grad_total_norm, a 0-dim DEVICE tensor (the norm of
+        grad_scale * gradients before clipping; rewritten by the next step).  Parameters whose .grad is None are left out."""
+        if closure is not None:
+            raise NotImplementedError("FusedAdamW.step: closures are not supported")
+        if self.device.type != "cuda":
+            raise RuntimeError("CPU not supported")
+        self.sync_hyperparameters()
+        return self.launch()
+
+    # ---- save / restore (CapturedStep's warm-up and capture runs must leave no trace) ---------------------------------------
+    def snapshot(self):
+        return [t.detach().clone() for t in (self.exp_avg, self.exp_avg_sq, self.counters, self.result)]
+
+    def restore(self, saved):
+        with torch.no_grad():
+            for t, s in zip((self.exp_avg, self.exp_avg_sq, self.counters, self.result), saved):
+                t.copy_(s)

@@ -13,7 +13,8 @@ Where it goes in the reference's driver (train.py:456-576): the three lines
 become `loss = stepper.step(batch, labels, next_inputs=next_batch)`; `optimizer.step()` (train.py:560-563) stays where
 it is and finds the gradients in `.grad` of the bare model's parameters, averaged over the ranks.  INTEGRATION.md shows
 the whole change.  The model is NOT wrapped in DistributedDataParallel: DDP reduces from per-parameter autograd hooks,
-which a captured step with deferred weight gradients never fires (`deferred_wgrads` refuses DDP parameters).
+which a captured step with deferred weight gradients never fires (`deferred_wgrads` refuses DDP parameters).  With `CapturedStep(..., optimizer=optim.FusedAdamW(...))` the clip and the AdamW step of train.py:562-563 run inside
+the captured step as well (three launches at its end, hyper-parameters in device memory) and only `scheduler.step()` stays.
 
 Launched kernel by kernel (`graph=False`, or under DDP) the same step is host-bound (about 2.3x slower at batch 8 x
 40 000 points on MI355X); the capture is what makes the 650 dependent launches of 3-150 us run back to back.
@@ -78,12 +79,37 @@ class CapturedStep:
                      the mean-teacher step (profiles/fps_resume_ab.txt: 12.35 ms against 13.15 at 0.70 x -- the value derived
                      from the chain's proportions, (6.2 / 2) / 4.44 -- and 13.86 at 0.85 x; the plain step preferred 0.70 x by
                      0.06 ms).  Neither beat lookahead=1 on this runtime (10.97 ms; plain step 7.77 vs 7.81): opt-in.
+    optimizer        None (default): the step ends with the gradients in `.grad`, the caller clips and steps.  An
+                     optim.FusedAdamW over net's parameters: gradient clipping + AdamW (train.py:562-563) become the last
+                     three launches of the step body, on the main stream behind the deferred weight-gradient flush and the
+                     bucket all-reduce (no fork, no join of their own), captured with it.  Its hyper-parameters live in
+                     device memory: step() stages what an LR scheduler wrote into `param_groups`
+                     (optimizer.sync_hyperparameters()) in front of the replay, so scheduler.step() stays where it is and
+                     update_teacher() is still called after step().  loss_scale != 1 sets optimizer.grad_scale =
+                     1 / loss_scale; a step whose gradient norm is not finite leaves the weights alone (optimizer.skipped).
+                     Building the stepper changes neither parameters nor optimiser state.  `stepper.grad_total_norm` is
+                     the device tensor clip_grad_norm_ would have returned.
+    step_freq        1.  Gradient accumulation (the reference's step_freq > 1) is refused: every step starts from
+                     empty gradients and an in-graph optimiser applies every step.
     """
 
     def __init__(self, net, criterion, example_inputs, example_labels=None, *, model=None, amp_dtype=torch.bfloat16,
                  loss_scale=1.0, graph=True, prefetch="forward", fps_footprint=None, teacher=None, teacher_example=None,
                  ema=None, buckets=None, defer=True, warmup=3, distributed=False, before_capture=None,
-                 teacher_to_criterion=False, lookahead=1, head_rounds=None):
+                 teacher_to_criterion=False, lookahead=1, head_rounds=None, optimizer=None, step_freq=1):
+        if step_freq != 1:
+            raise ValueError("CapturedStep: gradient accumulation (step_freq > 1) is not supported -- every step starts from "
+                             "empty gradients" + (", and the in-graph optimizer applies every step" if optimizer is not None
+                                                  else ""))
+        if optimizer is not None:
+            import optim
+            if not isinstance(optimizer, optim.FusedAdamW):
+                raise TypeError("CapturedStep(optimizer=...): an optim.FusedAdamW or None -- any other optimizer steps from the "
+                                "host, after step()")
+            if float(loss_scale) != 1.0:
+                optimizer.grad_scale = 1.0 / float(loss_scale)
+        self.optimizer = optimizer
+        self.grad_total_norm = optimizer.grad_total_norm if optimizer is not None else None
         if lookahead not in (1, 2):
             raise ValueError("CapturedStep: lookahead is 1 or 2")
         if lookahead == 2 and prefetch != "forward":
@@ -208,6 +234,11 @@ class CapturedStep:
             if teacher is not None:
                 teacher.prefetch({"point_clouds": nxt_t}, trusted=trusted)
         self._backward(loss)
+        if self.optimizer is not None:
+            # clip + AdamW: three launches on this stream, behind the weight-gradient flush and the bucket all-reduce
+            if not self._capturing:
+                self.optimizer.sync_hyperparameters()
+            self.optimizer.launch()
         if not self._capturing:
             for m in heads:
                 m.hand_over_head()                   # (this stream waits for the head; the host does not)
@@ -239,6 +270,12 @@ class CapturedStep:
         # the warm-up steps run the model in train mode on the EXAMPLE batch: what they do to the BatchNorm running
         # statistics / step counters of both networks is undone after the capture
         keep = [(b, b.detach().clone()) for m in (net, teacher) if m is not None for b in m.buffers()]
+        opt_saved = None
+        if self.optimizer is not None:
+            # ... and so is what the in-graph optimizer does to the parameters, its moments and its counters
+            keep += [(p, p.detach().clone()) for g in self.optimizer.param_groups for p in g["params"]]
+            opt_saved = self.optimizer.snapshot()
+            self.optimizer.sync_hyperparameters()
         try:
             self.nxt.copy_(self.cur)
             if teacher is not None:
@@ -279,6 +316,9 @@ class CapturedStep:
             # caller's optimizer.zero_grad() (set_to_none=True is torch's default) detaches them from the parameters, so
             # every replay hands them back.
             self._grads = [(p, p.grad) for p in net.parameters() if p.grad is not None]
+            if self.optimizer is not None:
+                self.optimizer.retarget()            # the table the captured launches read: the capture's own gradient tensors
+                self.optimizer.restore(opt_saved)
             self._forget_plans()
             with torch.no_grad():
                 for b, saved in keep:
@@ -367,6 +407,9 @@ class CapturedStep:
                 self._promised2 = (t2, t2._version)
             else:
                 self._promised2 = None
+        if self.optimizer is not None:
+            self.optimizer.sync_hyperparameters()    # what a scheduler wrote into param_groups since the last step
+            self.optimizer._opt_called = True        # (torch's schedulers warn when they never see optimizer.step())
         self.graph.replay()
         self.replays += 1
         for p, g in self._grads:
