@@ -27,12 +27,25 @@
  *   coef      ngroups rows of 8 floats, written by the finalise launch for the update launch:
  *             { 1 - lr * wd, beta1, 1 - beta1, beta2, 1 - beta2, lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t), eps }.
  *
+ * Gradient accumulation (the reference's step_freq: train.py:493-494 zeroes the gradients on the first of k micro-batches only,
+ * train.py:562-576 clips, steps and averages on the last; the loss is not divided, so the gradients are SUMMED) is the
+ * omnipq_adamw_accum_* family: the same three launches on EVERY micro-batch, so that one captured graph serves all of them.
+ *   acc       a flat f32 accumulator laid out exactly like the flat exp_avg buffer the records point into: the segment of a
+ *             record is acc_base + (rec.exp_avg - exp_avg_base), so p, m, v and acc of a chunk share one phase modulo 16 bytes.
+ *             The two bases are fixed addresses passed as arguments; the record layout is unchanged.
+ *   accum     int64[2] = { micro, apply }: micro-batches already summed, in [0, accum_steps), and whether the last finalise
+ *             launch was the applying one (0 or 1).  Written by the finalise launch only, with ordinary stores of thread 0.
+ *   accum_steps (k) is a kernel argument: it is fixed for the life of a captured launch.
+ * On an applying call result[0..3] mean what they mean above; on any other call only result[0] (the norm of grad_scale times
+ * the running sum) is written.  The sum is overwritten, not added to, when micro == 0: no zeroing launch, and a non-finite value
+ * left behind by a skipped step cannot leak into the next one.
+ *
  * `.grad` is READ-ONLY here: the clipped (and un-scaled) gradient g' = grad_scale * clip_coef * g exists in registers
  * only and is never written back.  Nothing in the reference reads the gradients after train.py:564; a caller that wants the
  * clipped gradients in memory must keep torch.nn.utils.clip_grad_norm_.
  *
- * Every entry point validates its host arguments (null tables, negative counts, ngroups < 1, a chunk size that is not a
- * positive multiple of 1024) and returns OMNIPQ_EINVAL before anything is launched.  What a DEVICE table holds cannot be seen
+ * Every entry point validates its host arguments (null tables or bases, negative counts, ngroups < 1, accum_steps < 1, a chunk
+ * size that is not a positive multiple of 1024) and returns OMNIPQ_EINVAL before anything is launched.  What a DEVICE table holds cannot be seen
  * from the host: omnipq_adamw_check_table validates the host copy a binding is about to upload.
  */
 #ifndef OMNIPQ_OPTIM_H
@@ -65,6 +78,25 @@ int omnipq_adamw_finalize(int nchunks, const double *partials, const double *hyp
  * A no-op for every element when result[2] (found_nonfinite) is set. */
 int omnipq_adamw_update(int nrec, int nchunks, const void *records, const int *chunks, int chunk_elems,
                         const float *coef, const float *result, void *stream);
+
+/* Accumulate + squared norm: a = (micro == 0) ? g : acc + g (one f32 add), acc = a, and
+ * partials[c] = sum over chunk c of (grad_scale * a)^2 in f64, in the order of omnipq_adamw_grad_sqnorm on a gradient at the
+ * same address -- the same bits as that call on the summed gradients.  The gradient is read once; no atomics. */
+int omnipq_adamw_accum_sqnorm(int nrec, int nchunks, const void *records, const int *chunks, int chunk_elems,
+                              const double *hyper, int ngroups, const float *exp_avg_base, float *acc_base,
+                              const long long *accum, double *partials, void *stream);
+
+/* Finalise of one micro-batch, one workgroup.  result[0] = grad_scale * |running sum| always.  micro != accum_steps - 1:
+ * micro += 1, apply = 0, nothing else is touched.  micro == accum_steps - 1: everything omnipq_adamw_finalize does (clip
+ * coefficient; non-finite: skipped += 1; else t += 1 and the coef rows), then micro = 0 and apply = 1. */
+int omnipq_adamw_accum_finalize(int nchunks, const double *partials, const double *hyper, int ngroups, int accum_steps,
+                                long long *counters, long long *accum, float *result, float *coef, void *stream);
+
+/* omnipq_adamw_update with the gradient read from the record's accumulator segment.  A no-op for every element when apply is 0
+ * or result[2] (found_nonfinite) is set. */
+int omnipq_adamw_accum_update(int nrec, int nchunks, const void *records, const int *chunks, int chunk_elems,
+                              const float *exp_avg_base, const float *acc_base, const long long *accum, const float *coef,
+                              const float *result, void *stream);
 
 #ifdef __cplusplus
 }

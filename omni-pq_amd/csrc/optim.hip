@@ -3,6 +3,12 @@
 // tensors.  Every hyper-parameter, the step count and the bias corrections are read from device memory, so a captured
 // launch follows a learning-rate schedule on replay.  HBM-bound: the norm pass reads 4 bytes per parameter, the update
 // reads 16 and writes 12.
+//
+// Gradient accumulation (the reference's step_freq, train.py:493-494 and :562-576) is the same three launches with one more
+// flat buffer: the norm pass adds the micro-batch's gradient into an f32 accumulator laid out like exp_avg (reads 8, writes 4
+// bytes per parameter; 4 and 4 on the first micro-batch, which overwrites), the finalise launch counts micro-batches in a device
+// word and marks the k-th call as the applying one, and the update reads the accumulator where it read the gradient.  The
+// templates below are the ONE body behind both families of entry points.
 #include <math.h>
 
 #include "common.h"
@@ -48,33 +54,84 @@ __device__ __forceinline__ double sq_acc(double acc, float g, float gs) {
   return __builtin_fma(x, x, acc);
 }
 
-__global__ __launch_bounds__(kAdamThreads) void adamw_grad_sqnorm_kernel(const AdamRec *__restrict__ recs,
-                                                                        const int *__restrict__ chunks, int chunk,
-                                                                        const double *__restrict__ hyper, int ngroups,
-                                                                        double *__restrict__ partials) {
-  const int *ck = chunks + 2 * (size_t)blockIdx.x;
-  const AdamRec r = recs[ck[0]];
-  const float gs = (float)hyper[8 * (size_t)ngroups + 1];
-  const long long base = (long long)ck[1] * chunk;
-  const long long left = r.numel - base;
-  const int len = left < (long long)chunk ? (int)left : chunk;
+// an f32x4 at any 4-byte-aligned address (the accumulator segment of a chunk whose gradient sits at another phase)
+struct __attribute__((packed, aligned(4))) adam_f32x4_any {
+  float e[4];
+};
+
+// Squared-norm partial of one chunk, in ONE fixed order: the head (up to 3 elements in front of the gradient's first 16-byte
+// boundary, lanes of wave 0), the tail (lanes of wave 1), then 16-byte vectors, four per thread and pass.  kAccum: the value
+// that is squared is the running sum a = first ? g : sum + g, which is stored back; `sum` is the chunk's accumulator
+// segment.  It shares the PARAMETER's phase, not necessarily the gradient's: where the two differ, the same elements go to the
+// same threads and the accumulator moves through 4-byte-aligned accesses.
+template <bool kAccum>
+__device__ __forceinline__ void adamw_sqnorm_chunk(const float *__restrict__ g, float *__restrict__ sum, bool first, int len,
+                                                   float gs, double *__restrict__ partial) {
   const int tid = (int)threadIdx.x;
   double acc = 0.0;
   if (len > 0) {
-    const float *g = r.grad + base;
     int head = (int)((4u - phase16(g)) & 3u);
     head = head < len ? head : len;
     const int nvec = (len - head) >> 2;
     const int tail0 = head + 4 * nvec;
-    if (tid < head) acc = sq_acc(acc, g[tid], gs);
-    if (tid >= 64 && tid < 64 + (len - tail0)) acc = sq_acc(acc, g[tail0 + tid - 64], gs);
+    {
+      int i = -1;
+      if (tid < head) i = tid;
+      if (tid >= 64 && tid < 64 + (len - tail0)) i = tail0 + tid - 64;
+      if (i >= 0) {
+        float a = g[i];
+        if (kAccum) {
+          if (!first) a = sum[i] + a;
+          sum[i] = a;
+        }
+        acc = sq_acc(acc, a, gs);
+      }
+    }
     const adam_f32x4 *gv = (const adam_f32x4 *)(g + head);
+    const bool together = kAccum && phase16(sum) == phase16(g);
     for (int j0 = 0; j0 < nvec; j0 += 4 * kAdamThreads) {
       adam_f32x4 x[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int j = j0 + u * kAdamThreads + tid;
         x[u] = j < nvec ? gv[j] : adam_f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      if (kAccum) {
+        if (together) {
+          adam_f32x4 *sv = (adam_f32x4 *)(sum + head);
+          if (!first) {
+            adam_f32x4 s[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              const int j = j0 + u * kAdamThreads + tid;
+              s[u] = j < nvec ? sv[j] : adam_f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) x[u] = s[u] + x[u];
+          }
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const int j = j0 + u * kAdamThreads + tid;
+            if (j < nvec) sv[j] = x[u];
+          }
+        } else {
+          adam_f32x4_any *sv = (adam_f32x4_any *)(sum + head);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const int j = j0 + u * kAdamThreads + tid;
+            if (j < nvec) {
+              adam_f32x4_any s;
+              if (!first) {
+                s = sv[j];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) x[u][e] = s.e[e] + x[u][e];
+              }
+#pragma unroll
+              for (int e = 0; e < 4; ++e) s.e[e] = x[u][e];
+              sv[j] = s;
+            }
+          }
+        }
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -86,12 +143,37 @@ __global__ __launch_bounds__(kAdamThreads) void adamw_grad_sqnorm_kernel(const A
     }
   }
   const double s = block_sum_f64(acc);
-  if (tid == 0) partials[blockIdx.x] = s;
+  if (tid == 0) *partial = s;
 }
 
+// accum (kAccum): int64[2] = { micro-batches already summed, apply mark of the last finalise }
+template <bool kAccum>
+__global__ __launch_bounds__(kAdamThreads) void adamw_grad_sqnorm_kernel(const AdamRec *__restrict__ recs,
+                                                                        const int *__restrict__ chunks, int chunk,
+                                                                        const double *__restrict__ hyper, int ngroups,
+                                                                        const float *exp_avg_base, float *sum_base,
+                                                                        const long long *__restrict__ accum,
+                                                                        double *__restrict__ partials) {
+  const int *ck = chunks + 2 * (size_t)blockIdx.x;
+  const AdamRec r = recs[ck[0]];
+  const float gs = (float)hyper[8 * (size_t)ngroups + 1];
+  const long long base = (long long)ck[1] * chunk;
+  const long long left = r.numel - base;
+  const int len = left < (long long)chunk ? (int)left : chunk;
+  float *sum = nullptr;
+  bool first = true;
+  if (kAccum) {
+    sum = sum_base + (r.exp_avg - exp_avg_base) + base;
+    first = accum[0] == 0;
+  }
+  adamw_sqnorm_chunk<kAccum>(r.grad + base, sum, first, len, gs, partials + blockIdx.x);
+}
+
+template <bool kAccum>
 __global__ __launch_bounds__(kAdamThreads) void adamw_finalize_kernel(int nchunks, const double *__restrict__ partials,
                                                                      const double *__restrict__ hyper, int ngroups,
-                                                                     long long *__restrict__ counters,
+                                                                     int accum_steps, long long *__restrict__ counters,
+                                                                     long long *__restrict__ accum,
                                                                      float *__restrict__ result, float *__restrict__ coef) {
   double acc = 0.0;
   for (int i = (int)threadIdx.x; i < nchunks; i += kAdamThreads) acc += partials[i];
@@ -102,6 +184,18 @@ __global__ __launch_bounds__(kAdamThreads) void adamw_finalize_kernel(int nchunk
   const float gs = (float)last[1];
   const float total_norm = (float)sqrt(sum);
   const bool finite = isfinite(total_norm);
+  if (kAccum) {
+    // a micro-batch that is not the k-th only counts: the norm of the running sum is reported, nothing else is touched
+    const long long micro = accum[0];
+    if (micro >= 0 && micro < (long long)accum_steps - 1) {
+      result[0] = total_norm;
+      accum[0] = micro + 1;
+      accum[1] = 0;
+      return;
+    }
+    accum[0] = 0;
+    accum[1] = 1;
+  }
   // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1, in the norm's f32
   float clip = 1.f;
   if (max_norm > 0.f && finite) clip = fminf(1.f, max_norm / (total_norm + 1e-6f));
@@ -147,10 +241,16 @@ __device__ __forceinline__ void adam1(float &p, float g, float &m, float &v, con
   p = __builtin_fmaf(-c.step, m / denom, pd);
 }
 
+// kAccum: the gradient is the chunk's segment of the accumulator (same offsets as exp_avg: always the vector path), and a
+// call that finalise did not mark as the applying one changes nothing
+template <bool kAccum>
 __global__ __launch_bounds__(kAdamThreads) void adamw_update_kernel(const AdamRec *__restrict__ recs,
                                                                    const int *__restrict__ chunks, int chunk,
+                                                                   const float *exp_avg_base, const float *sum_base,
+                                                                   const long long *__restrict__ accum,
                                                                    const float *__restrict__ coef,
                                                                    const float *__restrict__ result) {
+  if (kAccum && accum[1] == 0) return;           // not the k-th micro-batch
   if (result[2] != 0.f) return;                  // non-finite gradient norm: the whole step is skipped
   const int *ck = chunks + 2 * (size_t)blockIdx.x;
   const AdamRec r = recs[ck[0]];
@@ -161,7 +261,7 @@ __global__ __launch_bounds__(kAdamThreads) void adamw_update_kernel(const AdamRe
   const float *cf = coef + 8 * (size_t)r.group;
   const AdamCoef c = {cf[0], cf[1], cf[2], cf[3], cf[4], cf[5], cf[6], cf[7], result[3]};
   float *p = r.param + base;
-  const float *g = r.grad + base;
+  const float *g = (kAccum ? sum_base + (r.exp_avg - exp_avg_base) : r.grad) + base;
   float *m = r.exp_avg + base;
   float *v = r.exp_avg_sq + base;
   const int tid = (int)threadIdx.x;
@@ -278,8 +378,8 @@ extern "C" int omnipq_adamw_grad_sqnorm(int nrec, int nchunks, const void *recor
   if (!hyper) return OMNIPQ_EINVAL;
   if (nrec == 0 || nchunks == 0) return OMNIPQ_OK;
   if (!records || !chunks || !partials) return OMNIPQ_EINVAL;
-  adamw_grad_sqnorm_kernel<<<nchunks, kAdamThreads, 0, (hipStream_t)stream>>>((const AdamRec *)records, chunks, chunk_elems,
-                                                                             hyper, ngroups, partials);
+  adamw_grad_sqnorm_kernel<false><<<nchunks, kAdamThreads, 0, (hipStream_t)stream>>>(
+      (const AdamRec *)records, chunks, chunk_elems, hyper, ngroups, nullptr, nullptr, nullptr, partials);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }
@@ -288,7 +388,8 @@ extern "C" int omnipq_adamw_finalize(int nchunks, const double *partials, const 
                                      long long *counters, float *result, float *coef, void *stream) {
   if (nchunks < 0 || ngroups < 1) return OMNIPQ_EINVAL;
   if (!hyper || !counters || !result || !coef || (nchunks > 0 && !partials)) return OMNIPQ_EINVAL;
-  adamw_finalize_kernel<<<1, kAdamThreads, 0, (hipStream_t)stream>>>(nchunks, partials, hyper, ngroups, counters, result, coef);
+  adamw_finalize_kernel<false><<<1, kAdamThreads, 0, (hipStream_t)stream>>>(nchunks, partials, hyper, ngroups, 1, counters,
+                                                                            nullptr, result, coef);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }
@@ -299,8 +400,47 @@ extern "C" int omnipq_adamw_update(int nrec, int nchunks, const void *records, c
   if (!coef || !result) return OMNIPQ_EINVAL;
   if (nrec == 0 || nchunks == 0) return OMNIPQ_OK;
   if (!records || !chunks) return OMNIPQ_EINVAL;
-  adamw_update_kernel<<<nchunks, kAdamThreads, 0, (hipStream_t)stream>>>((const AdamRec *)records, chunks, chunk_elems, coef,
-                                                                        result);
+  adamw_update_kernel<false><<<nchunks, kAdamThreads, 0, (hipStream_t)stream>>>((const AdamRec *)records, chunks, chunk_elems,
+                                                                               nullptr, nullptr, nullptr, coef, result);
+  OMNIPQ_LAUNCH_CHECK();
+  return OMNIPQ_OK;
+}
+
+// ---- gradient accumulation: the same three launches on every micro-batch ----------------------------------------------------
+
+extern "C" int omnipq_adamw_accum_sqnorm(int nrec, int nchunks, const void *records, const int *chunks, int chunk_elems,
+                                         const double *hyper, int ngroups, const float *exp_avg_base, float *acc_base,
+                                         const long long *accum, double *partials, void *stream) {
+  if (nrec < 0 || nchunks < 0 || ngroups < 1 || bad_chunk(chunk_elems)) return OMNIPQ_EINVAL;
+  if (!hyper || !exp_avg_base || !acc_base || !accum) return OMNIPQ_EINVAL;
+  if (nrec == 0 || nchunks == 0) return OMNIPQ_OK;
+  if (!records || !chunks || !partials) return OMNIPQ_EINVAL;
+  adamw_grad_sqnorm_kernel<true><<<nchunks, kAdamThreads, 0, (hipStream_t)stream>>>(
+      (const AdamRec *)records, chunks, chunk_elems, hyper, ngroups, exp_avg_base, acc_base, accum, partials);
+  OMNIPQ_LAUNCH_CHECK();
+  return OMNIPQ_OK;
+}
+
+extern "C" int omnipq_adamw_accum_finalize(int nchunks, const double *partials, const double *hyper, int ngroups,
+                                           int accum_steps, long long *counters, long long *accum, float *result, float *coef,
+                                           void *stream) {
+  if (nchunks < 0 || ngroups < 1 || accum_steps < 1) return OMNIPQ_EINVAL;
+  if (!hyper || !counters || !accum || !result || !coef || (nchunks > 0 && !partials)) return OMNIPQ_EINVAL;
+  adamw_finalize_kernel<true><<<1, kAdamThreads, 0, (hipStream_t)stream>>>(nchunks, partials, hyper, ngroups, accum_steps,
+                                                                           counters, accum, result, coef);
+  OMNIPQ_LAUNCH_CHECK();
+  return OMNIPQ_OK;
+}
+
+extern "C" int omnipq_adamw_accum_update(int nrec, int nchunks, const void *records, const int *chunks, int chunk_elems,
+                                         const float *exp_avg_base, const float *acc_base, const long long *accum,
+                                         const float *coef, const float *result, void *stream) {
+  if (nrec < 0 || nchunks < 0 || bad_chunk(chunk_elems)) return OMNIPQ_EINVAL;
+  if (!exp_avg_base || !acc_base || !accum || !coef || !result) return OMNIPQ_EINVAL;
+  if (nrec == 0 || nchunks == 0) return OMNIPQ_OK;
+  if (!records || !chunks) return OMNIPQ_EINVAL;
+  adamw_update_kernel<true><<<nchunks, kAdamThreads, 0, (hipStream_t)stream>>>(
+      (const AdamRec *)records, chunks, chunk_elems, exp_avg_base, acc_base, accum, coef, result);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }

@@ -17,6 +17,13 @@ What differs from torch.optim.AdamW, all of it stated rather than hidden:
   * `.grad` is read-only: the clipped gradient is never written back (nothing in the reference reads it afterwards);
   * `exp_avg` / `exp_avg_sq` of all parameters are two flat f32 buffers, `state[p]` holds views into them.
 `state_dict()` / `load_state_dict()` are interchangeable with torch.optim.AdamW's in both directions.
+
+Gradient accumulation (the reference's `step_freq`: train.py:493-494 zeroes the gradients on the first of k micro-batches,
+train.py:562-576 clips and steps on the last): `FusedAdamW(..., accum_steps=k)`.  `step()` / `launch()` are then called once
+per MICRO-batch; each call is the same three launches (the omnipq_adamw_accum_* family), which add the gradients into a flat
+f32 accumulator laid out like `exp_avg`, and every k-th call clips and applies the SUM -- the reference does not divide its
+loss by step_freq either; `grad_scale = 1 / k` gives the mean.  The micro-batch counter is a device word the launches read, so
+one captured graph serves every micro-batch; `micro` / `is_update_step` mirror it on the host without reading the device.
 """
 import ctypes
 import os
@@ -53,13 +60,15 @@ class _Table:
 
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
-                 max_norm=0.0, grad_scale=1.0, chunk_elems=CHUNK):
+                 max_norm=0.0, grad_scale=1.0, chunk_elems=CHUNK, accum_steps=1):
         if amsgrad:
             raise NotImplementedError("FusedAdamW: amsgrad is not implemented (the reference does not use it)")
         if maximize:
             raise NotImplementedError("FusedAdamW: maximize is not implemented (the reference does not use it)")
         if chunk_elems <= 0 or chunk_elems % 1024:
             raise ValueError("FusedAdamW: chunk_elems must be a positive multiple of 1024")
+        if isinstance(accum_steps, bool) or not isinstance(accum_steps, (int, np.integer)) or accum_steps < 1:
+            raise ValueError("FusedAdamW: accum_steps must be an integer >= 1 (the number of micro-batches summed per step)")
         # torch.optim.AdamW validates the values and knows which keys a param_group of THIS torch carries: its defaults are
         # taken over as they are, so that a state_dict of either optimiser has the other's param_groups keys
         probe = torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
@@ -68,6 +77,7 @@ class FusedAdamW(torch.optim.Optimizer):
         super().__init__(params, dict(probe.defaults))
         self.max_norm, self.grad_scale = float(max_norm), float(grad_scale)
         self.chunk_elems = int(chunk_elems)
+        self.accum_steps = int(accum_steps)
         plist = [p for g in self.param_groups for p in g["params"]]
         if not plist:
             raise ValueError("FusedAdamW: no parameters")
@@ -85,6 +95,13 @@ class FusedAdamW(torch.optim.Optimizer):
             total += p.numel()
         self.exp_avg = torch.zeros(total + 4, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(total + 4, dtype=torch.float32, device=dev)
+        # accumulation: the running sum of the gradients, laid out like exp_avg (a record's segment is found through its
+        # exp_avg pointer), and {micro-batches summed, apply mark} in device memory.  accum_steps == 1 allocates neither.
+        self.acc = self.accum = None
+        if self.accum_steps > 1:
+            self.acc = torch.zeros(total + 4, dtype=torch.float32, device=dev)
+            self.accum = torch.zeros(2, dtype=torch.int64, device=dev)
+        self._micro, self._applied = 0, False
         ngroups = len(self.param_groups)
         self.counters = torch.zeros(2, dtype=torch.int64, device=dev)             # t, skipped
         self.result = torch.zeros(4, dtype=torch.float32, device=dev)             # total_norm, clip_coef, found_nonfinite, g coefficient
@@ -130,6 +147,30 @@ class FusedAdamW(torch.optim.Optimizer):
         """steps skipped because the gradient norm was not finite (reads the device)"""
         return int(self.counters[1])
 
+    @property
+    def micro(self):
+        """micro-batches summed into the accumulator since the last applying call, in [0, accum_steps): the host's mirror
+        of the device word (no device read -- exact, because a skipped non-finite step resets the device word as well)"""
+        return self._micro
+
+    @property
+    def is_update_step(self):
+        """was the last step() / launch() (or replay of a captured launch()) the applying one?  Host-side, no device read."""
+        return self._applied
+
+    def reset_accumulation(self):
+        """Discard a partial sum (where the reference's zero_grad does: the start of an epoch).  The device word is set to 0
+        on the current stream, the host does not read the device; the next call overwrites the accumulator."""
+        if self.accum is not None:
+            with torch.no_grad():
+                self.accum.zero_()
+        self._micro, self._applied = 0, False
+
+    def replayed(self):
+        """A captured launch() was replayed once: advance the host mirror as launch() itself does."""
+        self._micro = (self._micro + 1) % self.accum_steps
+        self._applied = self._micro == 0
+
     def state_dict(self):
         t = float(self.t)                          # the one host read of the device counter
         for st in self.state.values():
@@ -162,6 +203,7 @@ class FusedAdamW(torch.optim.Optimizer):
                     v.copy_(st["exp_avg_sq"])
                     st["exp_avg"], st["exp_avg_sq"] = m, v
             self.counters[0] = int(steps.pop()) if steps else 0
+        self.reset_accumulation()                    # the accumulator is not part of a state_dict (nor is torch's .grad)
         self._sent = None
         self.sync_hyperparameters()
 
@@ -229,6 +271,10 @@ class FusedAdamW(torch.optim.Optimizer):
         if hit is not None and hit.key == key:
             return hit
         shape_key = tuple((p.data_ptr(), p.numel(), gi) for gi, p in active)
+        if self._micro != 0 and hit is not None and hit.shape_key != shape_key:
+            # a parameter that was absent at micro == 0 would add into whatever an earlier step left in its accumulator
+            raise RuntimeError(f"FusedAdamW: the set of parameters with gradients changed after {self._micro} of "
+                               f"{self.accum_steps} accumulated micro-batches (reset_accumulation() discards the partial sum)")
         if hit is not None and hit.shape_key == shape_key:
             if capturing:
                 hit.key = None                       # stale until retarget()
@@ -258,7 +304,8 @@ class FusedAdamW(torch.optim.Optimizer):
     # ---- the step ------------------------------------------------------------------------------------------------------------
     def launch(self):
         """The three launches on the current stream, hyper-parameters as they are on the device (no staging, no host read):
-        what CapturedStep records into its graph.  -> the device tensor grad_total_norm."""
+        what CapturedStep records into its graph.  -> the device tensor grad_total_norm.  accum_steps = k > 1: one call per
+        micro-batch, the same three launches every time; the k-th call applies the sum, the others only add and count."""
         if self.device.type != "cuda":
             raise RuntimeError("CPU not supported")      # like the native ops: no CPU path in the product
         ext = _ext()
@@ -266,18 +313,35 @@ class FusedAdamW(torch.optim.Optimizer):
         if tab.nrec == 0:
             return self.grad_total_norm
         lib, ng = ext._lib0, len(self.param_groups)
+        if self.accum_steps > 1:
+            ext._run(lib.omnipq_adamw_accum_sqnorm, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.chunks),
+                     self.chunk_elems, _ptr(self._hyper), ng, _ptr(self.exp_avg), _ptr(self.acc), _ptr(self.accum),
+                     _ptr(tab.partials))
+            ext._run(lib.omnipq_adamw_accum_finalize, self.result, tab.nchunks, _ptr(tab.partials), _ptr(self._hyper), ng,
+                     self.accum_steps, _ptr(self.counters), _ptr(self.accum), _ptr(self.result), _ptr(self._coef))
+            ext._run(lib.omnipq_adamw_accum_update, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.chunks),
+                     self.chunk_elems, _ptr(self.exp_avg), _ptr(self.acc), _ptr(self.accum), _ptr(self._coef),
+                     _ptr(self.result))
+            self.replayed()
+            return self.grad_total_norm
         ext._run(lib.omnipq_adamw_grad_sqnorm, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.chunks),
                  self.chunk_elems, _ptr(self._hyper), ng, _ptr(tab.partials))
         ext._run(lib.omnipq_adamw_finalize, self.result, tab.nchunks, _ptr(tab.partials), _ptr(self._hyper), ng,
                  _ptr(self.counters), _ptr(self.result), _ptr(self._coef))
         ext._run(lib.omnipq_adamw_update, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.chunks),
                  self.chunk_elems, _ptr(self._coef), _ptr(self.result))
+        self._applied = True
         return self.grad_total_norm
 
     @torch.no_grad()
     def step(self, closure=None):
         """clip_grad_norm_(max_norm) + AdamW.step() in three launches.  -> grad_total_norm, a 0-dim DEVICE tensor (the norm of
-        grad_scale * gradients before clipping; rewritten by the next step).  Parameters whose .grad is None are left out."""
+        grad_scale * gradients before clipping; rewritten by the next step).  Parameters whose .grad is None are left out.
+        accum_steps = k > 1: call once per micro-batch.  Every call adds the gradients into the accumulator and returns the
+        norm of grad_scale * the running SUM; every k-th call clips and applies that sum (`is_update_step`), the others leave
+        parameters, moments and the step count alone.  The gradients are summed as in the reference, whose loss is not
+        divided by step_freq: grad_scale = 1 / k gives the mean.  The set of parameters with gradients must not change
+        inside one accumulation; their gradients' addresses may."""
         if closure is not None:
             raise NotImplementedError("FusedAdamW.step: closures are not supported")
         if self.device.type != "cuda":
@@ -286,10 +350,17 @@ class FusedAdamW(torch.optim.Optimizer):
         return self.launch()
 
     # ---- save / restore (CapturedStep's warm-up and capture runs must leave no trace) ---------------------------------------
+    def _saved_tensors(self):
+        return (self.exp_avg, self.exp_avg_sq, self.counters, self.result) + \
+            ((self.acc, self.accum) if self.accum_steps > 1 else ())
+
     def snapshot(self):
-        return [t.detach().clone() for t in (self.exp_avg, self.exp_avg_sq, self.counters, self.result)]
+        """moments, counters and -- the warm-up and capture runs advance them too -- the accumulator, the device micro-batch
+        counter and its host mirror"""
+        return [t.detach().clone() for t in self._saved_tensors()] + [(self._micro, self._applied)]
 
     def restore(self, saved):
         with torch.no_grad():
-            for t, s in zip((self.exp_avg, self.exp_avg_sq, self.counters, self.result), saved):
+            for t, s in zip(self._saved_tensors(), saved):
                 t.copy_(s)
+        self._micro, self._applied = saved[-1]

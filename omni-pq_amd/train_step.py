@@ -89,23 +89,38 @@ class CapturedStep:
                      1 / loss_scale; a step whose gradient norm is not finite leaves the weights alone (optimizer.skipped).
                      Building the stepper changes neither parameters nor optimiser state.  `stepper.grad_total_norm` is
                      the device tensor clip_grad_norm_ would have returned.
-    step_freq        1.  Gradient accumulation (the reference's step_freq > 1) is refused: every step starts from
-                     empty gradients and an in-graph optimiser applies every step.
+    step_freq        gradient accumulation (the reference's step_freq, train.py:493-494 and :562-576): k > 1 is accepted with
+                     optimizer=optim.FusedAdamW(..., accum_steps=k) and with nothing else -- every step still starts from
+                     empty gradients, the SUM lives in the optimizer's accumulator.  Every step() is then one micro-batch and
+                     one replay of the same graph: the micro-batch counter is a device word the captured launches read.
+                     `stepper.is_update_step` (a host bool, valid once step() has returned) says whether that call
+                     applied the sum: call scheduler.step() and update_teacher() only then.  The gradients are summed, as
+                     in the reference (grad_scale = 1 / k for the mean).  With `buckets` every micro-batch's gradients are
+                     all-reduced before they are accumulated: the same sum, k times the communication (an all-reduce
+                     deferred to the k-th micro-batch is not implemented).  A host-stepped optimizer accumulates outside:
+                     step_freq stays 1, the caller adds `.grad` up after each step().
     """
 
     def __init__(self, net, criterion, example_inputs, example_labels=None, *, model=None, amp_dtype=torch.bfloat16,
                  loss_scale=1.0, graph=True, prefetch="forward", fps_footprint=None, teacher=None, teacher_example=None,
                  ema=None, buckets=None, defer=True, warmup=3, distributed=False, before_capture=None,
                  teacher_to_criterion=False, lookahead=1, head_rounds=None, optimizer=None, step_freq=1):
-        if step_freq != 1:
-            raise ValueError("CapturedStep: gradient accumulation (step_freq > 1) is not supported -- every step starts from "
-                             "empty gradients" + (", and the in-graph optimizer applies every step" if optimizer is not None
-                                                  else ""))
         if optimizer is not None:
             import optim
             if not isinstance(optimizer, optim.FusedAdamW):
                 raise TypeError("CapturedStep(optimizer=...): an optim.FusedAdamW or None -- any other optimizer steps from the "
                                 "host, after step()")
+        accum_steps = optimizer.accum_steps if optimizer is not None else 1
+        if isinstance(step_freq, bool) or not isinstance(step_freq, int) or step_freq < 1 or step_freq != accum_steps:
+            raise ValueError(f"CapturedStep: step_freq={step_freq!r} with " +
+                             (f"an optimizer built with accum_steps={accum_steps}" if optimizer is not None
+                              else "no in-graph optimizer") +
+                             " -- every step starts from empty gradients, so gradient accumulation over k micro-batches "
+                             "needs optimizer=optim.FusedAdamW(accum_steps=k) together with step_freq=k (a host-stepped "
+                             "optimizer accumulates `.grad` itself after each step(), with step_freq=1)")
+        self.step_freq = step_freq
+        self.is_update_step = False
+        if optimizer is not None:
             if float(loss_scale) != 1.0:
                 optimizer.grad_scale = 1.0 / float(loss_scale)
         self.optimizer = optimizer
@@ -347,13 +362,16 @@ class CapturedStep:
         in front of the replay."""
         if self.lookahead != 2 and (after_next_inputs is not None or after_next_teacher_inputs is not None):
             raise ValueError("CapturedStep.step: after_next_inputs needs a stepper built with lookahead=2")
-        if self.teacher is not None and self.ema is not None:
+        # will this call apply the (accumulated) gradients?  Known up front: the optimizer mirrors its device counter
+        applies = self.optimizer is None or self.optimizer.micro == self.step_freq - 1
+        if self.teacher is not None and self.ema is not None and applies:
             self._steps_unaveraged = getattr(self, "_steps_unaveraged", 0) + 1
             if self._steps_unaveraged == 4:
                 import warnings
                 warnings.warn("CapturedStep: a teacher and an EMA decay are set but update_teacher(global_step) has not been "
-                              "called for three steps -- the teacher's weights are not being averaged (call it after "
+                              "called for three applying steps -- the teacher's weights are not being averaged (call it after "
                               "optimizer.step(), where the reference calls update_ema_variables)")
+        self.is_update_step = applies
         if self.graph is None:
             return self._eager_step(inputs, labels, next_inputs, teacher_inputs, next_teacher_inputs, after_next_inputs,
                                     after_next_teacher_inputs)
@@ -412,6 +430,8 @@ class CapturedStep:
             self.optimizer._opt_called = True        # (torch's schedulers warn when they never see optimizer.step())
         self.graph.replay()
         self.replays += 1
+        if self.optimizer is not None:
+            self.optimizer.replayed()                # the host mirror of the micro-batch counter the replay advanced
         for p, g in self._grads:
             p.grad = g
         self._forget_plans()

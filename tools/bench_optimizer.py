@@ -1,18 +1,26 @@
 #!/usr/bin/env python
 """What the three weight-changing lines of the training step (train.py:562-566) cost on the procedural PQ_Transformer with the
-reference's two parameter groups (train.py:364-374), five ways, all live in one process and taking turns:
+reference's two parameter groups (train.py:364-374), seven ways, all live in one process and taking turns:
 
     (a) torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW as train.py constructs it        what a user ran before optim.py
     (b) the same with fused=True
     (c) optim.FusedAdamW.step(), eager                                                       three HIP launches
     (d) a replayed train_step.CapturedStep with the FusedAdamW inside the graph
     (e) a replayed CapturedStep without optimiser, followed by (a)
+    (f) gradient accumulation over two micro-batches inside the graph: a replayed CapturedStep(step_freq=2) with
+        FusedAdamW(accum_steps=2); one iteration = one micro-batch
+    (g) the same accumulation from the host: a replayed CapturedStep without optimiser, the 519 gradient tensors copied
+        (first micro-batch) or added (second, torch._foreach_add_) into tensors of the caller's, FusedAdamW.step() on the
+        sum every second call; one iteration = one micro-batch
 
 Every case is timed `--rounds` times (>= 5), interleaved, over a window of `--iters` iterations that ends in a device
 synchronise: WALL time per iteration, median and spread (max - min) over the rounds.  A last pass runs a few iterations of
 every case under torch.profiler and sums the device time of its kernels.  For (c) the traffic the arithmetic needs (32 bytes
 per parameter: the norm reads g, the update reads p, g, m, v and writes p, m, v) over the time is set against 8 TB/s and
-against the 6.25 TB/s the project's copy probe reaches.  `--chunks` times (c) at other chunk sizes as well.
+against the 6.25 TB/s the project's copy probe reaches.  `--chunks` times (c) at other chunk sizes as well.  The accumulate
+launch of (f) (omnipq_adamw_accum_sqnorm: reads the gradient and the sum, writes the sum -- 12 bytes per parameter) is timed
+on its own: an eager FusedAdamW(accum_steps=10**6) never reaches its applying call, so every step() after the first is that
+launch on a non-first micro-batch plus a finalise and an update that return at once.
 
 Learning rates are tiny on purpose (time does not depend on them): hundreds of steps on the stand-in loss must not drive
 the weights to a non-finite gradient norm, which FusedAdamW would answer by skipping the update -- `skipped` is checked.
@@ -48,8 +56,9 @@ def groups(net):
             {"params": [p for n, p in net.named_parameters() if "decoder" in n and p.requires_grad], "lr": DECODER_LR}]
 
 
-def kernel_time_ms(fn, iters):
-    """summed device time of everything `fn` launches, per call (torch.profiler, a pass of its own); None: not measured"""
+def kernel_time_ms(fn, iters, match=None):
+    """summed device time of everything `fn` launches (match: of the kernels whose name contains it), per call
+    (torch.profiler, a pass of its own); None: not measured"""
     try:
         from torch.profiler import ProfilerActivity, profile
         torch.cuda.synchronize()
@@ -60,6 +69,11 @@ def kernel_time_ms(fn, iters):
         total = 0.0
         for e in prof.key_averages():
             total += getattr(e, "self_device_time_total", None) or getattr(e, "self_cuda_time_total", 0.0) or 0.0
+        if match is not None:
+            total = 0.0
+            for e in prof.key_averages():
+                if match in e.key:
+                    total += getattr(e, "self_device_time_total", None) or getattr(e, "self_cuda_time_total", 0.0) or 0.0
         return total / 1e3 / iters if total > 0 else None
     except Exception as exc:  # the figure is reported as not measured, never guessed
         print(f"kernel time not measured: {type(exc).__name__}: {exc}", flush=True)
@@ -143,6 +157,37 @@ def main():
         opt_e.step()
     cases["e_replay_then_torch_adamw_clip"] = run_e
 
+    net_f = copy.deepcopy(base)
+    opt_f = optim.FusedAdamW(groups(net_f), lr=LR, weight_decay=WD, max_norm=CLIP, accum_steps=2)
+    st_f = train_step.CapturedStep(net_f, criterion, {"point_clouds": pool[0]}, optimizer=opt_f, step_freq=2)
+    net_g = copy.deepcopy(base)
+    opt_g = optim.FusedAdamW(groups(net_g), lr=LR, weight_decay=WD, max_norm=CLIP)
+    st_g = train_step.CapturedStep(net_g, criterion, {"point_clouds": pool[0]})
+    assert st_f.launch == st_g.launch == "hipGraph replay"
+    count.update(f=0, g=0)
+    host_sum = {}
+
+    def run_f():
+        count["f"] += 1
+        st_f.step(None, None, next_inputs=pool[count["f"] % len(pool)])
+    cases["f_replay_accumulating_in_the_graph"] = run_f
+
+    def run_g():
+        count["g"] += 1
+        st_g.step(None, None, next_inputs=pool[count["g"] % len(pool)])
+        if "params" not in host_sum:
+            host_sum["params"] = [p for p in net_g.parameters() if p.grad is not None]
+            host_sum["sums"] = [torch.empty_like(p.grad) for p in host_sum["params"]]
+        grads = [p.grad for p in host_sum["params"]]
+        if count["g"] % 2:
+            torch._foreach_copy_(host_sum["sums"], grads)
+        else:
+            torch._foreach_add_(host_sum["sums"], grads)
+            for p, a in zip(host_sum["params"], host_sum["sums"]):
+                p.grad = a                            # (the next replay hands the graph's own gradient tensors back)
+            opt_g.step()
+    cases["g_replay_accumulating_from_the_host"] = run_g
+
     walls = {k: [] for k in cases}
     for rnd in range(args.rounds):
         for name, fn in cases.items():
@@ -155,9 +200,11 @@ def main():
             torch.cuda.synchronize()
             walls[name].append((time.perf_counter() - t0) * 1e3 / args.iters)
             print(f"round {rnd} {name:40s} {walls[name][-1]:8.4f} ms wall per iteration", flush=True)
-    for name, opt in list(fused.items()) + [("d", opt_d)]:
+    assert opt_f.t == opt_g.t == count["f"] // 2 == count["g"] // 2, (opt_f.t, opt_g.t, count)
+    for name, opt in list(fused.items()) + [("d", opt_d), ("f", opt_f), ("g", opt_g)]:
         assert opt.skipped == 0, f"{name}: {opt.skipped} steps were skipped for a non-finite gradient norm -- not a measurement"
     assert torch.isfinite(st_d.static_loss).item() and torch.isfinite(st_e.static_loss).item()
+    assert torch.isfinite(st_f.static_loss).item() and torch.isfinite(st_g.static_loss).item()
     import pointnet2_utils
     pointnet2_utils._ext.fps_check()
 
@@ -176,7 +223,8 @@ def main():
                 "old_spread_ms": o["wall_ms_spread"],
                 "holds": bool(o["wall_ms_median"] - n["wall_ms_median"] > o["wall_ms_spread"])}
     out["requirements"] = [verdict("c_fused_adamw_eager", "a_torch_adamw_clip"),
-                           verdict("d_replay_with_fused_adamw_inside", "e_replay_then_torch_adamw_clip")]
+                           verdict("d_replay_with_fused_adamw_inside", "e_replay_then_torch_adamw_clip"),
+                           verdict("f_replay_accumulating_in_the_graph", "g_replay_accumulating_from_the_host")]
     print(json.dumps(out), flush=True)           # (kept even if the profiler pass below does not come back)
 
     if not args.no_kernel_time:
@@ -195,6 +243,25 @@ def main():
                 c[f"{key}_fraction_of_6.25_TBps_copy_ceiling"] = round(rate / 6.25e12, 4)
                 print(f"{name:40s} {need / 1e6:.0f} MB / {key} time = {rate / 1e12:.3f} TB/s = {rate / 8e12:.1%} of 8 TB/s, "
                       f"{rate / 6.25e12:.1%} of the 6.25 TB/s copy ceiling", flush=True)
+    if not args.no_kernel_time:
+        # the accumulate launch alone, on a non-first micro-batch: 12 bytes per parameter
+        net_h = with_static_grads(copy.deepcopy(base))
+        opt_h = optim.FusedAdamW(groups(net_h), lr=LR, weight_decay=WD, max_norm=CLIP, accum_steps=10 ** 6)
+        for _ in range(args.warmup):
+            opt_h.step()
+        ms = kernel_time_ms(opt_h.step, 20, match="adamw_grad_sqnorm_kernel")
+        assert opt_h.t == 0 and 0 < opt_h.micro < 10 ** 6
+        acc = {"bytes_needed": 12 * nparam, "kernel_ms": None if ms is None else round(ms, 4)}
+        if ms:
+            rate = 12 * nparam / (ms * 1e-3)
+            acc.update(bytes_per_s=round(rate, 0), fraction_of_8_TBps=round(rate / 8e12, 4),
+                       **{"fraction_of_6.25_TBps_copy_ceiling": round(rate / 6.25e12, 4)})
+            print(f"{'accumulate launch (accum_sqnorm)':40s} {12 * nparam / 1e6:.0f} MB / {ms:.4f} ms kernel time = "
+                  f"{rate / 1e12:.3f} TB/s = {rate / 8e12:.1%} of 8 TB/s, {rate / 6.25e12:.1%} of the 6.25 TB/s copy ceiling "
+                  f"(beside it: the norm pass + update of c_fused_adamw_eager above, {32 * nparam / 1e6:.0f} MB)", flush=True)
+        else:
+            print("accumulate launch (accum_sqnorm): kernel time not measured", flush=True)
+        out["accumulate_launch"] = acc
     kb, kc = out["cases"]["b_torch_adamw_fused_clip"]["kernel_ms"], out["cases"]["c_fused_adamw_eager"]["kernel_ms"]
     if kb and kc:
         out["torch_fused_kernel_time_beats_ours"] = bool(kb < kc)
