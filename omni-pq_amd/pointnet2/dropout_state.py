@@ -68,6 +68,14 @@ class _DropoutState:
         self.cur[(self.slot, device)] = st.clone()
         self.salt = 0
 
+    def bump(self, device):
+        """Advance the current slot's counter in place and return the COUNTER ITSELF (static address) -- for a consumer
+        whose one launch reads the seed and whose backward does not (the gamma-mixture guide keeps its draws instead):
+        no copy, so a captured replay that finds the counter changed draws afresh."""
+        st = self._state(torch.device(device))
+        st.add_(0x9E3779B97F4A7C15 >> 2)
+        return st
+
     def set_state(self, device, value):
         """(tests) restart the counter from a known value"""
         device = torch.device(device)
