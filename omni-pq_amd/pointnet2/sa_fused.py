@@ -16,10 +16,12 @@ Numerics: activations are stored in bf16, every contraction accumulates in f32 o
 statistics are f32 per block / f64 across blocks.  This is the `bf16` compute mode of bench.py; the f32
 parity mode keeps the reference's op-by-op composition (pointnet2_modules.py).
 """
+import collections
 import ctypes
 import functools
 import os
 import threading
+import typing
 import weakref
 
 import torch
@@ -277,9 +279,6 @@ def affine_pays(P, N):
 # GEMM + slab reduction per layer, as outside the block)
 SA_WGRADS_GROUPED = True
 POOL_EPILOGUE = True
-# the last layer's BatchNorm finalize inside the pool-select launch, its backward means / affine gradients inside the pool
-# backward apply
-_FOLD_SMALL = True
 
 
 # Row plan (csrc/common.h: RowPlan, include/omnipq_sa.h: omnipq_sa_ball_plan).  ball_query pads a ball that holds fewer than
@@ -318,7 +317,7 @@ def row_plan_ok(training, S, P, L, needs_input_grad, pooled):
     centre-gradient kernel does not know it; feature gradients: the caller also asks for at most 8192 source points, the CSR
     builders that do)"""
     return ROW_PLAN and training and S in (32, 64, 128) and P >= PLAN_MIN_ROWS and P % 128 == 0 and L >= 2 and \
-        AFFINE_OPERANDS and POOL_EPILOGUE and _FOLD_SMALL and pooled and not needs_input_grad
+        AFFINE_OPERANDS and POOL_EPILOGUE and pooled and not needs_input_grad
 
 
 class _Plan:
@@ -515,7 +514,7 @@ def last_no_dy_ok(plan, L, P, c2, c3, S, below_keeps_y_only):
     and the no-store omnipq_gemm_nt_e16_bnaffine_pool require)"""
     return LAST_NO_DY and c3 <= LAST_NO_DY_MAX_C3 and plan is not None and getattr(plan, "unit_src", None) is not None and L >= 2 and \
         _partial_sum_rows(P) and below_keeps_y_only and c2 % 128 == 0 and c3 % 128 == 0 and c2 + 32 <= 1024 and S >= 8 and \
-        (S & (S - 1)) == 0 and AFFINE_OPERANDS and POOL_EPILOGUE and _FOLD_SMALL
+        (S & (S - 1)) == 0 and AFFINE_OPERANDS and POOL_EPILOGUE
 
 
 def last_wgrad_dz(Y2, below, hot, plan, S, C3, C2, P, alpha, beta, Wp, out=None):
@@ -586,8 +585,6 @@ class _TnProblem(ctypes.Structure):
                 ("out_rows", ctypes.c_int), ("out_cols", ctypes.c_int), ("out_ld", ctypes.c_int),
                 ("flags", ctypes.c_int), ("rot", ctypes.c_int), ("ba", ctypes.c_void_p), ("bb", ctypes.c_void_p),
                 ("rows_dev", ctypes.c_void_p)]
-
-
 
 
 _ZERO_TAILS = {}
@@ -851,7 +848,6 @@ class deferred_wgrads:
             self.ln_items = []
             if self.on_early_flush is not None:
                 self.on_early_flush(self)
-
 
     def _flush_layernorms(self):
         """All LayerNorm parameter gradients collected so far: ONE reduction launch per 32 of them into one flat
@@ -1273,6 +1269,444 @@ class _Layer:
     __slots__ = ("K", "C", "Wp", "Wt", "a", "b", "mean", "invstd", "Y", "X", "fin", "mom")
 
 
+# Sizes of one stage pass.  P = B * M * S grouped rows; cin = cin_raw rounded up to 8 (feature rows are moved in 16-byte pieces:
+# 6 extra input channels -- rgb + normals, BASELINE configs[3] -- travel as 8, the two extra columns and weight columns zero);
+# kpad: the first layer's contraction length; world: the ranks its BatchNorm statistics are summed over
+_Geom = collections.namedtuple("_Geom", "B N M S P cin cin_raw kpad inv_r world")
+
+
+class StageRoute(typing.NamedTuple):
+    """Every decision of one stage pass, made by stage_route() before anything is launched.  FusedSAStage._forward stores it
+    on ctx; forward and backward dispatch on it and decide nothing themselves.  A new route is a new value of a field here, its
+    condition in stage_route(), and a step function for the dispatchers (_forward_layers, FusedSAStage._backward) to call."""
+    training: bool
+    first: str        # layer 0: "grouped" (on the gathered rows [features | xyz]) | "xyz" (generated from the grouped coordinates,
+                      # never stored: XYZGEN) | "source" (on the source points, gathered afterwards: HOIST_L1)
+    plan_gs: int      # rows per group of the stage's row plan (ROW_PLAN); 0: every row is computed
+    plan_arrives: bool    # the plan that came with idx is the stage's (else forward makes one)
+    feed: tuple       # per layer below the last, what its consumers read: "stored" relu(bn(Y)) | "yab" (Y, a, b) (AFFINE_OPERANDS)
+    finalize: tuple   # per layer, where its BatchNorm is finalised: "launch" (its own) | "relu" (with the ReLU pass) | "consumer"
+                      # (the prologue of the GEMM it feeds) | "pool" (the pool-select launch) | "running" (eval: nothing to do)
+    extrema: str      # ball extrema recorded by the last GEMM (POOL_EPILOGUE): "" (the pool scans Y) | "both" | "one" (the side
+                      # gamma's sign selects: ONE_SIDED_EXTREMA)
+    last: str         # the last layer's backward: "y" (statistics from the stored Y) | "ysel" (from the pooled rows' values) |
+                      # "no_dy" (neither Y3 nor dY3 exists: LAST_NO_DY)
+    keep_x2: bool     # "no_dy": the data-gradient launch leaves X2 for the weight gradient (LAST_X2)
+
+
+def stage_route(training, B, N, M, S, cin_raw, widths, has_features, xyz_grad, feat_grad, plan_gs=None, plan_unit_map=False):
+    """The route of a stage from shapes alone (no tensor, no launch; the module switches are read now).  widths: the layers'
+    output channels; xyz_grad / feat_grad: a gradient flows into the coordinates / the features; plan_gs, plan_unit_map: group
+    size of the plan that came with idx (None: none did) and whether it carries a unit map."""
+    L, P = len(widths), B * M * S
+    if not training:
+        return StageRoute(False, "grouped", 0, False, ("stored",) * (L - 1), ("running",) * L, "", "y", False)
+    xgen = not has_features and xyzgen_ok(P, L, widths[0], xyz_grad) and affine_pays(P, widths[1])
+    plan, arrives = None, False
+    if row_plan_ok(True, S, P, L, xyz_grad or (feat_grad and N > 8192), 128 % S == 0):
+        arrives = plan_gs == PLAN_GROUP
+        plan = _Plan()                        # what the predicates below ask of the plan forward will use
+        plan.gs, plan.unit_src = PLAN_GROUP, (True if (plan_unit_map or not arrives) else None)
+    hoist = hoist_ok(True, has_features or None, _round_up(cin_raw, 8), cin_raw, L, widths[0], xgen)
+    feed = tuple("yab" if (affine_pays(P, widths[l + 1]) or (xgen and l == 0)) else "stored" for l in range(L - 1))
+    extrema = bool(POOL_EPILOGUE) and 128 % S == 0
+    no_dy = extrema and L >= 2 and feed[-1] == "yab" and last_no_dy_ok(plan, L, P, widths[-2], widths[-1], S, True)
+    return StageRoute(
+        True, "xyz" if xgen else "source" if hoist else "grouped", plan.gs if plan is not None else 0, arrives, feed,
+        tuple("consumer" if f == "yab" else "relu" for f in feed) + ("pool" if extrema and widths[-1] <= 1024 else "launch",),
+        "" if not extrema else "one" if (plan is not None and plan.gs == 8 and ONE_SIDED_EXTREMA) else "both",
+        "no_dy" if no_dy else "ysel" if extrema else "y", bool(no_dy and LAST_X2))
+
+
+def _count_uses(route):
+    """the counters the tests read to see which route ran"""
+    global xyzgen_uses, row_plan_uses, hoist_uses, last_no_dy_uses
+    xyzgen_uses += route.first == "xyz"
+    hoist_uses += route.first == "source"
+    row_plan_uses += route.plan_gs > 0
+    last_no_dy_uses += route.last == "no_dy"
+
+
+# ---- forward steps: each allocates its buffers and makes its calls (inside the caller's _row_plan block) ----
+
+def _new_layer(l, W, g, training):
+    """Layer l with its prepared weight.  The reference concatenates [xyz(3), features(cin)] (pointnet2_utils.py:357-359); the
+    gathered rows are [features(cin), xyz(3), 0-pad] so that feature pieces stay 16-byte aligned -- layer 0 rotates the weight
+    columns to match."""
+    lay = _Layer()
+    lay.X = lay.fin = None
+    W2 = W.detach().reshape(W.shape[0], -1)
+    padded_w = l == 0 and g.cin != g.cin_raw
+    if padded_w:
+        W2 = torch.nn.functional.pad(W2, (0, g.cin - g.cin_raw))     # zero columns for the padded feature channels
+    lay.K, lay.C = (g.kpad if l == 0 else W2.shape[1]), W2.shape[0]
+    lay.Wp, lay.Wt = prep_weight(W2, lay.C, lay.K, rot=3 if l == 0 else 0, transpose=training,
+                                 persistent=is_persistent(W) and not padded_w)
+    return lay
+
+
+def _gather_rows(g, xyz_c, cen_c, idx, feat_pm, xpad, dev):
+    """the grouped rows [features | xyz | 0-pad] (xpad = 8: the coordinates only, 16 bytes per grouped position); with a plan
+    the gather writes the compact row space, and every later launch works on the rows in use"""
+    X0 = torch.empty((g.P, xpad), device=dev, dtype=E16.dtype)
+    _call(_lib.omnipq_sa_gather, xyz_c, g.B, g.N, g.M, g.S, g.cin, xpad, g.inv_r, _p(xyz_c), _p(cen_c), _p(idx), _p(feat_pm),
+          _p(X0))
+    return X0
+
+
+def _first_generated(g, lay, X0, sums, dev):
+    """first layer "xyz": never materialised (see XYZGEN), its statistics from the moments of the grouped coordinates"""
+    lay.mom = torch.empty((12,), device=dev, dtype=torch.float64)
+    _call(_lib.omnipq_sa_xyz_moments, X0, g.P, _p(X0), X0.shape[1], _p(lay.mom))
+    _call(_lib.omnipq_sa_xyz_stats, X0, lay.C, _p(lay.Wp), lay.K, _p(lay.mom), _p(sums))
+    lay.Y = None
+
+
+def _first_on_source(g, lay, plan, xyz_c, cen_c, idx, feat2d, sums, dev):
+    """first layer "source" (see HOIST_L1): Z = features W_f^T per source point, then Y = Z[idx] + W_x . xrel per grouped row
+    with its statistics.  -> the rows' relative coordinates (the weight gradient's operand)"""
+    B, N, M, S, P, cin = g[:6]
+    Z = gemm_nt_f32(feat2d, lay.Wp, B * N, lay.C, cin, cin, lay.K)       # W_f = the first cin prepared columns
+    lay.Y = torch.empty((P, lay.C), device=dev, dtype=E16.dtype)
+    Xrel = torch.empty((P, 8), device=dev, dtype=E16.dtype)
+    nws = int(_lib.omnipq_sa_l1_rows_workspace_bytes(B, M, S, lay.C))
+    ws = torch.empty((nws // 4,), device=dev, dtype=torch.float32)
+    tk = zeros_f32(nws // (8 * lay.C * 16) + 1, dev)                     # one zero word per 16 workgroups
+    _call(_lib.omnipq_sa_l1_rows, Z, B, N, M, S, lay.C, g.inv_r, _p(xyz_c), _p(cen_c), _p(idx), _p(Z),
+          ctypes.c_void_p(lay.Wp.data_ptr() + cin * lay.Wp.element_size()), lay.K,
+          _p(plan.rows_dev if plan is not None else None), _p(plan.unit_src if plan is not None else None),
+          _p(plan.row_w if plan is not None else None), _p(lay.Y), _p(Xrel), _p(sums), _p(ws), _p(tk))
+    return Xrel
+
+
+def _middle_layer(route, g, l, lay, below, X, X0, sums):
+    if l == 1 and route.first == "xyz":
+        lay.Y = gemm_nt_xyz(X0, below, lay.Wp, g.P, lay.C, lay.K, sums)
+    elif route.feed[l - 1] == "yab":
+        # the layer below never stored relu(bn(Y)): this GEMM rebuilds it while staging its operand
+        lay.Y = gemm_nt_affine(below.Y, below, lay.Wp, g.P, lay.C, lay.K, sums=sums)
+    else:
+        lay.Y = _gemm_nt_stats(X, lay.Wp, g.P, lay.C, lay.K, sums)
+
+
+def _last_layer(route, g, lay, below, X, gamma, sums, dev):
+    """The last GEMM; route.extrema: it also records every ball's extrema, so the pooling pass needs no Y (a planned stage
+    records them per group of the compact row space; pool_select merges a ball's).  -> pool (see _gemm_nt_stats) or None"""
+    pool = None
+    if route.extrema:
+        per = route.plan_gs or g.S
+        ext16 = torch.empty((2, g.P // per, lay.C), device=dev, dtype=E16.dtype)
+        ext8 = torch.empty((2, g.P // per, lay.C), device=dev, dtype=torch.uint8)
+        pool = (per, ext16[0], ext16[1], ext8[0], ext8[1])
+        if route.extrema == "one":
+            _plan_pool_gamma(gamma.detach())         # include/omnipq_sa.h: omnipq_row_plan.pool_gamma
+    if below is not None and route.feed[-1] == "yab":
+        lay.Y = gemm_nt_affine(below.Y, below, lay.Wp, g.P, lay.C, lay.K, sums=sums, pool=pool, store=route.last != "no_dy")
+    else:
+        lay.Y = _gemm_nt_stats(X, lay.Wp, g.P, lay.C, lay.K, sums, pool=pool)
+    return pool
+
+
+def _finalize(how, g, lay, sums, gamma, beta, bn, dev):
+    """Layer constants a | b | mean | invstd and the running-statistics update, where the route puts them.  -> lay.X"""
+    rm, rv, _, momentum, eps = bn
+    stats = torch.empty((4, lay.C), device=dev)
+    lay.a, lay.b, lay.mean, lay.invstd = stats[0], stats[1], stats[2], stats[3]
+    count = float(g.P) * g.world
+    if how in ("consumer", "pool"):
+        # by the launch that reads the constants first: gemm_nt_affine / gemm_nt_xyz, omnipq_sa_pool_select_finalize
+        lay.fin = (sums, count, gamma.detach(), beta.detach(), eps, momentum, rm, rv, None)
+    elif how == "relu":
+        lay.X = torch.empty_like(lay.Y)
+        _call(_lib.omnipq_bn_finalize_relu, lay.Y, g.P, lay.C, count, _p(sums), _p(gamma.detach()), _p(beta.detach()), eps,
+              momentum, _p(rm), _p(rv), _p(None), _p(lay.Y), _p(lay.X), _p(lay.a), _p(lay.b), _p(lay.mean), _p(lay.invstd))
+    else:
+        _call(_lib.omnipq_bn_finalize, sums, lay.C, count, _p(sums), _p(gamma.detach()), _p(beta.detach()), eps, momentum,
+              _p(rm), _p(rv), _p(lay.a), _p(lay.b), _p(lay.mean), _p(lay.invstd), _p(None))
+    return lay.X
+
+
+def _eval_layer(g, lay, X, gamma, beta, bn, last):
+    """eval mode: constants from the running estimates, every activation stored.  -> lay.X"""
+    rm, rv, _, _, eps = bn
+    lay.Y = _gemm_nt(X, lay.Wp, g.P, lay.C, lay.K)
+    lay.invstd = torch.rsqrt(rv + eps)
+    lay.mean = rm
+    lay.a = (gamma.detach() * lay.invstd).contiguous()
+    lay.b = (beta.detach() - rm * lay.a).contiguous()
+    if not last:
+        lay.X = torch.empty_like(lay.Y)
+        _call(_lib.omnipq_bnrelu, lay.Y, g.P, lay.C, _p(lay.Y), _p(lay.a), _p(lay.b), _p(lay.X))
+    return lay.X
+
+
+def _forward_layers(route, g, plan, xyz_c, cen_c, idx, feat_pm, params, bn_cfg, dev):
+    """-> (layers, X0, the relative coordinates of a "source" first layer, pool of the last GEMM)"""
+    L = len(bn_cfg)
+    layers, X0, Xrel, pool = [], None, None, None
+    if route.first != "source":
+        X0 = _gather_rows(g, xyz_c, cen_c, idx, feat_pm, 8 if route.first == "xyz" else g.kpad, dev)
+    X = X0
+    for l in range(L):
+        W, gamma, beta = params[3 * l], params[3 * l + 1], params[3 * l + 2]
+        lay = _new_layer(l, W, g, route.training)
+        if not route.training:
+            X = _eval_layer(g, lay, X, gamma, beta, bn_cfg[l], l == L - 1)
+            layers.append(lay)
+            continue
+        sums = zeros_f64(2, lay.C, dev)
+        if l == L - 1:
+            pool = _last_layer(route, g, lay, layers[-1] if l else None, X, gamma, sums, dev)
+        elif l > 0:
+            _middle_layer(route, g, l, lay, layers[-1], X, X0, sums)
+        elif route.first == "xyz":
+            _first_generated(g, lay, X0, sums, dev)
+        elif route.first == "source":
+            Xrel = _first_on_source(g, lay, plan, xyz_c, cen_c, idx, feat_pm.reshape(g.B * g.N, g.cin), sums, dev)
+        else:
+            lay.Y = _gemm_nt_stats(X0, lay.Wp, g.P, lay.C, lay.K, sums)       # first layer "grouped": GEMM + batch statistics
+        _allreduce_(sums, g.world)
+        X = _finalize(route.finalize[l], g, lay, sums, gamma, beta, bn_cfg[l], dev)
+        bump(bn_cfg[l][2])
+        layers.append(lay)
+    return layers, X0, Xrel, pool
+
+
+def _pool_forward(route, g, last, pool, dev):
+    """max-pool over every ball -> (out f32 [B][M][C], its 16-bit twin, the arg-max rows, the selected pre-BN values | None)"""
+    B, M, S = g.B, g.M, g.S
+    out_f32 = torch.empty((B, M, last.C), device=dev, dtype=torch.float32)
+    out_pm = torch.empty((B * M, last.C), device=dev, dtype=E16.dtype)
+    arg = torch.empty((B * M, last.C), device=dev, dtype=torch.uint8)
+    if not route.extrema:
+        _call(_lib.omnipq_sa_pool, last.Y, B, M, S, last.C, _p(last.Y), _p(last.a), _p(last.b), _p(out_f32), _p(out_pm), _p(arg))
+        return out_f32, out_pm, arg, None
+    ysel = torch.empty((B * M, last.C), device=dev, dtype=E16.dtype)
+    if route.finalize[-1] == "pool":
+        fsums, count, pg, pb, peps, pmom, prm, prv, _ = last.fin
+        last.fin = None
+        _call(_lib.omnipq_sa_pool_select_finalize, out_pm, B * M, last.C, _p(pool[1]), _p(pool[2]), _p(pool[3]), _p(pool[4]),
+              _p(fsums), count, _p(pg), _p(pb), peps, pmom, _p(prm), _p(prv), _p(last.a), _p(last.b), _p(last.mean),
+              _p(last.invstd), _p(out_f32), _p(out_pm), _p(arg), _p(ysel))
+    else:
+        _call(_lib.omnipq_sa_pool_select, out_pm, B * M, last.C, _p(pool[1]), _p(pool[2]), _p(pool[3]), _p(pool[4]),
+              _p(last.a), _p(last.b), _p(out_f32), _p(out_pm), _p(arg), _p(ysel))
+    return out_f32, out_pm, arg, ysel
+
+
+# ---- backward steps: ctx is the stage's saved state; the other arguments are what this backward pass has computed so far ----
+
+def _exchanges(world):
+    """the BatchNorm-backward totals are summed over ranks between the statistics and the apply launch"""
+    return world > 1 or _FORCE_COLLECTIVES
+
+
+def _pool_bwd_apply(ctx, g_out, sums, grads):
+    """routes "y" / "ysel": dY of the last layer from the pool's gradient and the totals `sums`, and its affine gradients
+    (dgamma = sum dz * yhat, dbeta = sum dz: LOCAL totals -- DDP averages them -- taken before the all-reduce)"""
+    g, last, i = ctx.geom, ctx.layers[-1], 3 * (len(ctx.layers) - 1)
+    dY = torch.empty_like(last.Y)
+    if _exchanges(g.world):
+        grads[i + 1], grads[i + 2] = affine_grads(sums, last.C)
+        _allreduce_(sums[:2], g.world)
+        _call(_lib.omnipq_sa_pool_bwd_apply, g_out, g.B, g.M, g.S, last.C, float(g.P) * g.world, _p(last.Y), _p(last.a),
+              _p(last.mean), _p(last.invstd), _p(sums), _p(g_out), _p(ctx.out_pm), _p(ctx.arg), _p(dY))
+    else:
+        gb3 = torch.empty((2, last.C), device=dY.device, dtype=torch.float32)      # dbeta | dgamma, written by the apply
+        grads[i + 1], grads[i + 2] = gb3[1], gb3[0]
+        _call(_lib.omnipq_sa_pool_bwd_apply_gb, g_out, g.B, g.M, g.S, last.C, float(g.P) * g.world, _p(last.Y), _p(last.a),
+              _p(last.mean), _p(last.invstd), _p(sums), _p(g_out), _p(ctx.out_pm), _p(ctx.arg), _p(dY), _p(gb3))
+    return dY, None
+
+
+def _last_bwd_from_y(ctx, g_out, grads, dfr):
+    g, last = ctx.geom, ctx.layers[-1]
+    sums = torch.empty((3, last.C), device=g_out.device, dtype=torch.float64)
+    _call(_lib.omnipq_sa_pool_bwd_stats, g_out, g.B, g.M, g.S, last.C, _p(last.Y), _p(last.mean), _p(last.invstd), _p(g_out),
+          _p(ctx.out_pm), _p(ctx.arg), _p(sums))
+    return _pool_bwd_apply(ctx, g_out, sums, grads)
+
+
+def _last_bwd_from_ysel(ctx, g_out, grads, dfr):
+    g, last = ctx.geom, ctx.layers[-1]
+    sums = zeros_f64(3, last.C, g_out.device)                                   # [S | T | scratch], zero from the arena
+    _call(_lib.omnipq_sa_pool_bwd_stats_sel, g_out, g.B * g.M, last.C, _p(ctx.ysel), _p(last.mean), _p(last.invstd), _p(g_out),
+          _p(ctx.out_pm), _p(sums), 1)
+    return _pool_bwd_apply(ctx, g_out, sums, grads)
+
+
+def _last_bwd_no_dy(ctx, g_out, grads, dfr):
+    """route "no_dy" (see LAST_NO_DY).  -> (dX2, the BatchNorm-backward totals of the layer below)"""
+    g, plan, dev = ctx.geom, ctx.plan, g_out.device
+    B, M, S, P, world = g.B, g.M, g.S, g.P, g.world
+    L = len(ctx.layers)
+    last, below = ctx.layers[-1], ctx.layers[-2]
+    C3, C2 = last.C, last.K
+    # the statistics pass also leaves the one-hot operand, from the values it reads anyway
+    sums = zeros_f64(3, C3, dev)
+    hot = torch.empty((B * M, C3), device=dev, dtype=torch.int32)
+    _call(_lib.omnipq_sa_pool_bwd_stats_sel_hot, g_out, B * M, C3, _p(ctx.ysel), _p(last.mean), _p(last.invstd), _p(g_out),
+          _p(ctx.out_pm), _p(sums), 1, _p(last.a), _p(ctx.arg), _p(hot))
+    gb3 = None
+    if _exchanges(world):
+        grads[3 * (L - 1) + 1], grads[3 * (L - 1) + 2] = affine_grads(sums, C3)
+        _allreduce_(sums[:2], world)
+    else:
+        gb3 = torch.empty((2, C3), device=dev, dtype=torch.float32)      # dbeta | dgamma, written by the prep
+        grads[3 * (L - 1) + 1], grads[3 * (L - 1) + 2] = gb3[1], gb3[0]
+    B1 = torch.empty((C2, C2 + 32), device=dev, dtype=E16.dtype)
+    ab = torch.empty((2, C3), device=dev, dtype=torch.float32)          # alpha | beta
+    _call(_lib.omnipq_sa_last_bwd_prep, g_out, B * M, C3, C2, _p(sums), float(P) * world, _p(last.a), _p(last.mean),
+          _p(last.invstd), _p(None), _p(None), _p(None), _p(last.Wt), last.Wt.stride(0), _p(None), _p(B1), C2 + 32, _p(ab[0]),
+          _p(ab[1]), _p(gb3))
+    # the data gradient + the BatchNorm-backward sums of the layer below; X2 = relu(bn2(Y2)) as its first phase forms
+    # it is kept for the weight gradient (LAST_X2: the TN launch is bound by rebuilding X2 in every fragment)
+    want_w = ctx.needs_input_grad[9 + 3 * (L - 1)]
+    X2 = torch.empty((P, C2), device=dev, dtype=E16.dtype) if (want_w and ctx.route.keep_x2) else None
+    pend = zeros_f64(3, below.C, dev)
+    dX2 = torch.empty((P, C2), device=dev, dtype=E16.dtype)
+    ws = _stats_workspace(P, C2, dev)
+    _call(_lib.omnipq_gemm_nt_e16_dz_bnbwd, dX2, P, C2, C3, _p(below.Y), C2, _p(B1), C2 + 32, _p(last.Wt), last.Wt.stride(0),
+          _p(hot), _p(plan.unit_src), S, _p(dX2), C2, _p(below.a), _p(below.b), _p(below.mean), _p(below.invstd), _p(pend),
+          _p(ws), _p(X2))
+    # the layer's weight gradient: from X2 (or Y2) and `hot`, with the other SA stages' when the deferred block ends
+    if want_w:
+        wt = ctx.wtargets[L - 1] if (dfr is not None and SA_WGRADS_GROUPED) else None
+        src, blw = (X2, None) if X2 is not None else (below.Y, below)
+        if wt is not None and wt[0] == "param" and wt[2] == 0 and wt[1].numel() == C3 * C2:
+            dfr.add_dz((src, blw, hot, plan, S, C3, C2, P, ab[0], ab[1], last.Wp), wt, ctx.stage_label)
+        else:
+            grads[3 * (L - 1)] = last_wgrad_dz(src, blw, hot, plan, S, C3, C2, P, ab[0], ab[1], last.Wp).view(C3, C2, 1, 1)
+    return dX2, pend
+
+
+_LAST_BWD = {"y": _last_bwd_from_y, "ysel": _last_bwd_from_ysel, "no_dy": _last_bwd_no_dy}
+
+
+def _layer_wgrad(ctx, l, dY, grads, dfr):
+    """the weight gradient of layer l (not a "source" first layer) from dY = the gradient w.r.t. its pre-BN output: collected
+    for the grouped launch of ALL SA stages when the deferred_wgrads block ends, or launched now"""
+    g, lay = ctx.geom, ctx.layers[l]
+    below = ctx.layers[l - 1] if (l > 0 and ctx.route.feed[l - 1] == "yab") else None
+    Xin = below.Y if below is not None else (ctx.layers[l - 1].X if l > 0 else ctx.X0)
+    wt = ctx.wtargets[l] if (dfr is not None and SA_WGRADS_GROUPED) else None
+    if wt is not None and ctx.needs_input_grad[9 + 3 * l]:
+        if l == 0:
+            dfr.add_sa(dY, Xin, lay.C, lay.K, g.P, wt, (lay.C, g.cin_raw + 3, 3 | (g.cin << 8)), blk=ctx.plan)
+        else:
+            dfr.add_sa(dY, Xin, lay.C, lay.K, g.P, wt, (lay.C, lay.K), below, blk=ctx.plan)
+        return
+    dWp = _gemm_tn(dY, Xin, lay.C, lay.K, g.P, below=below)      # [Cout][K]
+    wk = g.cin + 3 if l == 0 else lay.K
+    grads[3 * l] = unprep_wgrad(dWp, lay.C, wk, 3 if l == 0 else 0, (lay.C, wk, 1, 1))
+    if l == 0 and g.cin_raw != g.cin:
+        grads[0] = grads[0][:, :g.cin_raw + 3].contiguous()       # drop the padded feature columns
+
+
+def _layer_bwd(ctx, l, dY, grads, dfr):
+    """layer l > 0.  -> (the gradient w.r.t. the ReLU output of the layer below, that layer's BatchNorm-backward totals)"""
+    lay, prev = ctx.layers[l], ctx.layers[l - 1]
+    _layer_wgrad(ctx, l, dY, grads, dfr)
+    pend = zeros_f64(3, prev.C, dY.device)
+    # Wt = [K][Cout]; the BN-backward sums of the layer below come out of the same pass
+    return _gemm_nt_bnbwd(dY, lay.Wt, ctx.geom.P, lay.K, lay.C, prev, pend), pend
+
+
+def _tail_grouped(ctx, dY, grads, dfr):
+    """first layer "grouped": its weight gradient, then the rows' gradient summed per source point.  -> (d_xyz, d_cen, d_feat)"""
+    B, N, M, S, P, cin, cin_raw, kpad, inv_r, _ = ctx.geom
+    lay, dev = ctx.layers[0], dY.device
+    _layer_wgrad(ctx, 0, dY, grads, dfr)
+    want_xyz = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+    want_feat = ctx.has_features and ctx.needs_input_grad[2]
+    d_xyz = d_cen = d_feat = None
+    if not (want_xyz or want_feat):
+        return d_xyz, d_cen, d_feat
+    dX = _gemm_nt(dY, lay.Wt, P, lay.K, lay.C)
+    dfeat_pm = torch.empty((B, N, cin), device=dev) if want_feat else None
+    if want_xyz:
+        d_xyz = torch.empty((B, N, 3), device=dev)
+        d_cen = torch.empty((B, M, 3), device=dev)
+    # bucket the positions by source point, then every (point, 8-channel piece) sums its
+    # own bucket: no atomics, each dX row is read exactly once
+    offsets, order = _csr_of(ctx.idx, B, N, M, S, ctx.plan, dX)
+    _call(_lib.omnipq_sa_scatter_csr, dX, B, N, M, S, cin, kpad, inv_r, _p(offsets), _p(order), _p(dX), _p(dfeat_pm), _p(d_xyz),
+          _p(d_cen))
+    if dfeat_pm is not None:
+        d_feat = dfeat_pm[..., :cin_raw].transpose(1, 2).to(ctx.feat_dtype)      # (B, cin, N) view, see forward
+    return d_xyz, d_cen, d_feat
+
+
+def _tail_generated(ctx, dY, grads):
+    """first layer "xyz", reached at layer 1 (dY = the gradient w.r.t. ITS pre-BN output): layer 1's weight gradient contracts
+    against activations rebuilt from the grouped coordinates, and its data-gradient GEMM is reduced to the five column sums
+    the first layer's dW / dgamma / dbeta follow from"""
+    P, world, dev = ctx.geom.P, ctx.geom.world, dY.device
+    prev, lay, X0c = ctx.layers[0], ctx.layers[1], ctx.X0
+    dWp = torch.empty((lay.C, lay.K), device=dev, dtype=torch.float32)
+    ws = torch.empty((int(_lib.omnipq_gemm_tn_workspace_floats(lay.C, lay.K, P)),), device=dev, dtype=torch.float32)
+    _call(_lib.omnipq_gemm_tn_e16_xyz_affine, dY, lay.C, lay.K, P, _p(dY), lay.C, _p(X0c), X0c.shape[1], _p(prev.Wp),
+          prev.Wp.shape[1], _p(prev.a), _p(prev.b), _p(dWp), _p(ws))
+    grads[3] = unprep_wgrad(dWp, lay.C, lay.K, 0, (lay.C, lay.K, 1, 1))
+    sums5 = zeros_f64(5, prev.C, dev)
+    ws5 = torch.empty((int(_lib.omnipq_gemm_nt_xyz_workspace_floats(P, prev.C)),), device=dev, dtype=torch.float32)
+    _call(_lib.omnipq_gemm_nt_e16_xyz_bnbwd, dY, P, prev.C, lay.C, _p(dY), lay.C, _p(lay.Wt), lay.C, _p(X0c), X0c.shape[1],
+          _p(prev.Wp), prev.Wp.shape[1], _p(prev.a), _p(prev.b), _p(prev.mean), _p(prev.invstd), _p(sums5), _p(ws5))
+    grads[1], grads[2] = affine_grads(sums5, prev.C)            # this rank's dgamma / dbeta
+    _allreduce_(sums5[:2], world)
+    dW0 = torch.empty((prev.C, 3, 1, 1), device=dev, dtype=torch.float32)
+    _call(_lib.omnipq_sa_xyz_bwd, dY, prev.C, _p(prev.Wp), prev.Wp.shape[1], _p(prev.mom), _p(sums5), _p(prev.a), _p(prev.mean),
+          _p(prev.invstd), 1.0 / (float(P) * world), _p(dW0))
+    grads[0] = dW0
+
+
+def _tail_on_source(ctx, dY, grads, dfr):
+    """first layer "source" (HOIST_L1): dY = the gradient w.r.t. its pre-BatchNorm output, (rows, C1) 16-bit.  Per-point sums
+    of dY's rows first (CSR, no atomics), then everything is a contraction over the B * N points: dW_f = dZ^T features,
+    d features = dZ W_f; the three coordinate columns of the weight take dW_x = dY^T xrel over the rows.
+    -> (d_xyz, d_cen, d_feat)"""
+    B, N, M, S, P, cin, cin_raw, _, inv_r, _ = ctx.geom
+    feat2d, Xrel = ctx.hoist
+    plan, lay, dev = ctx.plan, ctx.layers[0], dY.device
+    C1 = lay.C
+    want_xyz = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+    want_feat = ctx.has_features and ctx.needs_input_grad[2]
+    want_w = ctx.needs_input_grad[9]
+    d_xyz = d_cen = d_feat = None
+    if not (want_xyz or want_feat or want_w):
+        return d_xyz, d_cen, d_feat
+    offsets, order = _csr_of(ctx.idx, B, N, M, S, plan, dY)
+    dXr = None
+    if want_xyz:
+        # gradient of the relative coordinates: dY W_x (the rows cin .. cin + 7 of the transposed prepared weight: W_x^T | 0)
+        dXr = torch.empty((P, 8), device=dev, dtype=E16.dtype)
+        _call(_lib.omnipq_gemm_nt_e16, dY, P, 8, C1, _p(dY), C1,
+              ctypes.c_void_p(lay.Wt.data_ptr() + cin * C1 * lay.Wt.element_size()), C1, _p(dXr), 8)
+        d_xyz = torch.empty((B, N, 3), device=dev)
+        d_cen = torch.empty((B, M, 3), device=dev)
+    dZ = torch.empty((B * N, C1), device=dev, dtype=E16.dtype)
+    _call(_lib.omnipq_sa_scatter_rows_csr, dY, B, N, M, S, C1, inv_r, _p(offsets), _p(order), _p(dY), _p(dXr),
+          _p(plan.goff if plan is not None else None), plan.gs if plan is not None else 16, _p(None), _p(dZ), _p(d_xyz),
+          _p(d_cen))
+    if want_w:
+        wt = ctx.wtargets[0] if (dfr is not None and SA_WGRADS_GROUPED) else None
+        ld = cin_raw + 3
+        if wt is not None:
+            # the parameter's columns are [xyz(3) | features(cin)] (pointnet2_utils.py:357-359): two problems of the grouped
+            # launch write the two column ranges of one gradient buffer
+            dfr.add_sa(dZ, feat2d, C1, cin, B * N, wt, (C1, cin, 0, 3, ld))
+            dfr.add_sa(dY, Xrel, C1, 8, P, wt, (C1, 3, 0, 0, ld), blk=plan)
+        else:
+            dWf = _gemm_tn(dZ, feat2d, C1, cin, B * N)
+            dWx = _gemm_tn(dY, Xrel, C1, 8, P)              # (inside backward()'s _row_plan block: the rows in use)
+            grads[0] = torch.cat([dWx[:, :3], dWf], 1).view(C1, ld, 1, 1)
+    if want_feat:
+        # d features = dZ W_f: the first cin rows of the transposed prepared weight are W_f^T, K-contiguous over C1
+        dfeat = gemm_nt_f32(dZ, lay.Wt, B * N, cin, C1, C1, C1)
+        d_feat = dfeat.view(B, N, cin).transpose(1, 2).to(ctx.feat_dtype)
+    return d_xyz, d_cen, d_feat
+
+
 class FusedSAStage(torch.autograd.Function):
     """forward(xyz, new_xyz, features|None, idx, radius, normalize_xyz, training, bn_cfg, *params)
 
@@ -1294,14 +1728,17 @@ class FusedSAStage(torch.autograd.Function):
         dev = xyz.device
         B, N, _ = xyz.shape
         M, S = idx.shape[1], idx.shape[2]
-        P = B * M * S
         L = len(params) // 3
         cin_raw = 0 if features is None else features.shape[1]
-        cin = _round_up(cin_raw, 8)       # feature rows are moved in 16-byte pieces: 6 extra input channels (rgb + normals,
-                                          # BASELINE configs[3]) travel as 8, the two extra columns and weight columns zero
-        kpad = _round_up(cin + 3, 32)
-        inv_r = (1.0 / radius) if normalize_xyz else 1.0
-        world = _world() if (training and _SYNC) else 1
+        cin = _round_up(cin_raw, 8)
+        g = _Geom(B, N, M, S, B * M * S, cin, cin_raw, _round_up(cin + 3, 32), (1.0 / radius) if normalize_xyz else 1.0,
+                  _world() if (training and _SYNC) else 1)
+        plan = getattr(idx, "omnipq_plan", None)           # made ahead of the stage (run(group=)), or below
+        route = stage_route(training, B, N, M, S, cin_raw, [params[3 * l].shape[0] for l in range(L)], features is not None,
+                            ctx.needs_input_grad[0] or ctx.needs_input_grad[1],
+                            features is not None and ctx.needs_input_grad[2], None if plan is None else plan.gs,
+                            plan is not None and plan.unit_src is not None)
+        _count_uses(route)
         if features is None:
             feat_pm = None
         elif feat_pm is None or cin != cin_raw:
@@ -1310,419 +1747,65 @@ class FusedSAStage(torch.autograd.Function):
             feat_pm = torch.nn.functional.pad(feat_pm, (0, cin - cin_raw)) if cin != cin_raw else feat_pm.contiguous()
         xyz_c = xyz.detach().contiguous()
         cen_c = new_xyz.detach().contiguous()
-        xgen = training and features is None and xyzgen_ok(
-            P, L, params[0].shape[0], ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) and \
-            affine_pays(P, params[3].shape[0])
-        xpad = 8 if xgen else kpad          # only the coordinates travel: 16 bytes per grouped position
-        if xgen:
-            global xyzgen_uses
-            xyzgen_uses += 1
-        plan = None
-        xyz_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        feat_grad = features is not None and ctx.needs_input_grad[2]
-        if row_plan_ok(training, S, P, L, xyz_grad or (feat_grad and N > 8192), 128 % S == 0):
-            global row_plan_uses
-            row_plan_uses += 1
-            plan = getattr(idx, "omnipq_plan", None)           # made ahead of the stage (run(group=)), or here
-            if plan is None or plan.gs != PLAN_GROUP:
-                plan = make_row_plan(idx, P)
-        ctx.plan = plan
-        ctx.no_dy = False
-        hoist = hoist_ok(training, features, cin, cin_raw, L, params[0].shape[0], xgen) and \
-            (plan is None or not xyz_grad)
-        ctx.hoist = None
-        if hoist:
-            global hoist_uses
-            hoist_uses += 1
-            # (layer 0 of _forward_layers gathers Z rows instead of contracting grouped rows; nothing is gathered here)
-            ctx.hoist = (xyz_c, cen_c, idx, feat_pm.reshape(B * N, cin), N, M, S, inv_r)
-        X = None if hoist else torch.empty((P, xpad), device=dev, dtype=E16.dtype)
-        with _row_plan(plan, P):
-            # (with a plan: the gather writes the compact row space, every launch below works on the rows in use)
-            if not hoist:
-                _call(_lib.omnipq_sa_gather, xyz_c, B, N, M, S, cin, xpad, inv_r, _p(xyz_c), _p(cen_c),
-                      _p(idx), _p(feat_pm), _p(X))
-            X0 = X
-            layers, pool, X = FusedSAStage._forward_layers(ctx, params, bn_cfg, L, X, X0, P, B, M, S, cin, cin_raw, kpad,
-                                                           training, xgen, xpad, world, dev)
-            return FusedSAStage._forward_tail(ctx, layers, pool, X0, xgen, params, L, training, cin_raw, B, N, M, S, P, cin,
-                                              kpad, inv_r, world, idx, features, dev)
-
-    @staticmethod
-    def _forward_layers(ctx, params, bn_cfg, L, X, X0, P, B, M, S, cin, cin_raw, kpad, training, xgen, xpad, world, dev):
-        layers = []
-        pool = None
-        for l in range(L):
-            W, gamma, beta = params[3 * l], params[3 * l + 1], params[3 * l + 2]
-            rm, rv, nbt, momentum, eps = bn_cfg[l]
-            lay = _Layer()
-            W2 = W.detach().reshape(W.shape[0], -1)
-            cout = W2.shape[0]
-            padded_w = l == 0 and cin != cin_raw
-            if padded_w:
-                W2 = torch.nn.functional.pad(W2, (0, cin - cin_raw))     # zero columns for the padded feature channels
-            # the reference concatenates [xyz(3), features(cin)] (pointnet2_utils.py:357-359); the
-            # gathered rows are [features(cin), xyz(3), 0-pad] so that feature pieces stay 16-byte
-            # aligned -- layer 0 rotates the weight columns to match
-            K = kpad if l == 0 else W2.shape[1]
-            lay.K, lay.C = K, cout
-            lay.Wp, lay.Wt = prep_weight(W2, cout, K, rot=3 if l == 0 else 0, transpose=training,
-                                         persistent=is_persistent(W) and not padded_w)
-            if training:
-                sums = zeros_f64(2, cout, dev)
-                pool = None
-                if l == L - 1 and POOL_EPILOGUE and 128 % S == 0 and (X is not None or layers[l - 1].fin is not None):
-                    # the last layer's GEMM also records every ball's extrema: the pooling pass below needs no Y
-                    # (a planned stage records them per group of the compact row space; pool_select merges a ball's)
-                    plan = getattr(ctx, "plan", None)
-                    planned = plan is not None
-                    slots = P // plan.gs if planned else B * M
-                    ext16 = torch.empty((2, slots, cout), device=dev, dtype=E16.dtype)
-                    ext8 = torch.empty((2, slots, cout), device=dev, dtype=torch.uint8)
-                    pool = (plan.gs if planned else S, ext16[0], ext16[1], ext8[0], ext8[1])
-                    if planned and plan.gs == 8 and ONE_SIDED_EXTREMA:
-                        # only the extremum gamma's sign can select is recorded (include/omnipq_sa.h: omnipq_row_plan.pool_gamma)
-                        _plan_pool_gamma(gamma.detach())
-                if xgen and l == 0:
-                    # never materialised (see XYZGEN): statistics from the moments of the grouped coordinates
-                    lay.mom = torch.empty((12,), device=dev, dtype=torch.float64)
-                    _call(_lib.omnipq_sa_xyz_moments, X, P, _p(X), xpad, _p(lay.mom))
-                    _call(_lib.omnipq_sa_xyz_stats, X, cout, _p(lay.Wp), K, _p(lay.mom), _p(sums))
-                    lay.Y = None
-                elif l == 0 and getattr(ctx, "hoist", None) is not None:
-                    hx, hc, hidx, hfeat, hN, hM, hS, hinv = ctx.hoist
-                    Z = gemm_nt_f32(hfeat, lay.Wp, hfeat.shape[0], cout, cin, cin, K)     # W_f = the first cin prepared columns
-
-                    lay.Y = torch.empty((P, cout), device=dev, dtype=E16.dtype)
-                    Xrel = torch.empty((P, 8), device=dev, dtype=E16.dtype)
-                    plan = getattr(ctx, "plan", None)
-                    nws = int(_lib.omnipq_sa_l1_rows_workspace_bytes(B, hM, hS, cout))
-                    ws_ = torch.empty((nws // 4,), device=dev, dtype=torch.float32)
-                    tk_ = zeros_f32(nws // (8 * cout * 16) + 1, dev)          # one zero word per 16 workgroups
-                    _call(_lib.omnipq_sa_l1_rows, Z, B, hN, hM, hS, cout, hinv, _p(hx), _p(hc), _p(hidx), _p(Z),
-                          ctypes.c_void_p(lay.Wp.data_ptr() + cin * lay.Wp.element_size()), K,
-                          _p(plan.rows_dev if plan is not None else None), _p(plan.unit_src if plan is not None else None),
-                          _p(plan.row_w if plan is not None else None), _p(lay.Y), _p(Xrel), _p(sums), _p(ws_), _p(tk_))
-                    ctx.hoist = ctx.hoist + (Xrel,)
-                elif xgen and l == 1:
-                    lay.Y = gemm_nt_xyz(X0, layers[0], lay.Wp, P, cout, K, sums)
-                elif l > 0 and X is None:
-                    # the layer below never stored relu(bn(Y)): this GEMM rebuilds it while staging its operand
-                    nody = l == L - 1 and pool is not None and layers[l - 1].fin is not None and \
-                        last_no_dy_ok(getattr(ctx, "plan", None), L, P, K, cout, S, True)
-                    if nody:
-                        global last_no_dy_uses
-                        last_no_dy_uses += 1
-                        ctx.no_dy = True
-                    lay.Y = gemm_nt_affine(layers[l - 1].Y, layers[l - 1], lay.Wp, P, cout, K, sums=sums, pool=pool,
-                                           store=not nody)
-                else:
-                    lay.Y = _gemm_nt_stats(X, lay.Wp, P, cout, K, sums, pool=pool)     # GEMM + batch statistics
-                _allreduce_(sums, world)
-                stats = torch.empty((4, cout), device=dev)                # a | b | mean | invstd
-                lay.a, lay.b, lay.mean, lay.invstd = stats[0], stats[1], stats[2], stats[3]
-                keep_y_only = l < L - 1 and (affine_pays(P, params[3 * (l + 1)].shape[0]) or (xgen and l == 0))
-                fused_relu = l < L - 1 and not keep_y_only
-                lay.fin = None
-                if keep_y_only:
-                    # finalised inside the prologue of the GEMM that consumes (Y, a, b): see gemm_nt_affine
-                    lay.fin = (sums, float(P) * world, gamma.detach(), beta.detach(), eps, momentum, rm, rv, None)
-                elif fused_relu:
-                    # finalize + normalise + ReLU in one launch
-                    lay.X = torch.empty_like(lay.Y)
-                    _call(_lib.omnipq_bn_finalize_relu, lay.Y, P, cout, float(P) * world,
-                          _p(sums), _p(gamma.detach()), _p(beta.detach()), eps, momentum,
-                          _p(rm), _p(rv), _p(None), _p(lay.Y), _p(lay.X), _p(lay.a), _p(lay.b), _p(lay.mean),
-                          _p(lay.invstd))
-                elif _FOLD_SMALL and l == L - 1 and pool is not None and cout <= 1024:
-                    # the last layer: finalised inside omnipq_sa_pool_select_finalize below
-                    lay.fin = (sums, float(P) * world, gamma.detach(), beta.detach(), eps, momentum, rm, rv, None)
-                else:
-                    _call(_lib.omnipq_bn_finalize, sums, cout, float(P) * world, _p(sums),
-                          _p(gamma.detach()), _p(beta.detach()), eps, momentum,
-                          _p(rm), _p(rv), _p(lay.a), _p(lay.b), _p(lay.mean), _p(lay.invstd), _p(None))
-                bump(nbt)
-            else:
-                fused_relu = False
-                lay.Y = _gemm_nt(X, lay.Wp, P, cout, K)
-                lay.invstd = torch.rsqrt(rv + eps)
-                lay.mean = rm
-                lay.a = (gamma.detach() * lay.invstd).contiguous()
-                lay.b = (beta.detach() - rm * lay.a).contiguous()
-            if l < L - 1 and training and keep_y_only:
-                lay.X = X = None            # consumers take (Y, a, b)
-            elif l < L - 1:
-                if not fused_relu:
-                    lay.X = torch.empty_like(lay.Y)
-                    _call(_lib.omnipq_bnrelu, lay.Y, P, cout, _p(lay.Y), _p(lay.a), _p(lay.b),
-                          _p(lay.X))
-                X = lay.X
-            else:
-                lay.X = None
-            layers.append(lay)
-        return layers, pool, X
-
-    @staticmethod
-    def _forward_tail(ctx, layers, pool, X0, xgen, params, L, training, cin_raw, B, N, M, S, P, cin, kpad, inv_r, world, idx,
-                      features, dev):
-        last = layers[-1]
-        out_f32 = torch.empty((B, M, last.C), device=dev, dtype=torch.float32)
-        out_pm = torch.empty((B * M, last.C), device=dev, dtype=E16.dtype)
-        arg = torch.empty((B * M, last.C), device=dev, dtype=torch.uint8)
-        ysel = None
-        if training and pool is not None:
-            ysel = torch.empty((B * M, last.C), device=dev, dtype=E16.dtype)
-            if last.fin is not None:
-                fsums, count, pg, pb, peps, pmom, prm, prv, _ = last.fin
-                last.fin = None
-                _call(_lib.omnipq_sa_pool_select_finalize, out_pm, B * M, last.C, _p(pool[1]), _p(pool[2]),
-                      _p(pool[3]), _p(pool[4]), _p(fsums), count, _p(pg), _p(pb), peps,
-                      pmom, _p(prm), _p(prv), _p(last.a), _p(last.b), _p(last.mean), _p(last.invstd),
-                      _p(out_f32), _p(out_pm), _p(arg), _p(ysel))
-            else:
-                _call(_lib.omnipq_sa_pool_select, out_pm, B * M, last.C, _p(pool[1]), _p(pool[2]),
-                      _p(pool[3]), _p(pool[4]), _p(last.a), _p(last.b), _p(out_f32), _p(out_pm), _p(arg), _p(ysel))
-        else:
-            _call(_lib.omnipq_sa_pool, last.Y, B, M, S, last.C, _p(last.Y), _p(last.a), _p(last.b), _p(out_f32),
-                  _p(out_pm), _p(arg))
-        # reference layout (B, C, M) as a VIEW of the position-major result: values, shape and dtype are
-        # the reference's, only the strides differ (no transpose pass; every consumer on this path
-        # either accepts strides or wants the position-major form back)
-        out = out_f32.transpose(1, 2)
-
-        ctx.layers = layers
-        ctx.X0 = X0
-        ctx.xgen = xgen
+        if not route.plan_gs:
+            plan = None
+        elif not route.plan_arrives:
+            plan = make_row_plan(idx, g.P)
+        with _row_plan(plan, g.P):
+            layers, X0, Xrel, pool = _forward_layers(route, g, plan, xyz_c, cen_c, idx, feat_pm, params, bn_cfg, dev)
+            out_f32, out_pm, arg, ysel = _pool_forward(route, g, layers[-1], pool, dev)
+        ctx.route, ctx.geom, ctx.plan = route, g, plan
+        ctx.layers, ctx.X0 = layers, X0
+        ctx.hoist = (feat_pm.reshape(B * N, cin), Xrel) if route.first == "source" else None
         # where a layer's weight gradient may be written behind autograd's back (deferred_wgrads): Parameters only
         ctx.wtargets = [grad_target(params[3 * l]) for l in range(L)] if training else None
-        ctx.cin_raw = cin_raw
-        ctx.geom = (B, N, M, S, P, cin, kpad, inv_r, world)
         ctx.idx = idx
         ctx.out_pm, ctx.arg, ctx.ysel = out_pm, arg, ysel
         ctx.has_features = features is not None
         ctx.feat_dtype = features.dtype if features is not None else None
         ctx.training = training
-        twin = out_pm.view(B, M, last.C)
+        twin = out_pm.view(B, M, layers[-1].C)
         ctx.mark_non_differentiable(twin)
         ctx.set_materialize_grads(False)        # no zero tensor of the twin's size per backward (its gradient is never used)
-        return out, twin
+        # reference layout (B, C, M) as a VIEW of the position-major result: values, shape and dtype are
+        # the reference's, only the strides differ (no transpose pass; every consumer on this path
+        # either accepts strides or wants the position-major form back)
+        return out_f32.transpose(1, 2), twin
 
     @staticmethod
     def backward(ctx, g_out, _g_twin=None):
         E16.select(ctx.e16)
         if g_out is None:                       # the stage's output took no part in the loss
             return (None,) * ctx.n_inputs
-        with _tagged("@sa", getattr(ctx, "stage_label", None)), _row_plan(getattr(ctx, "plan", None), ctx.geom[4]):
+        with _tagged("@sa", ctx.stage_label), _row_plan(ctx.plan, ctx.geom.P):
             return FusedSAStage._backward(ctx, g_out)
 
     @staticmethod
     def _backward(ctx, g_out):
         if not ctx.training:
             raise RuntimeError("FusedSAStage: backward in eval mode is not supported (use the composed path)")
-        B, N, M, S, P, cin, kpad, inv_r, world = ctx.geom
-        layers = ctx.layers
+        route, g, layers = ctx.route, ctx.geom, ctx.layers
         L = len(layers)
-        dev = g_out.device
         g_out = g_out.float().transpose(1, 2).contiguous()      # position-major [B*M][C] (no-op for a view)
-        total = float(P) * world
         grads = [None] * (3 * L)
-
-        last = layers[-1]
-        hot = None
-        if ctx.ysel is not None and getattr(ctx, "no_dy", False):
-            # ... and the one-hot operand of the backward without dY (LAST_NO_DY), from the values this pass reads anyway
-            sums = zeros_f64(3, last.C, dev)
-            hot = torch.empty((B * M, last.C), device=dev, dtype=torch.int32)
-            _call(_lib.omnipq_sa_pool_bwd_stats_sel_hot, g_out, B * M, last.C, _p(ctx.ysel), _p(last.mean),
-                  _p(last.invstd), _p(g_out), _p(ctx.out_pm), _p(sums), 1, _p(last.a), _p(ctx.arg), _p(hot))
-        elif ctx.ysel is not None:
-            sums = zeros_f64(3, last.C, dev)                                     # [S | T | scratch], zero from the arena
-            _call(_lib.omnipq_sa_pool_bwd_stats_sel, g_out, B * M, last.C, _p(ctx.ysel), _p(last.mean),
-                  _p(last.invstd), _p(g_out), _p(ctx.out_pm), _p(sums), 1)
-        else:
-            sums = torch.empty((3, last.C), device=dev, dtype=torch.float64)
-            _call(_lib.omnipq_sa_pool_bwd_stats, g_out, B, M, S, last.C, _p(last.Y), _p(last.mean), _p(last.invstd),
-                  _p(g_out), _p(ctx.out_pm), _p(ctx.arg), _p(sums))
-        # dgamma = sum dz * yhat, dbeta = sum dz: LOCAL totals (DDP averages them), taken before the all-reduce
-        no_dy = getattr(ctx, "no_dy", False)
-        dY = None if no_dy else torch.empty_like(last.Y)
-        if no_dy:
-            below = layers[L - 2]
-            C3, C2 = last.C, last.K
-            plan = ctx.plan
-            gb3 = None
-            if world > 1 or _FORCE_COLLECTIVES:
-                grads[3 * (L - 1) + 1], grads[3 * (L - 1) + 2] = affine_grads(sums, C3)
-                _allreduce_(sums[:2], world)
-            else:
-                gb3 = torch.empty((2, C3), device=dev, dtype=torch.float32)      # dbeta | dgamma, written by the prep
-                grads[3 * (L - 1) + 1], grads[3 * (L - 1) + 2] = gb3[1], gb3[0]
-            B1 = torch.empty((C2, C2 + 32), device=dev, dtype=E16.dtype)
-            ab = torch.empty((2, C3), device=dev, dtype=torch.float32)          # alpha | beta
-            _call(_lib.omnipq_sa_last_bwd_prep, g_out, B * M, C3, C2, _p(sums), total, _p(last.a),
-                  _p(last.mean), _p(last.invstd), _p(None), _p(None), _p(None), _p(last.Wt), last.Wt.stride(0),
-                  _p(None), _p(B1), C2 + 32, _p(ab[0]), _p(ab[1]), _p(gb3))
-            # the data gradient + the BatchNorm-backward sums of the layer below; X2 = relu(bn2(Y2)) as its first phase forms
-            # it is kept for the weight gradient (LAST_X2: the TN launch is bound by rebuilding X2 in every fragment)
-            want_w = ctx.needs_input_grad[9 + 3 * (L - 1)]
-            X2 = torch.empty((P, C2), device=dev, dtype=E16.dtype) if (want_w and LAST_X2) else None
-            pend0 = zeros_f64(3, below.C, dev)
-            dX2 = torch.empty((P, C2), device=dev, dtype=E16.dtype)
-            ws = _stats_workspace(P, C2, dev)
-            _call(_lib.omnipq_gemm_nt_e16_dz_bnbwd, dX2, P, C2, C3, _p(below.Y), C2, _p(B1), C2 + 32, _p(last.Wt),
-                  last.Wt.stride(0), _p(hot), _p(plan.unit_src), S, _p(dX2), C2, _p(below.a), _p(below.b), _p(below.mean),
-                  _p(below.invstd), _p(pend0), _p(ws), _p(X2))
-            # the layer's weight gradient: from X2 (or Y2) and `hot`, with the other SA stages' when the deferred block ends
-            dfr = deferred_wgrads.active
-            wt = ctx.wtargets[L - 1] if (dfr is not None and SA_WGRADS_GROUPED) else None
-            if want_w:
-                src, blw = (X2, None) if X2 is not None else (below.Y, below)
-                if wt is not None and wt[0] == "param" and wt[2] == 0 and wt[1].numel() == C3 * C2:
-                    dfr.add_dz((src, blw, hot, plan, S, C3, C2, P, ab[0], ab[1], last.Wp), wt, ctx.stage_label)
-                else:
-                    grads[3 * (L - 1)] = last_wgrad_dz(src, blw, hot, plan, S, C3, C2, P, ab[0], ab[1],
-                                                       last.Wp).view(C3, C2, 1, 1)
-        elif world > 1 or _FORCE_COLLECTIVES or not _FOLD_SMALL:
-            grads[3 * (L - 1) + 1], grads[3 * (L - 1) + 2] = affine_grads(sums, last.C)
-            _allreduce_(sums[:2], world)
-            _call(_lib.omnipq_sa_pool_bwd_apply, g_out, B, M, S, last.C, total, _p(last.Y), _p(last.a), _p(last.mean),
-                  _p(last.invstd), _p(sums), _p(g_out), _p(ctx.out_pm), _p(ctx.arg), _p(dY))
-        else:
-            gb3 = torch.empty((2, last.C), device=dev, dtype=torch.float32)      # dbeta | dgamma, written by the apply
-            grads[3 * (L - 1) + 1], grads[3 * (L - 1) + 2] = gb3[1], gb3[0]
-            _call(_lib.omnipq_sa_pool_bwd_apply_gb, g_out, B, M, S, last.C, total, _p(last.Y), _p(last.a), _p(last.mean),
-                  _p(last.invstd), _p(sums), _p(g_out), _p(ctx.out_pm), _p(ctx.arg), _p(dY), _p(gb3))
-
-        d_feat = d_xyz = d_cen = None
-        need_in = ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or (ctx.has_features and ctx.needs_input_grad[2])
-        xgen = getattr(ctx, "xgen", False)
         dfr = deferred_wgrads.active
-        pend = None                  # BatchNorm-backward totals of layer l when `dY` still holds dX (gradient w.r.t. its ReLU output)
-        if no_dy:
-            dY, pend = dX2, pend0        # the last layer is done: the loop starts at the layer below
-        for l in range(L - 2 if no_dy else L - 1, -1, -1):
-            lay = layers[l]
+        d_xyz = d_cen = d_feat = None
+        # dY: the gradient w.r.t. layer l's pre-BN output -- or, while `pend` holds that layer's BatchNorm-backward totals,
+        # still the gradient w.r.t. its ReLU output
+        dY, pend = _LAST_BWD[route.last](ctx, g_out, grads, dfr)
+        for l in range(L - 2 if route.last == "no_dy" else L - 1, -1, -1):
             if pend is not None:
-                grads[3 * l + 1], grads[3 * l + 2] = bn_backward_apply(dY, lay, P, lay.C, total, pend, world)
-                pend = None
-            if l == 1 and xgen:
-                # the layer below is the never-materialised first layer (see XYZGEN): this layer's weight gradient
-                # contracts against activations rebuilt from the grouped coordinates, and the data-gradient GEMM is
-                # reduced to the five column sums the first layer's dW / dgamma / dbeta follow from
-                prev = layers[0]
-                X0c = ctx.X0
-                dWp = torch.empty((lay.C, lay.K), device=dev, dtype=torch.float32)
-                ws = torch.empty((int(_lib.omnipq_gemm_tn_workspace_floats(lay.C, lay.K, P)),), device=dev,
-                                 dtype=torch.float32)
-                _call(_lib.omnipq_gemm_tn_e16_xyz_affine, dY, lay.C, lay.K, P, _p(dY), lay.C, _p(X0c), X0c.shape[1],
-                      _p(prev.Wp), prev.Wp.shape[1], _p(prev.a), _p(prev.b), _p(dWp), _p(ws))
-                grads[3] = unprep_wgrad(dWp, lay.C, lay.K, 0, (lay.C, lay.K, 1, 1))
-                sums5 = zeros_f64(5, prev.C, dev)
-                ws5 = torch.empty((int(_lib.omnipq_gemm_nt_xyz_workspace_floats(P, prev.C)),), device=dev,
-                                  dtype=torch.float32)
-                _call(_lib.omnipq_gemm_nt_e16_xyz_bnbwd, dY, P, prev.C, lay.C, _p(dY), lay.C, _p(lay.Wt), lay.C, _p(X0c),
-                      X0c.shape[1], _p(prev.Wp), prev.Wp.shape[1], _p(prev.a), _p(prev.b), _p(prev.mean), _p(prev.invstd),
-                      _p(sums5), _p(ws5))
-                grads[1], grads[2] = affine_grads(sums5, prev.C)            # this rank's dgamma / dbeta
-                _allreduce_(sums5[:2], world)
-                dW0 = torch.empty((prev.C, 3, 1, 1), device=dev, dtype=torch.float32)
-                _call(_lib.omnipq_sa_xyz_bwd, dY, prev.C, _p(prev.Wp), prev.Wp.shape[1], _p(prev.mom), _p(sums5), _p(prev.a),
-                      _p(prev.mean), _p(prev.invstd), 1.0 / (float(P) * world), _p(dW0))
-                grads[0] = dW0
+                grads[3 * l + 1], grads[3 * l + 2] = bn_backward_apply(dY, layers[l], g.P, layers[l].C, float(g.P) * g.world,
+                                                                       pend, g.world)
+            if l == 1 and route.first == "xyz":
+                _tail_generated(ctx, dY, grads)
                 break
-            if l == 0 and getattr(ctx, "hoist", None) is not None:
-                d_xyz, d_cen, d_feat = FusedSAStage._backward_hoisted(ctx, dY, lay, grads, dfr, dev)
+            if l == 0:
+                d_xyz, d_cen, d_feat = (_tail_on_source if route.first == "source" else _tail_grouped)(ctx, dY, grads, dfr)
                 break
-            below = layers[l - 1] if (l > 0 and layers[l - 1].X is None) else None
-            Xin = below.Y if below is not None else (layers[l - 1].X if l > 0 else ctx.X0)
-            wt = ctx.wtargets[l] if (dfr is not None and SA_WGRADS_GROUPED) else None
-            if wt is not None and ctx.needs_input_grad[9 + 3 * l]:
-                # collected: one grouped launch for the layers of ALL SA stages when the deferred_wgrads block ends
-                blk = ctx.plan if getattr(ctx, "plan", None) is not None else None
-                if l == 0:
-                    dfr.add_sa(dY, Xin, lay.C, lay.K, P, wt, (lay.C, ctx.cin_raw + 3, 3 | (cin << 8)), blk=blk)
-                else:
-                    dfr.add_sa(dY, Xin, lay.C, lay.K, P, wt, (lay.C, lay.K), below, blk=blk)
-            else:
-                dWp = _gemm_tn(dY, Xin, lay.C, lay.K, P, below=below)      # [Cout][K]
-                wk = cin + 3 if l == 0 else lay.K
-                grads[3 * l] = unprep_wgrad(dWp, lay.C, wk, 3 if l == 0 else 0, (lay.C, wk, 1, 1))
-                if l == 0 and ctx.cin_raw != cin:
-                    grads[0] = grads[0][:, :ctx.cin_raw + 3].contiguous()       # drop the padded feature columns
-            if l == 0 and not need_in:
-                break
-            if l > 0:
-                prev = layers[l - 1]
-                pend = zeros_f64(3, prev.C, dev)
-                # Wt = [K][Cout]; the BN-backward sums of the layer below come out of the same pass
-                dY = _gemm_nt_bnbwd(dY, lay.Wt, P, lay.K, lay.C, prev, pend)
-            else:
-                dX = _gemm_nt(dY, lay.Wt, P, lay.K, lay.C)
-                want_xyz = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-                dfeat_pm = torch.empty((B, N, cin), device=dev) if (ctx.has_features and ctx.needs_input_grad[2]) \
-                    else None
-                if want_xyz:
-                    d_xyz = torch.empty((B, N, 3), device=dev)
-                    d_cen = torch.empty((B, M, 3), device=dev)
-                # bucket the positions by source point, then every (point, 8-channel piece) sums its
-                # own bucket: no atomics, each dX row is read exactly once
-                offsets, order = _csr_of(ctx.idx, B, N, M, S, getattr(ctx, "plan", None), dX)
-                _call(_lib.omnipq_sa_scatter_csr, dX, B, N, M, S, cin, kpad, inv_r, _p(offsets),
-                      _p(order), _p(dX), _p(dfeat_pm), _p(d_xyz), _p(d_cen))
-                if dfeat_pm is not None:
-                    d_feat = dfeat_pm[..., :ctx.cin_raw].transpose(1, 2).to(ctx.feat_dtype)      # (B, cin, N) view, see forward
+            dY, pend = _layer_bwd(ctx, l, dY, grads, dfr)
         ctx.layers = None
         return (d_xyz, d_cen, d_feat, None, None, None, None, None, None, *grads)
-
-
-def _backward_hoisted(ctx, dY, lay, grads, dfr, dev):
-    """Layer 0 of a stage whose first layer ran on the source points (HOIST_L1): dY = the gradient w.r.t. its pre-BatchNorm
-    output, (rows, C1) 16-bit.  Per-point sums of dY's rows first (CSR, no atomics), then everything is a contraction over
-    the B * N points: dW_f = dZ^T features, d features = dZ W_f; the three coordinate columns of the weight take
-    dW_x = dY^T xrel over the rows.  -> (d_xyz, d_cen, d_feat)"""
-    B, N, M, S, P, cin, kpad, inv_r, world = ctx.geom
-    xyz_c, cen_c, idx, feat2d, _, _, _, _, Xrel = ctx.hoist
-    plan = getattr(ctx, "plan", None)
-    C1 = lay.C
-    want_xyz = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-    want_feat = ctx.has_features and ctx.needs_input_grad[2]
-    want_w = ctx.needs_input_grad[9]
-    d_xyz = d_cen = d_feat = None
-    if not (want_xyz or want_feat or want_w):
-        return d_xyz, d_cen, d_feat
-    offsets, order = _csr_of(idx, B, N, M, S, plan, dY)
-    dXr = None
-    if want_xyz:
-        # gradient of the relative coordinates: dY W_x (the rows cin .. cin + 7 of the transposed prepared weight: W_x^T | 0)
-        dXr = torch.empty((P, 8), device=dev, dtype=E16.dtype)
-        _call(_lib.omnipq_gemm_nt_e16, dY, P, 8, C1, _p(dY), C1,
-              ctypes.c_void_p(lay.Wt.data_ptr() + cin * C1 * lay.Wt.element_size()), C1, _p(dXr), 8)
-        d_xyz = torch.empty((B, N, 3), device=dev)
-        d_cen = torch.empty((B, M, 3), device=dev)
-    dZ = torch.empty((B * N, C1), device=dev, dtype=E16.dtype)
-    _call(_lib.omnipq_sa_scatter_rows_csr, dY, B, N, M, S, C1, inv_r, _p(offsets), _p(order), _p(dY), _p(dXr),
-          _p(plan.goff if plan is not None else None), plan.gs if plan is not None else 16, _p(None), _p(dZ), _p(d_xyz),
-          _p(d_cen))
-    if want_w:
-        wt = ctx.wtargets[0] if (dfr is not None and SA_WGRADS_GROUPED) else None
-        ld = ctx.cin_raw + 3
-        if wt is not None:
-            # the parameter's columns are [xyz(3) | features(cin)] (pointnet2_utils.py:357-359): two problems of the grouped
-            # launch write the two column ranges of one gradient buffer
-            dfr.add_sa(dZ, feat2d, C1, cin, B * N, wt, (C1, cin, 0, 3, ld))
-            dfr.add_sa(dY, Xrel, C1, 8, P, wt, (C1, 3, 0, 0, ld), blk=plan)
-        else:
-            dWf = _gemm_tn(dZ, feat2d, C1, cin, B * N)
-            dWx = _gemm_tn(dY, Xrel, C1, 8, P)              # (inside backward()'s _row_plan block: the rows in use)
-            grads[0] = torch.cat([dWx[:, :3], dWf], 1).view(C1, ld, 1, 1)
-    if want_feat:
-        # d features = dZ W_f: the first cin rows of the transposed prepared weight are W_f^T, K-contiguous over C1
-        dfeat = gemm_nt_f32(dZ, lay.Wt, B * N, cin, C1, C1, C1)
-        d_feat = dfeat.view(B, N, cin).transpose(1, 2).to(ctx.feat_dtype)
-    return d_xyz, d_cen, d_feat
-
-
-FusedSAStage._backward_hoisted = staticmethod(_backward_hoisted)
 
 
 def _bn_of(layer):

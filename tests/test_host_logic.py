@@ -180,6 +180,86 @@ def test_last_layer_without_dy_needs_the_row_count_the_c_side_accepts(built_lib)
     assert sa_fused.last_no_dy_ok(plan, 3, 16384, 128, 256, 32, True)
 
 
+def test_stage_route_of_the_benchmark_model_and_its_edges(built_lib, monkeypatch):
+    """sa_fused.stage_route decides every route of a fused SA stage from shapes alone, before anything is launched.  The five
+    stages of the model at BASELINE configs[1] (B = 8, width 2, training, one rank, no gradient into the input cloud), the
+    edges of each predicate, and every switch in its off position: exactly the routes whose predicate names it turn off."""
+    import sa_fused
+    # name: (N, M, S, cin_raw, widths, features, xyz_grad, feat_grad)
+    model = {"sa1": (40000, 2048, 64, 0, (128, 128, 256), False, False, False),
+             "sa2": (2048, 1024, 32, 256, (256, 256, 512), True, False, True),
+             "sa3": (1024, 512, 16, 512, (256, 256, 512), True, False, True),
+             "sa4": (512, 256, 16, 512, (256, 256, 512), True, False, True),
+             "vote": (1024, 256, 16, 288, (288, 288, 288), True, True, True)}
+
+    def route(stage, B=8, training=True, **kw):
+        N, M, S, cin_raw, widths, feats, xyz_grad, feat_grad = model[stage]
+        a = dict(N=N, cin_raw=cin_raw, has_features=feats, xyz_grad=xyz_grad, feat_grad=feat_grad)
+        a.update(kw)
+        return sa_fused.stage_route(training, B, a["N"], M, S, a["cin_raw"], widths, a["has_features"], a["xyz_grad"],
+                                    a["feat_grad"])
+
+    want = {"sa1": ("xyz", 8, "one", "no_dy"), "sa2": ("source", 8, "one", "ysel"), "sa3": ("source", 0, "both", "ysel"),
+            "sa4": ("source", 0, "both", "ysel"), "vote": ("source", 0, "both", "ysel")}
+    base = {s: route(s) for s in model}
+    for s, r in base.items():
+        assert (r.first, r.plan_gs, r.extrema, r.last) == want[s], (s, r)
+        assert r.training and not r.plan_arrives and r.keep_x2 == (r.last == "no_dy")
+        assert r.feed == ("yab", "yab") and r.finalize == ("consumer", "consumer", "pool"), (s, r)
+    # the planning threshold: sa2 has P = 2^17 rows at batch 4
+    assert route("sa2", B=4).plan_gs == 8 and route("sa2", B=2).plan_gs == 0
+    r = route("sa1", cin_raw=6, has_features=True)
+    assert (r.first, r.plan_gs, r.last) == ("grouped", 8, "no_dy")
+    r = route("sa1", xyz_grad=True)
+    assert (r.first, r.plan_gs, r.last) == ("grouped", 0, "ysel")
+    assert route("sa2", N=16384).plan_gs == 0 and route("sa2", N=8192).plan_gs == 8
+    # a plan that arrives with idx is used if its groups are PLAN_GROUP rows; without a unit map the last layer keeps dY
+    N, M, S, cin_raw, widths = model["sa1"][:5]
+    assert sa_fused.stage_route(True, 8, N, M, S, 0, widths, False, False, False, 8, True)[2:4] == (8, True)
+    assert sa_fused.stage_route(True, 8, N, M, S, 0, widths, False, False, False, 8, True).last == "no_dy"
+    assert sa_fused.stage_route(True, 8, N, M, S, 0, widths, False, False, False, 8, False).last == "ysel"
+    assert sa_fused.stage_route(True, 8, N, M, S, 0, widths, False, False, False, 16, False)[2:4] == (8, False)
+    # eval mode: the stored dataflow, nothing else
+    stored = sa_fused.StageRoute(False, "grouped", 0, False, ("stored", "stored"), ("running",) * 3, "", "y", False)
+    assert all(route(s, training=False) == stored for s in model)
+    # P = 8192 rows take the statistics straight to atomics: the last layer keeps dY even with a plan (PLAN_MIN_ROWS lowered)
+    monkeypatch.setattr(sa_fused, "PLAN_MIN_ROWS", 8192)
+    r = sa_fused.stage_route(True, 1, 8192, 128, 64, 0, (128, 128, 256), False, False, False)
+    assert (r.plan_gs, r.last) == (8, "ysel")
+    assert sa_fused.stage_route(True, 2, 8192, 128, 64, 0, (128, 128, 256), False, False, False).last == "no_dy"
+    monkeypatch.undo()
+
+    def switched(name, value=False):
+        monkeypatch.setattr(sa_fused, name, value)
+        got = {s: route(s) for s in model}
+        monkeypatch.undo()
+        return got
+
+    for s, r in switched("XYZGEN").items():
+        assert r == (base[s]._replace(first="grouped") if s == "sa1" else base[s]), s
+    for s, r in switched("HOIST_L1").items():
+        assert r == (base[s] if s == "sa1" else base[s]._replace(first="grouped")), s
+    for s, r in switched("ROW_PLAN").items():
+        assert r == base[s]._replace(plan_gs=0, extrema="both", last="ysel", keep_x2=False), s
+    for s, r in switched("LAST_NO_DY").items():
+        assert r == base[s]._replace(last="ysel", keep_x2=False), s
+    for s, r in switched("LAST_X2").items():
+        assert r == base[s]._replace(keep_x2=False), s
+    for s, r in switched("ONE_SIDED_EXTREMA").items():
+        assert r == base[s]._replace(extrema="both"), s
+    # AFFINE_OPERANDS is named by every predicate: what is left is the stored dataflow with the extrema in the last GEMM
+    for s, r in switched("AFFINE_OPERANDS").items():
+        assert r == sa_fused.StageRoute(True, "grouped", 0, False, ("stored", "stored"), ("relu", "relu", "pool"), "both", "ysel",
+                                        False), s
+    for s, r in switched("PLAN_GROUP", 16).items():
+        assert r == (base[s]._replace(plan_gs=16, extrema="both") if base[s].plan_gs else base[s]), s
+    for s, r in switched("LAST_NO_DY_MAX_C3", 1 << 30).items():
+        assert r == (base[s]._replace(last="no_dy", keep_x2=True) if s == "sa2" else base[s]), s
+    for s, r in switched("POOL_EPILOGUE").items():
+        assert r == base[s]._replace(plan_gs=0, finalize=("consumer", "consumer", "launch"), extrema="", last="y",
+                                     keep_x2=False), s
+
+
 def test_bench_labels_committed_counter_figures_taken_on_other_kernel_sources():
     """bench.py reads HBM traffic / MFMA-busy from the counter summaries under profiles/; each carries the digest of the
     kernel sources it was measured on, and a figure from other sources is labelled stale in the JSON line."""
