@@ -7,6 +7,8 @@
  *   strides[8]      = {q_tok, q_batch, k_tok, k_batch, v_tok, v_batch, o_tok, o_batch}  (elements, % 4 == 0;
  *                     dO uses o's strides)
  *   grad_strides[6] = {dq_tok, dq_batch, dk_tok, dk_batch, dv_tok, dv_batch}
+ * Token strides (strides[0, 2, 4, 6], grad_strides[0, 2, 4]) must not be negative: OMNIPQ_EINVAL, before any launch.  The
+ * kernels bound every read by the slice's extent computed from the token stride; a negative one has no such extent.
  * L query tokens, S key tokens, N batch, H heads, D head channels (D % 4 == 0, D <= 48).
  * lse2[N*H][L] (f32): log2 of the softmax denominator in the log2 domain, saved by forward for backward.
  * delta[N*H][L] (f32): backward scratch.

@@ -615,6 +615,19 @@ __global__ void attn_mask_kernel(AttnArgs g, unsigned char *__restrict__ mask) {
 
 static int g_attn_xcd_map = 1;     // omnipq_attn_block_map
 
+// Token strides (every second entry of `strides`, n of them) as the descriptors need them: not negative -- att_rsrc's
+// num_records = ((T - 1 - t0) * stride + D) * 2 would come out negative, which the hardware reads as a huge unsigned range,
+// i.e. no bounds check at all -- and small enough for 32-bit byte offsets.  A zero stride (every token the same row) is fine.
+static int token_strides_ok(const long long *strides, int n, int L, int S, int D) {
+  const long long tok = L > S ? L : S;
+  for (int i = 0; i < 2 * n; i += 2) {
+    const long long sl = strides[i];
+    if (sl < 0) return OMNIPQ_EINVAL;
+    if (((tok - 1) * sl + D) * 2 >= (1ll << 31) || 32 * sl * 2 >= (1ll << 31)) return OMNIPQ_ETOOLARGE;
+  }
+  return OMNIPQ_OK;
+}
+
 static int fill_args(AttnArgs &g, int N, int H, int L, int S, int D, const long long *strides, float dropout_p,
                      const unsigned long long *seed_ptr, unsigned salt) {
   if (N <= 0 || H <= 0 || L <= 0 || S <= 0 || D <= 0 || (D % 4) || D > ATT_DMAX) return OMNIPQ_EINVAL;
@@ -624,11 +637,8 @@ static int fill_args(AttnArgs &g, int N, int H, int L, int S, int D, const long 
     if (strides[i] % 4) return OMNIPQ_EINVAL;
   // the kernels address a (batch, head) slice through a buffer descriptor: 32-bit byte offsets, num_records an int
   {
-    const long long tok = L > S ? L : S;
-    for (int i = 0; i < 8; i += 2) {
-      const long long sl = strides[i] < 0 ? -strides[i] : strides[i];
-      if (((tok - 1) * sl + D) * 2 >= (1ll << 31) || 32 * sl * 2 >= (1ll << 31)) return OMNIPQ_ETOOLARGE;
-    }
+    const int rc = token_strides_ok(strides, 4, L, S, D);
+    if (rc) return rc;
   }
   g.N = N, g.H = H, g.L = L, g.S = S, g.D = D;
   g.q_sl = strides[0], g.q_sn = strides[1], g.k_sl = strides[2], g.k_sn = strides[3];
@@ -675,11 +685,7 @@ extern "C" int omnipq_attn_bwd(int N, int H, int L, int S, int D, const void *q,
   if (rc) return rc;
   for (int i = 0; i < 6; ++i)
     if (grad_strides[i] % 4) return OMNIPQ_EINVAL;
-  for (int i = 0; i < 6; i += 2) {
-    const long long sl = grad_strides[i] < 0 ? -grad_strides[i] : grad_strides[i];
-    const long long tok = L > S ? L : S;
-    if (((tok - 1) * sl + D) * 2 >= (1ll << 31) || 32 * sl * 2 >= (1ll << 31)) return OMNIPQ_ETOOLARGE;
-  }
+  if (const int rs = token_strides_ok(grad_strides, 3, L, S, D)) return rs;
   attn_bwd_dq_kernel<<<dim3((L + 31) / 32, N * H), 256, 0, (hipStream_t)stream>>>(
       g, (const e16_t *)q, (const e16_t *)k, (const e16_t *)v, (const e16_t *)o, (const e16_t *)d_o, lse2, delta,
       (e16_t *)dq, grad_strides[0], grad_strides[1]);

@@ -204,6 +204,30 @@ def test_argument_validation_needs_no_gpu(built_lib):
     assert lib.omnipq_attn_fwd(8, 8, 256, 256, 36, p, p, p, p, strides, p, f(1.0), p, 0, null) == EINVAL
     assert lib.omnipq_attn_fwd(8, 8, 256, 256, 36, p, p, p, p, strides, p, f(0.1), null, 0, null) == EINVAL   # no seed
     assert lib.omnipq_attn_fwd(64, 16, 4096, 4096, 36, p, p, p, p, strides, p, f(0.0), null, 0, null) == ETOOLARGE
+    # a negative token stride has no extent to bound the kernels' reads by (att_rsrc: num_records would be negative, which the
+    # hardware takes for no bound at all): refused by forward and backward, for every tensor, before any launch
+    good = [288, 2304, 288, 2304, 288, 2304, 288, 2304]
+    ggood = [288, 2304, 288, 2304, 288, 2304]
+
+    def bwd(st, gst):
+        return lib.omnipq_attn_bwd(8, 8, 256, 256, 36, p, p, p, p, p, (ll * 8)(*st), p, p, p, p, p, (ll * 6)(*gst), f(0.0),
+                                   null, 0, null)
+
+    for i in (0, 2, 4, 6):
+        for bad in (-288, -4):
+            st = list(good)
+            st[i] = bad
+            assert lib.omnipq_attn_fwd(8, 8, 256, 256, 36, p, p, p, p, (ll * 8)(*st), p, f(0.0), null, 0, null) == EINVAL, i
+            assert bwd(st, ggood) == EINVAL, i
+    for i in (0, 2, 4):
+        for bad in (-288, -4):
+            gst = list(ggood)
+            gst[i] = bad
+            assert bwd(good, gst) == EINVAL, i
+    assert bwd(good, [288, 2304, 288, 2304, 290, 2304]) == EINVAL                      # the rules that were there stay
+    assert bwd(good, [288, 2304, 1 << 30, 2304, 288, 2304]) == ETOOLARGE
+    assert lib.omnipq_attn_fwd(8, 8, 256, 256, 36, p, p, p, p, (ll * 8)(1 << 30, 2304, 288, 2304, 288, 2304, 288, 2304), p,
+                               f(0.0), null, 0, null) == ETOOLARGE
     # GEMMs: contraction length must be a multiple of the K step, leading dimensions of 8
     assert lib.omnipq_gemm_nt_e16(128, 128, 33, p, 40, p, 40, p, 128, null, null) == EINVAL
     assert lib.omnipq_gemm_nt_e16_stats(128, 128, 32, p, 32, p, 32, p, 128, null, null, null, null, null) == EINVAL  # no sums
