@@ -16,18 +16,20 @@ mean accounts for it (and its gradient is exactly zero).
 
 Used under `torch.autocast("cuda", dtype=torch.bfloat16)` (or float16: sa_fused.E16); otherwise callers keep PyTorch's f32 layers.
 """
+import collections
 import os
+import typing
 
 import torch
 
 import dropout_state
 import sa_fused
+from sa_fused import E16, _call, _gemm_nt_bnbwd, _gemm_nt_stats, _gemm_tn, _lib, _p, _round_up, _world, prep_weight, unprep_wgrad, zeros_f32
 
-# ReLU + dropout of a `relu_dropout` layer inside its GEMM's epilogue (False: the separate in-place pass; the tests
-# compare the two)
+# ReLU + dropout of a `relu_dropout` layer inside its GEMM's epilogue, and its backward mask in the epilogue of the data-gradient
+# GEMM above it (False: the separate in-place passes; tests/test_gpu_decoder.py:
+# test_rows_stack_with_and_without_fused_activation compares the two)
 _FUSE_ACT = True
-from sa_fused import (E16, _allreduce_, _call, _gemm_nt_bnbwd, _gemm_nt_stats, _gemm_tn, _lib, _p, _round_up, _world, affine_grads, prep_weight,
-                      unprep_wgrad, zeros_f32, zeros_f64)
 
 
 class Layer:
@@ -74,14 +76,77 @@ def run(x_rows, layers, training, padded=False):
     return RowsMLP.apply(x_rows, spec, bool(training), *params)
 
 
-def _is_bn(entry):
-    return entry is not None and entry[0] != "relu_dropout"
+# What follows a layer's linear map (run / run_pair pass these to the autograd nodes as non-tensor arguments; None: nothing).
+# BnSpec: BatchNorm + ReLU, the module's buffers and constants.  ActSpec: ReLU + dropout(p), seed and salt pick the mask
+# (dropout_state; p = 0: no seed).  StackSpec: layers = one of them per layer, padded: see run(), sync: the BatchNorm layers are
+# SyncBatchNorm (statistics over all ranks).
+BnSpec = collections.namedtuple("BnSpec", "running_mean running_var num_batches_tracked momentum eps")
+ActSpec = collections.namedtuple("ActSpec", "p seed salt")
+StackSpec = collections.namedtuple("StackSpec", "layers padded sync")
+
+
+def _kind(spec):
+    return "bn" if isinstance(spec, BnSpec) else "act" if isinstance(spec, ActSpec) else "plain"
+
+
+class LayerRoute(typing.NamedTuple):
+    kind: str         # "bn" | "act" | "plain"
+    feed: str         # the GEMM's operand: "input" (layer 0: the prepared input rows) | "stored" (the layer below's output) | "yab"
+                      # (rebuilt from the layer below's pre-BN output and its scale / shift while the GEMM stages it)
+    gemm: str         # "stats" (with the batch statistics of its output) | "relu_dropout" (ReLU + dropout in its epilogue) | "plain";
+                      # on a "yab" feed the affine entry point of the same kind
+    finalize: str     # bn: where the layer's constants are derived: "consumer" (the prologue of the GEMM it feeds, nothing stored) |
+                      # "launch" (omnipq_bn_finalize_relu) | "running" (eval: from the running estimates, + omnipq_bnrelu); else ""
+    act: str          # act: ReLU + dropout in the GEMM's "epilogue" | the in-place "pass" (omnipq_relu_dropout); else ""
+    dgrad: str        # the data gradient: "input" (layer 0: only if the input needs one) | "bnbwd" (with the BatchNorm-backward totals
+                      # of the layer below) | "mask" (with the layer below's ReLU + dropout mask in its epilogue) | "plain"
+    bwd_stats: str    # bn: its BatchNorm-backward totals come from the data-gradient GEMM "above" | its "own" launch; else ""
+    bwd_act: str      # act: its backward mask is applied by the data-gradient GEMM "above" | its own "pass"; else ""
+
+
+class StackRoute(typing.NamedTuple):
+    """Every decision of one stack pass, made by stack_route() before anything is launched.  _forward_program stores it on its
+    context; forward and backward dispatch on it and decide nothing themselves.  A new route is a new value of a field of
+    LayerRoute, its condition in stack_route(), and a step function for the two programs to call.  (What depends on the moment
+    of the launch stays there: the statistics exchange, deferred weight gradients, the input cache, PairStats.)"""
+    training: bool
+    layers: tuple     # one LayerRoute per layer
+
+
+def stack_route(training, N, cin, layers):
+    """The route of a stack from shapes alone (no tensor, no launch; the switches are read now).  N rows of cin channels;
+    layers: per layer (output channels, kind)."""
+    L, K, out = len(layers), _round_up(cin, 32), []
+    for l, (cout, kind) in enumerate(layers):
+        Cp = _round_up(cout, 32)
+        feed = "input" if l == 0 else "yab" if out[-1].finalize == "consumer" else "stored"
+        if kind == "bn" and training:
+            gemm = "stats"
+        elif kind == "act" and feed != "yab" and _FUSE_ACT and K < 1024 and N * Cp < (1 << 32):
+            gemm = "relu_dropout"             # (the widths the epilogue kernel is built for; its mask hashes a 32-bit element index)
+        else:
+            gemm = "plain"
+        finalize = ""
+        if kind == "bn":
+            # "consumer": relu(bn(Y)) is never stored: the next layer's GEMM and this layer's consumers in backward rebuild it
+            # from (Y, a, b) while staging their operand, and the finalize happens in the prologue of that GEMM
+            finalize = "running" if not training else \
+                "consumer" if (l < L - 1 and sa_fused.affine_pays(N, layers[l + 1][0])) else "launch"
+        below = layers[l - 1][1] if l else None
+        dgrad = "input" if l == 0 else "bnbwd" if below == "bn" else \
+            "mask" if (below == "act" and _FUSE_ACT and Cp < 1024) else "plain"
+        out.append(LayerRoute(kind, feed, gemm, finalize, "" if kind != "act" else "epilogue" if gemm == "relu_dropout" else "pass",
+                              dgrad, "" if kind != "bn" else "above" if l < L - 1 else "own", ""))
+        K = Cp
+    for l, r in enumerate(out):
+        if r.kind == "act":
+            out[l] = r._replace(bwd_act="above" if (l < L - 1 and out[l + 1].dgrad == "mask") else "pass")
+    return StackRoute(bool(training), tuple(out))
 
 
 class _L:
-    __slots__ = ("act", "K", "C", "Cp", "Wp", "Wt", "wk", "a", "b", "mean", "invstd", "Y", "X", "has_bn", "has_bias", "fin")
-
-
+    """Per-layer constants and saved tensors (the attributes sa_fused's helpers read of a layer: Y, a, b, mean, invstd, fin)."""
+    __slots__ = ("act", "K", "C", "Cp", "Wp", "Wt", "wk", "a", "b", "mean", "invstd", "Y", "X", "has_bias", "fin")
 
 
 def _hold(lead):
@@ -130,226 +195,274 @@ def _lockstep(lead, follow):
 class _Ctx:
     """What a stack's program keeps between forward and backward (one per stack of a pair; a lone stack uses the autograd
     context itself)."""
+    __slots__ = ("route", "layers", "X0", "geom", "wshapes", "nbias", "targets", "in_dtype", "padded")
+
+
+# ---- forward steps ----
+
+def _input_rows(x, N, cin, K):
+    """x (N, cin) -> the first GEMM's operand: E16 rows (N, K), zero-padded.  The same input tensor feeding several stacks (the
+    decoder's key positions: one embedding per layer) is prepared once; the copy is tied to the tensor's version counter, so
+    an input updated in place (a static buffer refilled with copy_) is converted again instead of feeding stale rows."""
+    cached = getattr(x, "omnipq_rows_in", None)
+    if cached is not None and cached[0] == x._version and cached[1].shape == (N, K):
+        return cached[1]
+    if K == cin:
+        X = x.detach().to(E16.dtype).contiguous()
+    elif x.dtype in (torch.float32, E16.dtype) and x.stride(1) == 1:
+        X = torch.empty((N, K), device=x.device, dtype=E16.dtype)          # cast + zero padding in one launch
+        _call(_lib.omnipq_pad_rows_e16, x, N, cin, K, x.stride(0), _p(x), int(x.dtype == torch.float32), _p(X))
+    else:
+        X = torch.nn.functional.pad(x.detach().to(E16.dtype), (0, K - cin))
+    if X.data_ptr() != x.data_ptr() and not x.requires_grad:
+        try:
+            x.omnipq_rows_in = (x._version, X)    # inputs without gradient only: constants of the forward pass
+        except Exception:
+            pass
+    return X
+
+
+def _new_layer(W, bias, K, act, training):
+    """The layer's sizes and its prepared weight; act: its ActSpec, if it has one."""
+    lay = _L()
+    W2 = W.detach().reshape(W.shape[0], -1)
+    lay.C, lay.wk = W2.shape
+    lay.K, lay.Cp = K, _round_up(lay.C, 32)
+    lay.has_bias, lay.act, lay.fin = bias is not None, act, None
+    lay.Wp, lay.Wt = prep_weight(W2, lay.Cp, K, transpose=training, persistent=sa_fused.is_persistent(W))
+    return lay
+
+
+def _padded_bias(bias, Cp):
+    bp = bias.detach().float()                 # may come zero-padded already (cat_params(pad_to=))
+    return bp if bp.shape[0] >= Cp else torch.nn.functional.pad(bp, (0, Cp - bp.shape[0]))
+
+
+# the forward GEMM of a layer, by LayerRoute.gemm: (lay, X, below, N, bias, sums) -> Y.  below: the layer X is rebuilt from
+# (feed "yab"; X is None then)
+def _gemm_stats(lay, X, below, N, bias, sums):
+    if below is not None:
+        return sa_fused.gemm_nt_affine(below.Y, below, lay.Wp, N, lay.Cp, lay.K, sums=sums)
+    return _gemm_nt_stats(X, lay.Wp, N, lay.Cp, lay.K, sums)
+
+
+def _gemm_relu_dropout(lay, X, below, N, bias, sums):
+    """ReLU + dropout in the GEMM's epilogue (same decisions as omnipq_relu_dropout on the stored matrix)"""
+    Y = torch.empty((N, lay.Cp), device=X.device, dtype=E16.dtype)
+    _call(_lib.omnipq_gemm_nt_e16_relu_dropout, X, N, lay.Cp, lay.K, _p(X), lay.K, _p(lay.Wp), lay.K, _p(Y), lay.Cp, _p(bias),
+          lay.act.p, _p(lay.act.seed), lay.act.salt)
+    return Y
+
+
+def _gemm_plain(lay, X, below, N, bias, sums):
+    Y = torch.empty((N, lay.Cp), device=lay.Wp.device, dtype=E16.dtype)
+    if below is not None:
+        sa_fused.gemm_nt_affine(below.Y, below, lay.Wp, N, lay.Cp, lay.K, bias=bias, out=Y)
+    else:
+        sa_fused.gemm_nt_into(X, lay.Wp, Y, N, lay.Cp, lay.K, bias=bias)
+    return Y
+
+
+_GEMM = {"stats": _gemm_stats, "relu_dropout": _gemm_relu_dropout, "plain": _gemm_plain}
+
+
+# where a BatchNorm layer gets its constants, by LayerRoute.finalize: (lay, N, count, sums, bn, bias, gamma, beta) -> lay.X
+def _batch_constants(lay, bias):
+    stats = torch.empty((4, lay.C), device=lay.Y.device)            # a | b | mean | invstd
+    lay.a, lay.b, lay.mean, lay.invstd = stats[0], stats[1], stats[2], stats[3]
+    return bias.detach().float().contiguous() if lay.has_bias else None          # only the running mean accounts for the bias
+
+
+def _finalize_in_consumer(lay, N, count, sums, bn, bias, gamma, beta):
+    """by the GEMM this layer feeds (sa_fused.gemm_nt_affine takes `fin`); relu(bn(Y)) is never stored"""
+    cb = _batch_constants(lay, bias)
+    lay.fin = (sums, count, gamma.detach(), beta.detach(), bn.eps, bn.momentum, bn.running_mean, bn.running_var, cb)
+    lay.X = None
+    return None
+
+
+def _finalize_launch(lay, N, count, sums, bn, bias, gamma, beta):
+    cb = _batch_constants(lay, bias)
+    lay.X = torch.empty_like(lay.Y)
+    _call(_lib.omnipq_bn_finalize_relu, lay.Y, N, lay.C, count, _p(sums), _p(gamma.detach()), _p(beta.detach()), bn.eps,
+          bn.momentum, _p(bn.running_mean), _p(bn.running_var), _p(cb), _p(lay.Y), _p(lay.X), _p(lay.a), _p(lay.b), _p(lay.mean),
+          _p(lay.invstd))
+    return lay.X
+
+
+def _finalize_running(lay, N, count, sums, bn, bias, gamma, beta):
+    """eval mode: constants from the running estimates, then normalise + ReLU"""
+    lay.invstd = torch.rsqrt(bn.running_var + bn.eps)
+    lay.mean = bn.running_mean - bias.detach().float() if lay.has_bias else bn.running_mean
+    lay.a = (gamma.detach() * lay.invstd).contiguous()
+    lay.b = (beta.detach() - lay.mean * lay.a).contiguous()
+    lay.X = torch.empty_like(lay.Y)
+    _call(_lib.omnipq_bnrelu, lay.Y, N, lay.C, _p(lay.Y), _p(lay.a), _p(lay.b), _p(lay.X))
+    return lay.X
+
+
+_FINALIZE = {"consumer": _finalize_in_consumer, "launch": _finalize_launch, "running": _finalize_running}
 
 
 def _forward_program(ctx, lead, x, spec, training, params):
-        spec, padded, sync = spec
-        dev = x.device
-        N, cin = x.shape
-        L = len(spec)
-        world = _world() if (training and sync) else 1
-        K = _round_up(cin, 32)
-        # the same input tensor feeding several stacks (the decoder's key positions: one embedding per layer) is prepared
-        # once; the copy is tied to the tensor's version counter, so an input updated in place (a static buffer refilled
-        # with copy_) is converted again instead of feeding stale rows
-        cached = getattr(x, "omnipq_rows_in", None)
-        if cached is not None and cached[0] == x._version and cached[1].shape == (N, K):
-            X = cached[1]
+    dev = x.device
+    N, cin = x.shape
+    L = len(spec.layers)
+    world = _world() if (training and spec.sync) else 1
+    route = stack_route(training, N, cin, tuple((params[4 * l].shape[0], _kind(spec.layers[l])) for l in range(L)))
+    X0 = X = _input_rows(x, N, cin, _round_up(cin, 32))
+    K = X.shape[1]
+    layers = []
+    for l, r in enumerate(route.layers):
+        W, bias, gamma, beta = params[4 * l:4 * l + 4]
+        lay = _new_layer(W, bias, K, spec.layers[l] if r.kind == "act" else None, training)
+        if r.kind == "bn" and lay.Cp != lay.C:
+            raise RuntimeError("RowsMLP: BatchNorm widths must be multiples of 32")
+        sums, slot = sa_fused.pair_sums(lead, 2, lay.C, dev, world) if r.gemm == "stats" else (None, None)
+        # (a linear bias that feeds a BatchNorm is never added: see the module's docstring)
+        bp = _padded_bias(bias, lay.Cp) if (lay.has_bias and r.kind != "bn") else None
+        _hold(lead)
+        lay.Y = _GEMM[r.gemm](lay, X, layers[-1] if r.feed == "yab" else None, N, bp, sums)
+        yield
+        if r.kind == "bn":
+            if training:
+                sa_fused.pair_allreduce(sums, slot, lead, world)
+            X = _FINALIZE[r.finalize](lay, N, float(N) * world, sums, spec.layers[l], bias, gamma, beta)
+            if training:
+                sa_fused.bump(spec.layers[l].num_batches_tracked)
         else:
-            if K == cin:
-                X = x.detach().to(E16.dtype).contiguous()
-            elif x.dtype in (torch.float32, E16.dtype) and x.stride(1) == 1:
-                X = torch.empty((N, K), device=x.device, dtype=E16.dtype)          # cast + zero padding in one launch
-                _call(_lib.omnipq_pad_rows_e16, x, N, cin, K, x.stride(0), _p(x),
-                      int(x.dtype == torch.float32), _p(X))
-            else:
-                X = torch.nn.functional.pad(x.detach().to(E16.dtype), (0, K - cin))
-            if X.data_ptr() != x.data_ptr() and not x.requires_grad:
-                try:
-                    x.omnipq_rows_in = (x._version, X)    # inputs without gradient only: constants of the forward pass
-                except Exception:
-                    pass
-        X0 = X
-        layers = []
-        for l in range(L):
-            W, bias, gamma, beta = params[4 * l:4 * l + 4]
-            lay = _L()
-            W2 = W.detach().reshape(W.shape[0], -1)
-            cout, wk = W2.shape
-            lay.C, lay.K, lay.Cp = cout, K, _round_up(cout, 32)
-            lay.has_bn, lay.has_bias, lay.wk = _is_bn(spec[l]), bias is not None, wk
-            lay.act = spec[l] if (spec[l] is not None and not lay.has_bn) else None
-            lay.fin = None
-            act_fused = False
-            lay.Wp, lay.Wt = prep_weight(W2, lay.Cp, K, transpose=training, persistent=sa_fused.is_persistent(W))
-            if lay.has_bn and lay.Cp != cout:
-                raise RuntimeError("RowsMLP: BatchNorm widths must be multiples of 32")
-            sums = None
-            below = layers[-1] if (X is None) else None      # the layer below kept only (Y, a, b): see sa_fused
-            slot = None
-            if lay.has_bn and training:
-                sums, slot = sa_fused.pair_sums(lead, 2, cout, dev, world)
-                _hold(lead)
-                if below is not None:
-                    Y = sa_fused.gemm_nt_affine(below.Y, below, lay.Wp, N, lay.Cp, K, sums=sums)
-                else:
-                    Y = _gemm_nt_stats(X, lay.Wp, N, lay.Cp, K, sums)
-                yield
-            else:
-                Y = torch.empty((N, lay.Cp), device=dev, dtype=E16.dtype)
-                bp = None
-                if lay.has_bias and not lay.has_bn:
-                    bp = bias.detach().float()                 # may come zero-padded already (cat_params(pad_to=))
-                    if bp.shape[0] < lay.Cp:
-                        bp = torch.nn.functional.pad(bp, (0, lay.Cp - bp.shape[0]))
-                act_fused = False
-                _hold(lead)
-                if below is not None:
-                    sa_fused.gemm_nt_affine(below.Y, below, lay.Wp, N, lay.Cp, K, bias=bp, out=Y)
-                elif lay.act is not None and _FUSE_ACT and K < 1024 and N * lay.Cp < (1 << 32):
-                    # ReLU + dropout in the GEMM's epilogue (same decisions as omnipq_relu_dropout on the stored matrix)
-                    _, p_act, seed_act, salt_act = lay.act
-                    _call(_lib.omnipq_gemm_nt_e16_relu_dropout, X, N, lay.Cp, K, _p(X), K, _p(lay.Wp), K, _p(Y), lay.Cp,
-                          _p(bp), p_act, _p(seed_act), salt_act)
-                    act_fused = True
-                else:
-                    sa_fused.gemm_nt_into(X, lay.Wp, Y, N, lay.Cp, K, bias=bp)
-                yield
-            lay.Y = Y
-            if lay.has_bn:
-                rm, rv, nbt, momentum, eps = spec[l]
-                if training:
-                    sa_fused.pair_allreduce(sums, slot, lead, world)
-                    stats = torch.empty((4, cout), device=dev)            # a | b | mean | invstd
-                    lay.a, lay.b, lay.mean, lay.invstd = stats[0], stats[1], stats[2], stats[3]
-                    cb = bias.detach().float().contiguous() if lay.has_bias else None
-                    if l < L - 1 and sa_fused.affine_pays(N, params[4 * (l + 1)].shape[0]):
-                        # relu(bn(Y)) is never stored: the next layer's GEMM and this layer's consumers in backward
-                        # rebuild it from (Y, a, b) while staging their operand
-                        # ... and the finalize itself happens in the prologue of that GEMM (sa_fused.gemm_nt_affine)
-                        lay.fin = (sums, float(N) * world, gamma.detach(), beta.detach(), eps, momentum, rm, rv, cb)
-                        lay.X = None
-                    else:
-                        lay.X = torch.empty_like(Y)
-                        _call(_lib.omnipq_bn_finalize_relu, Y, N, cout, float(N) * world,
-                              _p(sums), _p(gamma.detach()), _p(beta.detach()), eps, momentum,
-                              _p(rm), _p(rv), _p(cb), _p(Y), _p(lay.X), _p(lay.a), _p(lay.b), _p(lay.mean), _p(lay.invstd))
-                    sa_fused.bump(nbt)
-                else:
-                    lay.invstd = torch.rsqrt(rv + eps)
-                    shift = rm - bias.detach().float() if lay.has_bias else rm
-                    lay.mean = shift
-                    lay.a = (gamma.detach() * lay.invstd).contiguous()
-                    lay.b = (beta.detach() - shift * lay.a).contiguous()
-                if not training:
-                    lay.X = torch.empty_like(Y)
-                    _call(_lib.omnipq_bnrelu, Y, N, cout, _p(Y), _p(lay.a), _p(lay.b), _p(lay.X))
-                X = lay.X
-            else:
-                if lay.act is not None and not act_fused:
-                    _, p, seed, salt = lay.act
-                    _call(_lib.omnipq_relu_dropout, Y, N * lay.Cp, _p(Y), p,
-                          _p(seed), salt)
-                lay.X = Y
-                X = Y
-            K = lay.Cp
-            layers.append(lay)
-        ctx.layers, ctx.X0, ctx.geom = layers, X0, (N, cin, world)
-        ctx.wshapes = [tuple(params[4 * l].shape) for l in range(L)]
-        ctx.nbias = [0 if params[4 * l + 1] is None else params[4 * l + 1].shape[0] for l in range(L)]
-        # where the weight / bias gradients may be written directly (sa_fused.deferred_wgrads)
-        ctx.targets = [(sa_fused.grad_target(params[4 * l]),
-                        None if params[4 * l + 1] is None else sa_fused.grad_target(params[4 * l + 1]))
-                       for l in range(L)] if training else None
-        ctx.training = training
-        ctx.in_dtype = x.dtype
-        last = layers[-1]
-        ctx.padded = padded
-        return X if (padded or last.Cp == last.C) else X[:, :last.C]
+            if r.act == "pass":
+                _call(_lib.omnipq_relu_dropout, lay.Y, N * lay.Cp, _p(lay.Y), lay.act.p, _p(lay.act.seed), lay.act.salt)
+            X = lay.X = lay.Y
+        K = lay.Cp
+        layers.append(lay)
+    ctx.route, ctx.layers, ctx.X0, ctx.geom = route, layers, X0, (N, cin, world)
+    ctx.wshapes = [tuple(params[4 * l].shape) for l in range(L)]
+    ctx.nbias = [0 if params[4 * l + 1] is None else params[4 * l + 1].shape[0] for l in range(L)]
+    # where the weight / bias gradients may be written directly (sa_fused.deferred_wgrads)
+    ctx.targets = [(sa_fused.grad_target(params[4 * l]),
+                    None if params[4 * l + 1] is None else sa_fused.grad_target(params[4 * l + 1]))
+                   for l in range(L)] if training else None
+    ctx.in_dtype, ctx.padded = x.dtype, spec.padded
+    last = layers[-1]
+    return X if (spec.padded or last.Cp == last.C) else X[:, :last.C]
+
+
+# ---- backward steps ----
+
+def _output_grad(g, last, N, padded):
+    """-> (the gradient as E16 rows of the last layer's padded width, whether the buffer is this program's to overwrite)"""
+    if last.Cp == last.C or padded:
+        dcur = g.to(E16.dtype).contiguous()
+        return dcur, dcur.data_ptr() != g.data_ptr()        # autograd's buffer must not be modified in place
+    dcur = torch.zeros((N, last.Cp), device=g.device, dtype=E16.dtype)
+    dcur[:, :last.C] = g
+    return dcur, True
+
+
+def _bn_bwd_stats(lay, dcur, N, sums):
+    """the BatchNorm-backward totals of a layer that no data-gradient GEMM above it produced (LayerRoute.bwd_stats "own")"""
+    _call(_lib.omnipq_bn_bwd_stats_z, dcur, N, lay.C, _p(dcur), _p(lay.Y), _p(lay.a), _p(lay.b), _p(lay.mean), _p(lay.invstd),
+          _p(sums))
+
+
+def _act_bwd(lay, dcur, dst, N):
+    """lay.Y holds dropout(relu(.)): positive exactly where the unit was active and kept"""
+    _call(_lib.omnipq_relu_dropout_bwd, dcur, N * lay.Cp, _p(lay.Y), _p(dcur), _p(dst), lay.act.p)
+
+
+def _weight_grad(ctx, l, dcur, Xin, below, dfr, needs_input_grad, grads):
+    """dW (and the bias gradient: column sums of dY, from the same pass) of layer l, now or -- inside deferred_wgrads, where
+    the parameters can be written directly -- with all the others when the block ends"""
+    lay, N = ctx.layers[l], ctx.geom[0]
+    want_bias = ctx.route.layers[l].kind != "bn" and lay.has_bias
+    wt, bt = ctx.targets[l] if (dfr is not None and ctx.targets is not None) else (None, None)
+    if wt is not None and needs_input_grad[3 + 4 * l] and (
+            not want_bias or (sa_fused.bias_target_ok(bt, lay.C, lay.Cp) and needs_input_grad[4 + 4 * l])):
+        dfr.add(dcur, Xin, lay.Cp, lay.K, N, wt, (lay.C, lay.wk), bt if want_bias else None, below)
+        return
+    bsum = None
+    if want_bias:
+        bsum = zeros_f32(lay.Cp, dcur.device)
+        grads[4 * l + 1] = bsum[:ctx.nbias[l]]
+    dWp = _gemm_tn(dcur, Xin, lay.Cp, lay.K, N, colsum=bsum, below=below)
+    grads[4 * l] = unprep_wgrad(dWp, lay.C, lay.wk, 0, ctx.wshapes[l])      # in the parameter's own shape
+
+
+# the data gradient of a layer, by LayerRoute.dgrad: (lay, under, dcur, N, sums) -> gradient w.r.t. the layer's operand;
+# under: the layer below
+def _dgrad_bnbwd(lay, under, dcur, N, sums):
+    return _gemm_nt_bnbwd(dcur, lay.Wt, N, lay.K, lay.Cp, under, sums)
+
+
+def _dgrad_mask(lay, under, dcur, N, sums):
+    """the layer below is dropout(relu(.)): its backward mask in this GEMM's epilogue"""
+    dprev = torch.empty((N, lay.K), device=dcur.device, dtype=E16.dtype)
+    _call(_lib.omnipq_gemm_nt_e16_mask, dcur, N, lay.K, lay.Cp, _p(dcur), lay.Cp, _p(lay.Wt), lay.Cp, _p(dprev), lay.K,
+          _p(under.Y), under.act.p)
+    return dprev
+
+
+def _dgrad_plain(lay, under, dcur, N, sums):
+    dprev = torch.empty((N, lay.K), device=dcur.device, dtype=E16.dtype)
+    sa_fused.gemm_nt_into(dcur, lay.Wt, dprev, N, lay.K, lay.Cp)
+    return dprev
+
+
+_DGRAD = {"bnbwd": _dgrad_bnbwd, "mask": _dgrad_mask, "plain": _dgrad_plain, "input": _dgrad_plain}
 
 
 def _backward_program(ctx, lead, g, needs_input_grad):
-        if not ctx.training and any(l.has_bn for l in ctx.layers):
-            raise RuntimeError("RowsMLP: backward through eval-mode BatchNorm is not supported")
-        N, cin, world = ctx.geom
-        layers = ctx.layers
-        L = len(layers)
-        dev = g.device
-        total = float(N) * world
-        grads = [None] * (4 * L)
-        last = layers[-1]
-        if last.Cp == last.C or ctx.padded:
-            dcur = g.to(E16.dtype).contiguous()
-            owned = dcur.data_ptr() != g.data_ptr()        # autograd's buffer must not be modified in place
+    route, layers = ctx.route, ctx.layers
+    if not route.training and any(r.kind == "bn" for r in route.layers):
+        raise RuntimeError("RowsMLP: backward through eval-mode BatchNorm is not supported")
+    N, cin, world = ctx.geom
+    L = len(layers)
+    dev = g.device
+    grads = [None] * (4 * L)
+    dcur, owned = _output_grad(g, layers[-1], N, ctx.padded)
+    dx = None
+    sums = slot = None        # BatchNorm-backward totals that a "bnbwd" data gradient produced for the layer below it, and the
+                              # pair buffer they live in (sa_fused.PairStats)
+    dfr = sa_fused.deferred_wgrads.active
+    for l in range(L - 1, -1, -1):
+        lay, r = layers[l], route.layers[l]
+        below = layers[l - 1] if r.feed == "yab" else None      # the operand was rebuilt from its pre-BN output inside the GEMM
+        Xin = ctx.X0 if r.feed == "input" else layers[l - 1].Y if r.feed == "yab" else layers[l - 1].X
+        if r.kind == "bn":
+            if r.bwd_stats == "own":
+                sums, slot = sa_fused.pair_sums(lead, 3, lay.C, dev, world)
+                _bn_bwd_stats(lay, dcur, N, sums)
+                if sa_fused.PairStats.active is not None and (world > 1 or sa_fused._FORCE_COLLECTIVES):
+                    yield              # the partner's statistics kernel goes out before the exchange both share
+            assert sums is not None
+            dst = dcur if owned else torch.empty_like(dcur)
+            _hold(lead)
+            grads[4 * l + 2], grads[4 * l + 3] = sa_fused.bn_backward_apply(dcur, lay, N, lay.C, float(N) * world, sums, world,
+                                                                            out=dst, pair=(slot, lead))
+            yield
+            dcur, owned = dst, True
+            if lay.has_bias:
+                grads[4 * l + 1] = zeros_f32(lay.C, dev)                # removed by the batch mean
+        elif r.bwd_act == "pass":
+            dst = dcur if owned else torch.empty_like(dcur)
+            _act_bwd(lay, dcur, dst, N)
+            dcur, owned = dst, True
+        _weight_grad(ctx, l, dcur, Xin, below, dfr, needs_input_grad, grads)
+        sums = slot = None
+        if r.dgrad == "input" and not needs_input_grad[0]:
+            break
+        if r.dgrad == "bnbwd":
+            sums, slot = sa_fused.pair_sums(lead, 3, lay.K, dev, world)
+        _hold(lead)
+        dprev = _DGRAD[r.dgrad](lay, layers[l - 1] if l else None, dcur, N, sums)
+        yield
+        if l > 0:
+            dcur, owned = dprev, True
         else:
-            dcur = torch.zeros((N, last.Cp), device=dev, dtype=E16.dtype)
-            dcur[:, :last.C] = g
-            owned = True
-        dx = None
-        sums = None               # BN-backward sums of the current layer if the GEMM above already produced them
-        slot = None               # ... and the pair buffer they live in (sa_fused.PairStats)
-        dfr = sa_fused.deferred_wgrads.active
-        act_masked = -1                  # the dropout(relu(.)) layer whose backward mask the GEMM above it has applied already
-        for l in range(L - 1, -1, -1):
-            lay = layers[l]
-            Xin = layers[l - 1].X if l > 0 else ctx.X0
-            below = None
-            if Xin is None:                    # rebuilt from the layer's pre-BN output inside the GEMM
-                below = layers[l - 1]
-                Xin = below.Y
-            if lay.has_bn:
-                if sums is None:
-                    sums, slot = sa_fused.pair_sums(lead, 3, lay.C, dev, world)
-                    _call(_lib.omnipq_bn_bwd_stats_z, dcur, N, lay.C, _p(dcur), _p(lay.Y),
-                          _p(lay.a), _p(lay.b), _p(lay.mean), _p(lay.invstd), _p(sums))
-                    if sa_fused.PairStats.active is not None and (world > 1 or sa_fused._FORCE_COLLECTIVES):
-                        yield              # the partner's statistics kernel goes out before the exchange both share
-                dst = dcur if owned else torch.empty_like(dcur)
-                _hold(lead)
-                grads[4 * l + 2], grads[4 * l + 3] = sa_fused.bn_backward_apply(dcur, lay, N, lay.C, total, sums,
-                                                                                world, out=dst, pair=(slot, lead))
-                yield
-                dcur, owned = dst, True
-                if lay.has_bias:
-                    grads[4 * l + 1] = zeros_f32(lay.C, dev)                # removed by the batch mean
-            elif lay.act is not None and act_masked != l:
-                # lay.Y holds dropout(relu(.)): positive exactly where the unit was active and kept
-                dst = dcur if owned else torch.empty_like(dcur)
-                _call(_lib.omnipq_relu_dropout_bwd, dcur, N * lay.Cp, _p(lay.Y), _p(dcur), _p(dst),
-                      lay.act[1])
-                dcur, owned = dst, True
-            want_bias = not lay.has_bn and lay.has_bias
-            wt, bt = ctx.targets[l] if (dfr is not None and ctx.targets is not None) else (None, None)
-            if wt is not None and needs_input_grad[3 + 4 * l] and (
-                    not want_bias or (sa_fused.bias_target_ok(bt, lay.C, lay.Cp) and needs_input_grad[4 + 4 * l])):
-                # collected; computed with all the others when the deferred_wgrads block ends
-                dfr.add(dcur, Xin, lay.Cp, lay.K, N, wt, (lay.C, lay.wk), bt if want_bias else None, below)
-            else:
-                bsum = None
-                if want_bias:
-                    bsum = zeros_f32(lay.Cp, dev)            # bias gradient: column sums of dY, from the same pass
-                    grads[4 * l + 1] = bsum[:ctx.nbias[l]]
-                dWp = _gemm_tn(dcur, Xin, lay.Cp, lay.K, N, colsum=bsum, below=below)
-                grads[4 * l] = unprep_wgrad(dWp, lay.C, lay.wk, 0, ctx.wshapes[l])
-            sums, slot = None, None
-            if l > 0 and layers[l - 1].has_bn:
-                sums, slot = sa_fused.pair_sums(lead, 3, lay.K, dev, world)
-                _hold(lead)
-                dprev = _gemm_nt_bnbwd(dcur, lay.Wt, N, lay.K, lay.Cp, layers[l - 1], sums)
-                yield
-                dcur, owned = dprev, True
-            elif l > 0 or needs_input_grad[0]:
-                dprev = torch.empty((N, lay.K), device=dev, dtype=E16.dtype)
-                _hold(lead)
-                if l > 0 and layers[l - 1].act is not None and _FUSE_ACT and lay.Cp < 1024:
-                    # the layer below is dropout(relu(.)): its backward mask in this GEMM's epilogue
-                    _call(_lib.omnipq_gemm_nt_e16_mask, dcur, N, lay.K, lay.Cp, _p(dcur), lay.Cp, _p(lay.Wt), lay.Cp,
-                          _p(dprev), lay.K, _p(layers[l - 1].Y), layers[l - 1].act[1])
-                    act_masked = l - 1
-                else:
-                    sa_fused.gemm_nt_into(dcur, lay.Wt, dprev, N, lay.K, lay.Cp)
-                yield
-                if l > 0:
-                    dcur, owned = dprev, True
-                else:
-                    dx = dprev[:, :cin].to(ctx.in_dtype)
-        # weight gradients in the parameters' own shapes
-        out = [dx, None, None]
-        for l in range(L):
-            for j in range(4):
-                out.append(grads[4 * l + j])
-        ctx.layers = None
-        return tuple(out)
+            dx = dprev[:, :cin].to(ctx.in_dtype)
+    ctx.layers = None
+    return (dx, None, None, *grads)
 
 
 class RowsMLP(torch.autograd.Function):
@@ -401,17 +514,16 @@ def _spec_of(x_rows, layers, training, padded):
         bn = lay.bn
         if bn is None and lay.relu_dropout is not None:
             p = float(lay.relu_dropout) if training else 0.0
-            spec.append(("relu_dropout", p, dropout_state.seed(x_rows.device) if p > 0 else None,
-                         dropout_state.next_salt() if p > 0 else 0))
+            spec.append(ActSpec(p, dropout_state.seed(x_rows.device) if p > 0 else None, dropout_state.next_salt() if p > 0 else 0))
         else:
             spec.append(None if bn is None else
-                        (bn.running_mean, bn.running_var, bn.num_batches_tracked, float(bn.momentum), float(bn.eps)))
+                        BnSpec(bn.running_mean, bn.running_var, bn.num_batches_tracked, float(bn.momentum), float(bn.eps)))
         params += [lay.weight, lay.bias, None if bn is None else bn.weight, None if bn is None else bn.bias]
     # SyncBatchNorm semantics (statistics over all ranks) only where the layers ARE SyncBatchNorm; a stack of plain
     # BatchNorm layers keeps per-rank statistics under DDP, as torch's does
     bns = [lay.bn for lay in layers if lay.bn is not None]
     sync = bool(bns) and all(bool(sa_fused.bn_syncs(bn)) for bn in bns)
-    return (spec, bool(padded), sync), params
+    return StackSpec(tuple(spec), bool(padded), sync), params
 
 
 def run_pair(xa, layers_a, xb, layers_b, training, padded=False):

@@ -155,6 +155,62 @@ def test_relu_dropout_rows_layer_matches_torch():
         assert rel_l2(u, v) < 6e-2, rel_l2(u, v)
 
 
+@pytest.mark.parametrize("p", [0.0, 0.5])
+def test_rows_stack_with_and_without_fused_activation(p, monkeypatch):
+    """rows_mlp._FUSE_ACT: the stack 96 -> 256 (ReLU + dropout p) -> 64 over 300 rows with the activation in the GEMMs'
+    epilogues (forward: omnipq_gemm_nt_e16_relu_dropout; backward: the mask in omnipq_gemm_nt_e16_mask) against the separate
+    in-place passes, same seed and salt.  p = 0: everything bit for bit -- the epilogue equals GEMM + pass bit for bit at
+    p = 0 and the masked GEMM equals GEMM + pass always (the two kernel-level tests below).  p > 0: the same units are dropped;
+    the hidden layer differs by one bf16 rounding (the epilogue scales the f32 accumulator and rounds once, the pass rounds
+    twice: 2^-8 relative per element), and the second GEMM only sums those differences with its weights and rounds the output
+    once more (2^-9), so the output stays within 2^-7 of its largest element."""
+    import dropout_state
+    import rows_mlp
+    torch.manual_seed(5)
+    dropout_state.STATE.reset()
+    N, cin, hid, cout, salt = 300, 96, 256, 64, 9
+    x = torch.randn(N, cin, device=dev()).to(torch.bfloat16).requires_grad_(True)
+    l1 = torch.nn.Linear(cin, hid).to(dev())
+    l2 = torch.nn.Linear(hid, cout).to(dev())
+    g = torch.randn(N, cout, device=dev()).to(torch.bfloat16)
+    leaves = [x, l1.weight, l1.bias, l2.weight, l2.bias]
+    called = []
+    launch = rows_mlp._call
+    monkeypatch.setattr(rows_mlp, "_call", lambda fn, *args: (called.append(fn.__name__), launch(fn, *args))[1])
+
+    def run(fused):
+        monkeypatch.setattr(rows_mlp, "_FUSE_ACT", fused)
+        dropout_state.STATE.salt = salt - 1
+        del called[:]
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            stack = [rows_mlp.Layer(l1.weight, l1.bias, relu_dropout=p), rows_mlp.Layer(l2.weight, l2.bias)]
+            y = rows_mlp.run(x, stack, True)
+        grads = torch.autograd.grad(y, leaves, g)
+        return y.detach(), grads, set(called)
+
+    want, want_grads, passes = run(False)
+    got, got_grads, fused = run(True)
+    assert {"omnipq_relu_dropout", "omnipq_relu_dropout_bwd"} <= passes
+    assert {"omnipq_gemm_nt_e16_relu_dropout", "omnipq_gemm_nt_e16_mask"} <= fused
+    assert not (passes & {"omnipq_gemm_nt_e16_relu_dropout", "omnipq_gemm_nt_e16_mask"})
+    assert not (fused & {"omnipq_relu_dropout", "omnipq_relu_dropout_bwd"})
+    if p == 0:
+        assert torch.equal(got, want)
+        for u, v in zip(got_grads, want_grads):
+            assert torch.equal(u, v)
+        return
+    err, scale = float((got.float() - want.float()).abs().max()), float(want.float().abs().max())
+    print(f"fused vs two-pass, p = {p}: output max|diff| {err:.3e} of max|want| {scale:.3e}; "
+          f"second weight gradient rel. L2 {rel_l2(got_grads[3], want_grads[3]):.3e}")
+    assert torch.equal(got == 0, want == 0)
+    assert err <= 2.0 ** -7 * scale
+    # backward: the hidden layer enters every gradient but the second weight's only through WHERE it is positive, and it is
+    # positive at the same units, so those four are bit-identical; the second weight gradient sees its one rounding
+    for i in (0, 1, 2, 4):
+        assert torch.equal(got_grads[i], want_grads[i]), i
+    assert torch.equal(got_grads[3] == 0, want_grads[3] == 0)
+
+
 @pytest.mark.parametrize("train", [True, False])
 def test_decoder_layer_rows_matches_torch_path(train):
     import decoder_rows

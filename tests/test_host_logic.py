@@ -260,6 +260,77 @@ def test_stage_route_of_the_benchmark_model_and_its_edges(built_lib, monkeypatch
                                      keep_x2=False), s
 
 
+def test_stack_route_of_the_models_stacks_and_its_edges(built_lib, monkeypatch):
+    """rows_mlp.stack_route decides every route of a per-point MLP stack from shapes alone, before anything is launched.  The
+    stacks the benchmark model runs in training (lone linear layers, the feed-forward, position embeddings, voting and the heads,
+    an FP layer) with every field of every layer, then the edge of each condition and every switch in its off position: exactly
+    the fields whose condition names it change."""
+    import rows_mlp
+    import sa_fused
+    R = rows_mlp.LayerRoute
+
+    def route(cin, layers, N=4096, training=True):
+        r = rows_mlp.stack_route(training, N, cin, tuple(zip(layers[0::2], layers[1::2])))
+        assert isinstance(r, rows_mlp.StackRoute) and r.training is training and len(r.layers) == len(layers) // 2
+        return r.layers
+
+    # kind, feed, gemm, finalize, act, dgrad, bwd_stats, bwd_act
+    lone = (R("plain", "input", "plain", "", "", "input", "", ""),)
+    for N in (4096, 8192):
+        for cout in (864, 576, 288):
+            assert route(288, (cout, "plain"), N) == lone
+    ff = (288, (2048, "act", 288, "plain"))
+    ff_want = (R("act", "input", "relu_dropout", "", "epilogue", "input", "", "above"),
+               R("plain", "stored", "plain", "", "", "mask", "", ""))
+    assert route(*ff) == ff_want
+    first = R("bn", "input", "stats", "consumer", "", "input", "above", "")
+    middle = R("bn", "yab", "stats", "consumer", "", "bnbwd", "above", "")
+    out = R("plain", "yab", "plain", "", "", "bnbwd", "", "")
+    for N in (4096, 8192):
+        assert route(3, (288, "bn", 288, "plain"), N) == (first, out)
+    for cout in (291, 97):
+        assert route(288, (288, "bn", 288, "bn", cout, "plain")) == (first, middle, out)
+    fp = (1024, (512, "bn", 512, "bn"))
+    assert route(*fp) == (first, middle._replace(finalize="launch", bwd_stats="own"))
+
+    # the activation's two fusions test different widths and are independent: the epilogue the contraction of the act layer's
+    # GEMM (and the 32-bit element index of its mask), the backward mask the width of the layer above
+    k992, k1024 = route(992, (64, "act", 32, "plain")), route(1024, (64, "act", 32, "plain"))
+    assert k992 == ff_want and k1024 == (ff_want[0]._replace(gemm="plain", act="pass"), ff_want[1])
+    w992, w1024 = route(96, (256, "act", 992, "plain")), route(96, (256, "act", 1024, "plain"))
+    assert w992 == ff_want and w1024 == (ff_want[0]._replace(bwd_act="pass"), ff_want[1]._replace(dgrad="plain"))
+    assert route(32, (2048, "act", 32, "plain"), N=(1 << 21) - 1) == ff_want
+    assert route(32, (2048, "act", 32, "plain"), N=1 << 21) == (ff_want[0]._replace(gemm="plain", act="pass"), ff_want[1])
+    assert route(32, (2017, "act", 32, "plain"), N=1 << 21) == route(32, (2048, "act", 32, "plain"), N=1 << 21)   # the PADDED width
+    # an act layer fed from (Y, a, b): there is no affine GEMM with the activation in its epilogue
+    assert route(96, (128, "bn", 256, "act", 64, "plain")) == (
+        first, R("act", "yab", "plain", "", "pass", "bnbwd", "", "above"), ff_want[1])
+    # eval mode: constants from the running estimates, every activation stored; the BN-less stacks keep their routes
+    assert route(*fp, training=False) == tuple(r._replace(feed=f, gemm="plain", finalize="running")
+                                               for r, f in zip(route(*fp), ("input", "stored")))
+    assert route(*ff, training=False) == ff_want
+
+    stacks = [ff, fp, (3, (288, "bn", 288, "plain")), (288, (288, "bn", 288, "bn", 291, "plain")),
+              (96, (128, "bn", 256, "act", 64, "plain")), (288, (864, "plain"))]
+    base = [route(*s) for s in stacks]
+    monkeypatch.setattr(rows_mlp, "_FUSE_ACT", False)
+    for s, b in zip(stacks, base):
+        assert route(*s) == tuple(r._replace(gemm="plain" if r.gemm == "relu_dropout" else r.gemm,
+                                             act="pass" if r.act else "", bwd_act="pass" if r.bwd_act else "",
+                                             dgrad="plain" if r.dgrad == "mask" else r.dgrad) for r in b), s
+    monkeypatch.undo()
+    monkeypatch.setattr(sa_fused, "AFFINE_OPERANDS", False)
+    for s, b in zip(stacks, base):
+        got = route(*s)
+        assert all(r.feed == ("stored" if l else "input") and r.finalize in ("", "launch") for l, r in enumerate(got)), s
+        want = [r._replace(feed="stored" if r.feed == "yab" else r.feed, finalize="launch" if r.finalize else "") for r in b]
+        if s is stacks[4]:                # `gemm` names the feed: an act layer on a stored operand gets its epilogue back
+            want[1] = want[1]._replace(gemm="relu_dropout", act="epilogue")
+        assert got == tuple(want), s
+    monkeypatch.undo()
+    assert [route(*s) for s in stacks] == base
+
+
 def test_bench_labels_committed_counter_figures_taken_on_other_kernel_sources():
     """bench.py reads HBM traffic / MFMA-busy from the counter summaries under profiles/; each carries the digest of the
     kernel sources it was measured on, and a figure from other sources is labelled stale in the JSON line."""
