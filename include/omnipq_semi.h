@@ -1,4 +1,5 @@
-/* omnipq_semi.h -- C ABI of the semi-supervised criteria: the gamma-mixture guide.
+/* omnipq_semi.h -- C ABI of the semi-supervised criteria: the gamma-mixture guide and, below it, the mean-teacher
+ * consistency loss.
  *
  * Reference: models/utils/gamma_mixture_loss_util.py:130-191 `gamma_mixture_guide_criterion(end_points, DATASET_CONFIG,
  * config)` and :27-127 `quad_point_mixture_metric`, called by train.py:513 on the unlabelled half of the batch.  Per scene
@@ -80,6 +81,103 @@ int omnipq_gm_guide_grad(int b, int n, int q, int k, int xyz_pitch, const float 
                          const float *quad_scores, const float *quad_center, const float *normal_vector,
                          const float *quad_size, const int *pick, const int *sample_inds, const float *record,
                          const float *g_terms, float *g_quad_scores, float *g_quad_center, float *g_quad_size, void *stream);
+
+/* ---- mean-teacher consistency loss -------------------------------------------------------------------------------------
+ * Reference: models/utils/mean_teacher_consistency_util.py:201-270 `get_consistency_loss(end_points, ema_end_points,
+ * DATASET_CONFIG)`, called by train.py:531 with the student's and the teacher's outputs.  For each of `prefixes` prediction
+ * heads and each of two kinds (0 objects, 1 quads; "pk" = 2 * prefix + kind below), per scene s with k proposals:
+ *
+ *   align    e = teacher centre; x negated where flip_x[s] != 0, y where flip_y[s] != 0; e <- e rot_mat[s]^T; e <- e scale[s].
+ *            NOT written back to the teacher's tensor (the reference flips it in place, :32-35): e goes to `ema_center`.
+ *   assign   ind1[i] = argmin_j |c_i - e_j|^2, dist1[i] the minimum; ind2[j] = argmin_i |c_i - e_j|^2, dist2[j] (c: the
+ *            student's centres; first index on ties);  conf[r] = softmax(score[s, r])[1] of the STUDENT (objectness_scores /
+ *            quad_scores);  d[r] = dist1[r] conf[ind1[r]] + dist2[r] conf[r]   (ind1 indexes the student's scores: :45)
+ *   clip     eps = torch.quantile(v, 0.85) over all b * k values v of the call (rank in f32, lerp between the bracketing order
+ *            statistics); term = sum_r [v_r < eps] v_r / (b k); no gradient through eps.  Applied to d and to the three
+ *            distances below.
+ *   objects  a = ind2.  class = 2 * sum_{r,c} pT[r,c] (log pT[r,c] - log pS[a_r,c]) / (b k nc), p = softmax(sem_cls_scores);
+ *            size(x) = mean_size[argmax size_scores] + size_residuals[argmax], the teacher's times scale[s];
+ *            dsz[r] = |size_S[a_r] - size_T[r]|^2 conf[r], clipped.
+ *   quads    dn[r] = (1 - |cos(nS[a_r].xy, nT[r].xy)|) conf[r] (cos as torch's cosine_similarity: each vector divided by
+ *            max(|.|, 1e-8); the teacher's normal is NOT aligned, as in the reference), clipped;
+ *            dqs[r] = |quad_size_S[a_r] - quad_size_T[r]|^2 conf[r], clipped;
+ *            qclass = 2 * sum_{r,c} KL as above over quad_scores / b  (`batchmean`; weight 0 in the total, still reported).
+ *   per prefix   obj = 0.5 centre + class + 0.05 size;   quad = 0.5 centre_q + 0 qclass + normal + 0.05 size_q
+ *   terms[0..8]  the sums over the prefixes / prefixes of: centre, class, size, obj, centre_q, qclass, normal, size_q, quad
+ *   terms[9]     terms[3] + terms[8]
+ *
+ * Everything per row is computed in f64 from the f32 inputs; the clipped values are stored as f32 and selected from by the
+ * integer radix selection of the guide; sums are f64 in a fixed order: the same inputs give the same bits.  No float atomics,
+ * no host read.  Forward: three launches (rows: grid (b, 2 prefixes); clip: one workgroup per pk; a one-wave fold in prefix
+ * order).  Backward: one launch, grid (b, 2 prefixes); every gradient row is written exactly once (a gather over the stored
+ * assignments and masks), nothing is accumulated into.
+ *
+ * OMNIPQ_EINVAL: a null required pointer, b < 0, k < 1, prefixes outside [1, OMNIPQ_MT_MAX_PREFIXES], nc or ns outside
+ * [1, OMNIPQ_MT_MAX_CLASSES].  OMNIPQ_ETOOLARGE: k > OMNIPQ_MT_MAX_K or b * k > OMNIPQ_MT_MAX_ROWS.  b == 0 succeeds and does
+ * nothing. */
+#define OMNIPQ_MT_MAX_PREFIXES 8
+#define OMNIPQ_MT_MAX_CLASSES 64
+/* one scene's centres, confidences, distances and assignments live in the rows kernel's LDS: 68 bytes per proposal */
+#define OMNIPQ_MT_MAX_K 512
+/* the b * k values of one clipped array are selected from in the clip kernel's LDS, 4 bytes each: 60 KiB */
+#define OMNIPQ_MT_MAX_ROWS 15360
+#define OMNIPQ_MT_TERMS 10
+
+typedef struct {
+  int prefixes, b, k, nc, ns;
+  /* the student's outputs, one pointer per prefix */
+  const float *center[OMNIPQ_MT_MAX_PREFIXES];              /* (b, k, 3) */
+  const float *objectness_scores[OMNIPQ_MT_MAX_PREFIXES];   /* (b, k, 2) */
+  const float *sem_cls_scores[OMNIPQ_MT_MAX_PREFIXES];      /* (b, k, nc) */
+  const float *size_scores[OMNIPQ_MT_MAX_PREFIXES];         /* (b, k, ns) */
+  const float *size_residuals[OMNIPQ_MT_MAX_PREFIXES];      /* (b, k, ns, 3) */
+  const float *quad_center[OMNIPQ_MT_MAX_PREFIXES];         /* (b, k, 3) */
+  const float *quad_scores[OMNIPQ_MT_MAX_PREFIXES];         /* (b, k, 2) */
+  const float *normal_vector[OMNIPQ_MT_MAX_PREFIXES];       /* (b, k, 3) */
+  const float *quad_size[OMNIPQ_MT_MAX_PREFIXES];           /* (b, k, 2) */
+  /* the teacher's (its objectness_scores are not read) */
+  const float *t_center[OMNIPQ_MT_MAX_PREFIXES];
+  const float *t_sem_cls_scores[OMNIPQ_MT_MAX_PREFIXES];
+  const float *t_size_scores[OMNIPQ_MT_MAX_PREFIXES];
+  const float *t_size_residuals[OMNIPQ_MT_MAX_PREFIXES];
+  const float *t_quad_center[OMNIPQ_MT_MAX_PREFIXES];
+  const float *t_quad_scores[OMNIPQ_MT_MAX_PREFIXES];
+  const float *t_normal_vector[OMNIPQ_MT_MAX_PREFIXES];
+  const float *t_quad_size[OMNIPQ_MT_MAX_PREFIXES];
+  /* the augmentation of the student's input relative to the teacher's (train.py:526-529) and the size templates */
+  const int *flip_x;                                        /* (b) */
+  const int *flip_y;                                        /* (b) */
+  const float *rot_mat;                                     /* (b, 3, 3) */
+  const float *scale;                                       /* (b) */
+  const float *mean_size;                                   /* (ns, 3) */
+} omnipq_mt_desc;
+
+typedef struct {
+  float *center[OMNIPQ_MT_MAX_PREFIXES];
+  float *objectness_scores[OMNIPQ_MT_MAX_PREFIXES];
+  float *sem_cls_scores[OMNIPQ_MT_MAX_PREFIXES];
+  float *size_residuals[OMNIPQ_MT_MAX_PREFIXES];
+  float *quad_center[OMNIPQ_MT_MAX_PREFIXES];
+  float *quad_scores[OMNIPQ_MT_MAX_PREFIXES];
+  float *normal_vector[OMNIPQ_MT_MAX_PREFIXES];
+  float *quad_size[OMNIPQ_MT_MAX_PREFIXES];
+} omnipq_mt_grads;
+
+/* bytes of the workspace the forward fills and the backward reads (values, assignments, classes, masks, records); 0 for
+ * arguments the forward would refuse */
+long long omnipq_mt_consistency_workspace_bytes(int prefixes, int b, int k);
+
+/* ema_center float[prefixes][2][b][k][3], assignment long long[prefixes][2][b][k] (ind2), confidence float[prefixes][2][b][k],
+ * terms float[OMNIPQ_MT_TERMS]: all overwritten.  The inputs are left untouched. */
+int omnipq_mt_consistency(const omnipq_mt_desc *d, float *ema_center, long long *assignment, float *confidence,
+                          void *workspace, float *terms, void *stream);
+
+/* g_terms float[OMNIPQ_MT_TERMS] = dLoss/dterms, folded with the term weights above -> the gradients of the student's
+ * center, objectness_scores, sem_cls_scores, size_residuals, quad_center, quad_scores, normal_vector and quad_size of every
+ * prefix, each overwritten in full (size_residuals: zero outside the arg-max class; normal_vector: zero in z).  Nothing flows
+ * to the teacher, to size_scores or through any eps.  The masks are the forward's (read from the workspace), not recomputed. */
+int omnipq_mt_consistency_grad(const omnipq_mt_desc *d, const void *workspace, const float *g_terms,
+                               const omnipq_mt_grads *g, void *stream);
 
 #ifdef __cplusplus
 }

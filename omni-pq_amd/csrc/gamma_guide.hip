@@ -3,6 +3,7 @@
 // element-type libraries.
 #include "common.h"
 #include "omnipq_semi.h"
+#include "radix_select.h"
 
 namespace omnipq {
 namespace {
@@ -154,74 +155,9 @@ __device__ __forceinline__ float gm_block_max(float v, double *scratch) {
   return t;
 }
 
-// Order statistics `rank` and `rank + 1` (0-based, ascending) of vals[0, cnt): non-negative floats, whose bit patterns
-// order like unsigned integers (+inf marks a dropped sample and sorts last).  Radix selection, 8 bits per pass: a 256-bin
-// histogram of the values that match the prefix found so far, then the bin that holds the rank.  Integer atomics only.
-// hist: 256 words, sel: 4 words of LDS.  rank + 1 >= cnt: hi = lo.
-__device__ void gm_select(const float *vals, int cnt, int rank, unsigned *hist, unsigned *sel, float &lo, float &hi) {
-  const int tid = (int)threadIdx.x;
-  unsigned prefix = 0, mask = 0, r = (unsigned)rank;
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    if (tid < 256) hist[tid] = 0;
-    __syncthreads();
-    for (int i = tid; i < cnt; i += kGmThreads) {
-      const unsigned key = __float_as_uint(vals[i]);
-      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (tid < 64) {                               // lane l owns bins 4 l .. 4 l + 3
-      const unsigned c0 = hist[4 * tid], c1 = hist[4 * tid + 1], c2 = hist[4 * tid + 2], c3 = hist[4 * tid + 3];
-      const unsigned own = c0 + c1 + c2 + c3;
-      unsigned incl = own;
-      for (int d = 1; d < 64; d <<= 1) {
-        const unsigned up = __shfl_up(incl, d, 64);
-        if (tid >= d) incl += up;
-      }
-      unsigned below = incl - own;
-      const unsigned c[4] = {c0, c1, c2, c3};
-      for (int j = 0; j < 4; ++j) {
-        if (r >= below && r < below + c[j]) {
-          sel[0] = (unsigned)(4 * tid + j);
-          sel[1] = r - below;
-        }
-        below += c[j];
-      }
-    }
-    __syncthreads();
-    prefix |= sel[0] << shift;
-    mask |= 255u << shift;
-    r = sel[1];
-  }
-  // the next order statistic: the same value if it occurs beyond the rank, else the smallest larger one
-  if (tid == 0) {
-    sel[2] = 0;
-    sel[3] = 0xffffffffu;
-  }
-  __syncthreads();
-  unsigned le = 0, next = 0xffffffffu;
-  for (int i = tid; i < cnt; i += kGmThreads) {
-    const unsigned key = __float_as_uint(vals[i]);
-    if (key <= prefix) ++le;
-    else next = min(next, key);
-  }
-  atomicAdd(&sel[2], le);
-  atomicMin(&sel[3], next);
-  __syncthreads();
-  lo = __uint_as_float(prefix);
-  hi = (rank + 1 >= cnt || (unsigned)(rank + 1) < sel[2]) ? lo : __uint_as_float(sel[3]);
-  __syncthreads();                                // sel is free again
-}
-
-// torch.quantile(vals, t) with the default linear interpolation: rank = t (cnt - 1) in f32, Tensor.lerp's formula
-__device__ float gm_quantile(const float *vals, int cnt, int n_k, float t, unsigned *hist, unsigned *sel) {
-  const float rank = t * (float)(n_k - 1);
-  const float below = floorf(rank);
-  const float w = rank - below;
-  float lo, hi;
-  gm_select(vals, cnt, (int)below, hist, sel, lo, hi);
-  if (!(w > 0.0f)) return lo;
-  const float diff = hi - lo;
-  return w < 0.5f ? lo + w * diff : hi - diff * (1.0f - w);
+// order statistics and torch.quantile over the workgroup's LDS array: radix_select.h
+__device__ __forceinline__ float gm_quantile(const float *vals, int cnt, int n_k, float t, unsigned *hist, unsigned *sel) {
+  return radix_quantile<kGmThreads>(vals, cnt, n_k, t, hist, sel);
 }
 
 __device__ __forceinline__ double gm_sl1(double e) {
