@@ -1,5 +1,5 @@
 /* omnipq_semi.h -- C ABI of the semi-supervised criteria: the gamma-mixture guide and, below it, the mean-teacher
- * consistency loss.
+ * consistency loss and the ARKit physical-constraint loss.
  *
  * Reference: models/utils/gamma_mixture_loss_util.py:130-191 `gamma_mixture_guide_criterion(end_points, DATASET_CONFIG,
  * config)` and :27-127 `quad_point_mixture_metric`, called by train.py:513 on the unlabelled half of the batch.  Per scene
@@ -178,6 +178,64 @@ int omnipq_mt_consistency(const omnipq_mt_desc *d, float *ema_center, long long 
  * to the teacher, to size_scores or through any eps.  The masks are the forward's (read from the workspace), not recomputed. */
 int omnipq_mt_consistency_grad(const omnipq_mt_desc *d, const void *workspace, const float *g_terms,
                                const omnipq_mt_grads *g, void *stream);
+
+/* ---- ARKit physical-constraint loss ------------------------------------------------------------------------------------
+ * Reference: models/utils/arkit_loss_util.py:5-52 `get_arkit_pc_loss(end_points, batch_data_unlabeled, DATASET_CONFIG)` with
+ * models/loss_helper_pq.py:307-350 (`get_2d_box`, `projection2d`), called by train.py:537: the ground-truth boxes of the
+ * UNLABELLED scenes must not poke through the quads predicted for them.  There it is a Python loop over B x 256 quads with a
+ * host read (`if quad_scores[b, k] > 0.1`) and about twenty small ops each.
+ *
+ * The full batch holds first + b scenes; the predictions read are those of scenes [first, first + b) (the reference's
+ * `[batch_size:]`, first = b = the number of unlabelled scenes), the labels are the unlabelled batch's own:
+ *   quad_center, normal_vector (first + b, q, 3); quad_size, quad_scores (first + b, q, 2)           f32
+ *   center_label, size_label (b, k2, 3) f32; num_gt_boxes: the count n_s of scene s is num_gt_boxes[s * count_stride]
+ *   (int64; a strided view such as `num_gt_boxes[..., 0]` needs no copy)
+ * Per unlabelled scene s and quad j, c = quad_center[j], n = normal_vector[j]:
+ *   gate_j  = softmax(quad_scores[j])[1] > 0.1                                                        (no gradient)
+ *   rev_j   = -(c.x n.x + c.y n.y) < 0          (the normal points away from the pseudo scene centre; c detached: no gradient)
+ *   (a, b)  = rev_j ? -(n.x, n.y) : (n.x, n.y)                                     NOT normalised, as in the reference
+ *   corners : for every box i < min(n_s, k2) the four points p = (g.x +- l / 2, g.y +- w / 2), g = center_label[i],
+ *             (l, w) = size_label[i][:2], in the order (+, +), (+, -), (-, +), (-, -)
+ *   delta   = a p.x + b p.y - (a c.x + b c.y)
+ *   t       = p - (a, b) delta;  inside = |t - c.xy| < quad_size[j][0]                                 (no gradient)
+ *   pair    = relu(-delta) * inside                                                                    relu'(0) = 0
+ *   loss   += gate_j * sum_p pair / n_s;   collisions += gate_j * #{p : pair > 1e-4}
+ * loss is the sum over scenes and quads; there is no division by the batch size, as in the reference.
+ *
+ * Differences from the reference, on purpose:
+ *   - a scene with n_s <= 0 contributes 0 to both outputs (the reference: 0 / 0, NaN as soon as one quad passes the gate);
+ *   - rows i >= n_s of the labels are never read (they may hold NaN);
+ *   - arithmetic per pair is f64 from the f32 inputs (the reference: f32); per-quad sums in corner order, a fixed-order sum
+ *     over the workgroup, then over the scenes in scene order: the same inputs give the same bits;
+ *   - the inputs are left untouched.
+ * No float atomics, no host read.  Forward: two launches (one workgroup per scene with the scene's boxes in LDS, 16 bytes
+ * per box, one thread per quad looping over the corners and over the quads beyond 256; a one-wave fold).  Backward: one launch,
+ * grid (first + b), which re-evaluates the forward's per-pair functions (compiled without FP contraction: the same decisions)
+ * on the quads whose record shows live pairs.
+ *
+ * record: int[b][q][OMNIPQ_ARKIT_RECORD_INTS] = {gate, rev, pairs inside, pairs inside with delta < 0, collisions}; a quad
+ * that does not pass the gate has {0, 0, 0, 0, 0}.  scene_sums: double[b][2], the scenes' (loss, collisions) between the
+ * two launches.  out: float[2] = (loss, collisions).  All three are overwritten.
+ *
+ * OMNIPQ_EINVAL: a null required pointer, b < 0, first < 0, q < 1, k2 < 1, count_stride < 1.  OMNIPQ_ETOOLARGE:
+ * k2 > OMNIPQ_ARKIT_MAX_BOXES, or (first + b) * q * OMNIPQ_ARKIT_RECORD_INTS beyond 2^31.  b == 0 succeeds and does nothing. */
+#define OMNIPQ_ARKIT_MAX_BOXES 256
+#define OMNIPQ_ARKIT_RECORD_INTS 5
+
+int omnipq_arkit_pc(int first, int b, int q, int k2, const float *quad_center, const float *normal_vector,
+                    const float *quad_size, const float *quad_scores, const float *center_label, const float *size_label,
+                    const long long *num_gt_boxes, long long count_stride, int *record, double *scene_sums, float *out,
+                    void *stream);
+
+/* g_out float[1] = dLoss/dloss -> g_quad_center, g_normal_vector (first + b, q, 3): every element is written exactly once by
+ * this launch -- zero for the scenes below `first` and in z; in x and y of the unlabelled scenes, with S = the pairs inside
+ * with delta < 0 and sgn = rev_j ? -1 : 1,
+ *   d loss / d c.xy = gate_j |S| (a, b) / n_s;      d loss / d n.xy = -gate_j sgn sum_S (p - c.xy) / n_s.
+ * Nothing flows to quad_scores, quad_size or the labels. */
+int omnipq_arkit_pc_grad(int first, int b, int q, int k2, const float *quad_center, const float *normal_vector,
+                         const float *quad_size, const float *quad_scores, const float *center_label, const float *size_label,
+                         const long long *num_gt_boxes, long long count_stride, const int *record, const float *g_out,
+                         float *g_quad_center, float *g_normal_vector, void *stream);
 
 #ifdef __cplusplus
 }
