@@ -200,14 +200,22 @@ __device__ __forceinline__ float xor32(float v) { return __shfl_xor(v, 32, 64); 
 // dK/dV) sit on gx different XCDs and each L2 fetches the slice for itself.  This mapping keeps the workgroups of one
 // (batch, head) on one XCD (g_y % 8 == 0; otherwise the plain reading): id = x + gx * y, xcd = id % 8, slot = id / 8 ->
 // nh = xcd + 8 * (slot / gx), block = slot % gx.  A bijection of the same grid.
+// att_block_of: the same for workgroup `id` (launch order) of a grid of gx blocks x gy (batch, head)s.
+__device__ __forceinline__ void att_block_of(const AttnArgs &g, int id, int gx, int gy, int &blk, int &nh) {
+  if (g.xcd_map && (gy & 7) == 0) {
+    const int slot = id >> 3;
+    nh = (id & 7) + 8 * (slot / gx);
+    blk = slot % gx;
+  } else {
+    nh = id / gx;
+    blk = id - nh * gx;
+  }
+}
+
 __device__ __forceinline__ void att_block(const AttnArgs &g, int &blk, int &nh) {
   const int gx = (int)gridDim.x, gy = (int)gridDim.y;
   blk = (int)blockIdx.x, nh = (int)blockIdx.y;
-  if (g.xcd_map && (gy & 7) == 0) {
-    const int id = blk + gx * nh, slot = id >> 3;
-    nh = (id & 7) + 8 * (slot / gx);
-    blk = slot % gx;
-  }
+  if (g.xcd_map && (gy & 7) == 0) att_block_of(g, blk + gx * nh, gx, gy, blk, nh);
 }
 
 #define MFMA(a, b, c) mfma_e16_32x32x16(a, b, c)
@@ -358,16 +366,18 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs g, const e16_t *
 }
 
 // ---- backward, dQ ---------------------------------------------------------------------------------------
-// grid (ceil(L/32), N*H).  Also writes delta[N*H][L] = sum_d dO*O for the dK/dV kernel.
-__global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs g, const e16_t *__restrict__ Q,
-                                                         const e16_t *__restrict__ K, const e16_t *__restrict__ V,
-                                                         const e16_t *__restrict__ O, const e16_t *__restrict__ dO,
-                                                         const float *__restrict__ lse2, float *__restrict__ delta,
-                                                         e16_t *__restrict__ dQ, long long dq_sl, long long dq_sn) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[4 * 64 * 33 * 4];
+// The backward pass is two programs, each the body of a workgroup: dQ (32 queries of one (batch, head), all keys) and dK/dV
+// (128 keys, all queries).  They share no data -- each forms delta = sum_d dO*O for itself -- so they run as the two roles
+// of ONE launch (attn_bwd_kernel), or alone (attn_bwd_dq_kernel, attn_bwd_dkdv_kernel).
+// dQ: block `blk` of ceil(L/32), smem of 4 * 64 * 33 * 4 bytes.  Also writes delta[N*H][L] (an output of the C ABI; dK/dV
+// reads it only in its DELTA_IN form, the two dependent launches of omnipq_attn_bwd_mode(0)).
+__device__ __forceinline__ void attn_bwd_dq_program(const AttnArgs &g, int blk, int nh, unsigned char *smem,
+                                                    const e16_t *__restrict__ Q, const e16_t *__restrict__ K,
+                                                    const e16_t *__restrict__ V, const e16_t *__restrict__ O,
+                                                    const e16_t *__restrict__ dO, const float *__restrict__ lse2,
+                                                    float *__restrict__ delta, e16_t *__restrict__ dQ, long long dq_sl,
+                                                    long long dq_sn) {
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), h = lane >> 5, ql = lane & 31;
-  int blk, nh;
-  att_block(g, blk, nh);
   const int n = nh / g.H, hd = nh - n * g.H;
   const int q0 = blk * 32, q = q0 + ql;
   const bool qv = q < g.L;
@@ -466,27 +476,55 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs g, const e16_
   }
 }
 
-// ---- backward, dK and dV --------------------------------------------------------------------------------
-// grid (ceil(S/128), N*H).  Each WAVE owns 32 keys and walks over all query blocks, so there is nothing to
-// merge; the four waves of a workgroup share the staged Q / dO block and the per-query lse / delta.
-__global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(AttnArgs g, const e16_t *__restrict__ Q,
-                                                           const e16_t *__restrict__ K, const e16_t *__restrict__ V,
-                                                           const e16_t *__restrict__ dO, const float *__restrict__ lse2,
-                                                           const float *__restrict__ delta, e16_t *__restrict__ dK,
-                                                           long long dk_sl, long long dk_sn, e16_t *__restrict__ dV,
-                                                           long long dv_sl, long long dv_sn) {
-  __shared__ __attribute__((aligned(16))) e16_t qs[2 * ATT_AREA];       // the staged Q block, then the dO block
-  __shared__ float rowv[64];                                               // [0,32) lse2, [32,64) delta
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), h = lane >> 5, kl = lane & 31;
+constexpr int ATT_DQ_SMEM = 4 * 64 * 33 * 4;      // bytes: the four waves' accumulators at the merge (the staged areas fit inside)
+
+// grid (ceil(L/32), N*H)
+__global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs g, const e16_t *__restrict__ Q,
+                                                         const e16_t *__restrict__ K, const e16_t *__restrict__ V,
+                                                         const e16_t *__restrict__ O, const e16_t *__restrict__ dO,
+                                                         const float *__restrict__ lse2, float *__restrict__ delta,
+                                                         e16_t *__restrict__ dQ, long long dq_sl, long long dq_sn) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[ATT_DQ_SMEM];
   int blk, nh;
   att_block(g, blk, nh);
+  attn_bwd_dq_program(g, blk, nh, smem, Q, K, V, O, dO, lse2, delta, dQ, dq_sl, dq_sn);
+}
+
+// ---- backward, dK and dV --------------------------------------------------------------------------------
+// Block `blk` of ceil(S/128).  Each WAVE owns 32 keys and walks over all query blocks, so there is nothing to
+// merge; the four waves of a workgroup share the staged Q / dO / O block and the per-query lse.
+// delta[q] = sum_d dO*O of the block's 32 queries is formed here, by every wave for itself, from the staged dO and O blocks:
+// the same fragments (lane = query, channels [16 j + 8 h, +8)), frag_dot's order of products, the sum over j and the add
+// across the lane halves as in the dQ program, and the pad channels are the same exact zeros -- bit for bit the value dQ
+// writes to `delta`, without waiting for it.  DELTA_IN = true is the program as it was: no O block, delta read from memory
+// (written by a dQ launch earlier on the stream).
+template <bool DELTA_IN>
+struct DkdvSmem {
+  static constexpr int areas = DELTA_IN ? 2 : 3;                  // the staged Q block, the dO block, the O block
+  static constexpr int rows = DELTA_IN ? 64 : 32 + 4 * 32;        // f32: [0,32) lse2, then delta: [32,64) read / per wave [32] formed
+  static constexpr int bytes = areas * ATT_AREA * 2 + rows * 4;
+};
+
+template <bool DELTA_IN>
+__device__ __forceinline__ void attn_bwd_dkdv_program(const AttnArgs &g, int blk, int nh, unsigned char *smem,
+                                                      const e16_t *__restrict__ Q, const e16_t *__restrict__ K,
+                                                      const e16_t *__restrict__ V, const e16_t *__restrict__ O,
+                                                      const e16_t *__restrict__ dO, const float *__restrict__ lse2,
+                                                      const float *__restrict__ delta, e16_t *__restrict__ dK,
+                                                      long long dk_sl, long long dk_sn, e16_t *__restrict__ dV,
+                                                      long long dv_sl, long long dv_sn) {
+  constexpr int AREAS = DkdvSmem<DELTA_IN>::areas;
+  e16_t *qs = reinterpret_cast<e16_t *>(smem);
+  float *rowv = reinterpret_cast<float *>(smem + AREAS * ATT_AREA * 2);
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), h = lane >> 5, kl = lane & 31;
   const int n = nh / g.H, hd = nh - n * g.H;
   const int kb0 = blk * 128, k0 = kb0 + wave * 32, key = k0 + kl;
   const bool kv = key < g.S;
   const e16_t *Qb = Q + n * g.q_sn + hd * g.D, *Kb = K + n * g.k_sn + hd * g.D, *Vb = V + n * g.v_sn + hd * g.D;
-  const e16_t *dOb = dO + n * g.o_sn + hd * g.D;
-  e16_t *dos = qs + ATT_AREA;
-  for (int o = tid * 4; o < 2 * ATT_AREA; o += 1024) *reinterpret_cast<v2u *>(qs + o) = v2u{0u, 0u};   // the pad channels stay zero
+  const e16_t *dOb = dO + n * g.o_sn + hd * g.D, *Ob = DELTA_IN ? dOb : O + n * g.o_sn + hd * g.D;
+  e16_t *dos = qs + ATT_AREA, *os = qs + (AREAS - 1) * ATT_AREA;
+  float *rowd = DELTA_IN ? rowv + 32 : rowv + 32 + wave * 32;          // the deltas this wave reads
+  for (int o = tid * 4; o < AREAS * ATT_AREA; o += 1024) *reinterpret_cast<v2u *>(qs + o) = v2u{0u, 0u};   // the pad channels stay zero
 
   e16x8 kf[3], vf[3];
   {
@@ -518,8 +556,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(AttnArgs g, const e1
     dvo[i] = has ? (unsigned)(tok * (int)g.o_sl + off) * 2u : ATT_OOB;
     plds[i] = has ? tok * ATT_PITCH + off : 32 * ATT_PITCH;
   }
-  const float *rowsrc = (tid < 32 ? lse2 : delta) + (long long)nh * g.L;
-  v2u qn[2], dn[2];
+  constexpr int NROW = DELTA_IN ? 64 : 32;                  // threads that carry a per-query value: lse2 (and delta)
+  const float *rowsrc = (tid < 32 || !DELTA_IN ? lse2 : delta) + (long long)nh * g.L;
+  v2u qn[2], dn[2], on[2];
   float rown = 0.f;
   auto fetch = [&](int q0) {
     const rsrc_t rq = att_rsrc(Qb, g.q_sl, q0, g.L, g.D), rdo = att_rsrc(dOb, g.o_sl, q0, g.L, g.D);
@@ -528,16 +567,24 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(AttnArgs g, const e1
       qn[i] = att_load8(rq, qvo[i]);
       dn[i] = att_load8(rdo, dvo[i]);
     }
-    rown = (tid < 64 && q0 + (tid & 31) < g.L) ? rowsrc[q0 + (tid & 31)] : 0.f;
+    if (!DELTA_IN) {
+      const rsrc_t ro = att_rsrc(Ob, g.o_sl, q0, g.L, g.D);       // O has dO's strides: the same piece offsets
+#pragma unroll
+      for (int i = 0; i < 2; ++i) on[i] = att_load8(ro, dvo[i]);
+    }
+    rown = (tid < NROW && q0 + (tid & 31) < g.L) ? rowsrc[q0 + (tid & 31)] : 0.f;
   };
   fetch(0);
   const int nqb = (g.L + 31) >> 5;
   __syncthreads();                                          // the areas are cleared
   for (int it = 0; it < nqb; ++it) {
     const int q0 = it * 32;
-    v2u qc[2], dc[2];
+    v2u qc[2], dc[2], oc[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) qc[i] = qn[i], dc[i] = dn[i];
+    for (int i = 0; i < 2; ++i) {
+      qc[i] = qn[i], dc[i] = dn[i];
+      if (!DELTA_IN) oc[i] = on[i];
+    }
     const float rowc = rown;
     if (it + 1 < nqb) fetch(q0 + 32);
     __syncthreads();                                        // the previous block has been consumed
@@ -545,8 +592,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(AttnArgs g, const e1
     for (int i = 0; i < 2; ++i) {
       *reinterpret_cast<v2u *>(qs + plds[i]) = qc[i];
       *reinterpret_cast<v2u *>(dos + plds[i]) = dc[i];
+      if (!DELTA_IN) *reinterpret_cast<v2u *>(os + plds[i]) = oc[i];
     }
-    if (tid < 64) rowv[tid] = rowc;
+    if (tid < NROW) rowv[tid] = rowc;
     __syncthreads();
     f32x16 s, dp;
 #pragma unroll
@@ -555,6 +603,20 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(AttnArgs g, const e1
     for (int j = 0; j < 3; ++j) {
       s = MFMA(frag_lds_tok(qs, kl, j, h), kf[j], s);             // S: rows = queries, cols = keys
       dp = MFMA(frag_lds_tok(dos, kl, j, h), vf[j], dp);          // dO V^T
+    }
+    if (!DELTA_IN) {
+      // the block's 32 deltas, lane = query, while the matrix instructions above are in flight; handed from the lane that
+      // holds a query to the lanes that hold its accumulator rows through the wave's own 32 floats (a wave's LDS
+      // instructions execute in program order: no workgroup barrier)
+      float dl = 0.f;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) dl += frag_dot(frag_lds_tok(dos, kl, j, h), frag_lds_tok(os, kl, j, h));
+      dl += xor32(dl);
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      if (h == 0) rowd[kl] = dl;
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
     }
     float pt[16], ds[16];
     const bool full = q0 + 32 <= g.L && k0 + 32 <= g.S;    // wave-uniform
@@ -577,7 +639,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(AttnArgs g, const e1
       }
     }
 #pragma unroll
-    for (int r = 0; r < 16; ++r) ds[r] *= dp[r] - rowv[32 + acc_row(r, h)];
+    for (int r = 0; r < 16; ++r) ds[r] *= dp[r] - rowd[acc_row(r, h)];
 #pragma unroll
     for (int j2 = 0; j2 < 2; ++j2) {
       const e16x8 pf = pack_regs(pt, j2), df = pack_regs(ds, j2);
@@ -602,6 +664,50 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(AttnArgs g, const e1
         }
       }
     }
+  }
+}
+
+// grid (ceil(S/128), N*H).  DELTA_IN: `delta` is read (O is not); otherwise O is read (`delta` is not).
+template <bool DELTA_IN>
+__global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(AttnArgs g, const e16_t *__restrict__ Q,
+                                                           const e16_t *__restrict__ K, const e16_t *__restrict__ V,
+                                                           const e16_t *__restrict__ O, const e16_t *__restrict__ dO,
+                                                           const float *__restrict__ lse2, const float *__restrict__ delta,
+                                                           e16_t *__restrict__ dK, long long dk_sl, long long dk_sn,
+                                                           e16_t *__restrict__ dV, long long dv_sl, long long dv_sn) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[DkdvSmem<DELTA_IN>::bytes];
+  int blk, nh;
+  att_block(g, blk, nh);
+  attn_bwd_dkdv_program<DELTA_IN>(g, blk, nh, smem, Q, K, V, O, dO, lse2, delta, dK, dk_sl, dk_sn, dV, dv_sl, dv_sn);
+}
+
+// ---- backward, both programs in one launch ----------------------------------------------------------------
+// grid (ceil(S/128) + ceil(L/32), N*H).  Neither program waits for the other (no workgroup ever waits for a workgroup of
+// its grid), so the chip is filled by both at once: a dK/dV workgroup is a long chain (all query blocks, two barriers
+// each) of which a launch of its own has one per compute unit at the decoder's shapes.  Launch order is ROLE-MAJOR: the
+// first ceil(S/128) * N*H workgroups of the grid (x fastest) are ALL the dK/dV blocks, the rest the dQ blocks -- every long
+// workgroup starts at once and the short dQ workgroups fill in beside and behind them.  (Interleaved per (batch, head) the
+// dK/dV blocks of the later (batch, head)s queue behind two rounds of dQ blocks and the launch ends with their chains.)
+// Within each role att_block_of keeps the blocks of a (batch, head) on one XCD, and -- N*H a multiple of 8 -- it is the same
+// XCD for both roles, which then share Q, K, V and dO in one L2.  The role is a test on the workgroup's index: uniform.
+__global__ __launch_bounds__(256) void attn_bwd_kernel(AttnArgs g, const e16_t *__restrict__ Q, const e16_t *__restrict__ K,
+                                                      const e16_t *__restrict__ V, const e16_t *__restrict__ O,
+                                                      const e16_t *__restrict__ dO, const float *__restrict__ lse2,
+                                                      float *__restrict__ delta, e16_t *__restrict__ dQ, long long dq_sl,
+                                                      long long dq_sn, e16_t *__restrict__ dK, long long dk_sl,
+                                                      long long dk_sn, e16_t *__restrict__ dV, long long dv_sl,
+                                                      long long dv_sn) {
+  static_assert(DkdvSmem<false>::bytes <= ATT_DQ_SMEM, "one buffer of the larger size");
+  __shared__ __attribute__((aligned(16))) unsigned char smem[ATT_DQ_SMEM];
+  const int gy = (int)gridDim.y, gk = (g.S + 127) >> 7, gq = (int)gridDim.x - gk;
+  const int id = (int)blockIdx.x + (int)gridDim.x * (int)blockIdx.y;
+  int blk, nh;
+  if (id < gk * gy) {
+    att_block_of(g, id, gk, gy, blk, nh);
+    attn_bwd_dkdv_program<false>(g, blk, nh, smem, Q, K, V, O, dO, lse2, nullptr, dK, dk_sl, dk_sn, dV, dv_sl, dv_sn);
+  } else {
+    att_block_of(g, id - gk * gy, gq, gy, blk, nh);
+    attn_bwd_dq_program(g, blk, nh, smem, Q, K, V, O, dO, lse2, delta, dQ, dq_sl, dq_sn);
   }
 }
 
@@ -673,6 +779,23 @@ extern "C" int omnipq_attn_fwd(int N, int H, int L, int S, int D, const void *q,
   return OMNIPQ_OK;
 }
 
+namespace omnipq {
+
+static int g_attn_bwd_mode = 1;    // omnipq_attn_bwd_mode
+
+// the gradient tensors' strides (pairs of token, batch; n tensors): multiples of 4, token strides as token_strides_ok says
+static int grad_strides_ok(const long long *gs, int n, int L, int S, int D) {
+  for (int i = 0; i < 2 * n; ++i)
+    if (gs[i] % 4) return OMNIPQ_EINVAL;
+  return token_strides_ok(gs, n, L, S, D);
+}
+
+}  // namespace omnipq
+
+// Timing aid: 0 = omnipq_attn_bwd issues the dQ launch and then a dK/dV launch that reads the `delta` the first one wrote,
+// 1 (default) = one launch with both programs.  Same results either way.
+extern "C" void omnipq_attn_bwd_mode(int mode) { omnipq::g_attn_bwd_mode = mode ? 1 : 0; }
+
 extern "C" int omnipq_attn_bwd(int N, int H, int L, int S, int D, const void *q, const void *k, const void *v,
                                const void *o, const void *d_o, const long long *strides, const float *lse2,
                                float *delta, void *dq, void *dk, void *dv, const long long *grad_strides,
@@ -683,16 +806,57 @@ extern "C" int omnipq_attn_bwd(int N, int H, int L, int S, int D, const void *q,
     return OMNIPQ_EINVAL;
   const int rc = fill_args(g, N, H, L, S, D, strides, dropout_p, seed_ptr, salt);
   if (rc) return rc;
-  for (int i = 0; i < 6; ++i)
-    if (grad_strides[i] % 4) return OMNIPQ_EINVAL;
-  if (const int rs = token_strides_ok(grad_strides, 3, L, S, D)) return rs;
+  if (const int rs = grad_strides_ok(grad_strides, 3, L, S, D)) return rs;
+  const int gq = (L + 31) / 32, gk = (S + 127) / 128;
+  if (g_attn_bwd_mode) {
+    attn_bwd_kernel<<<dim3(gk + gq, N * H), 256, 0, (hipStream_t)stream>>>(
+        g, (const e16_t *)q, (const e16_t *)k, (const e16_t *)v, (const e16_t *)o, (const e16_t *)d_o, lse2, delta,
+        (e16_t *)dq, grad_strides[0], grad_strides[1], (e16_t *)dk, grad_strides[2], grad_strides[3], (e16_t *)dv,
+        grad_strides[4], grad_strides[5]);
+    OMNIPQ_LAUNCH_CHECK();
+    return OMNIPQ_OK;
+  }
+  attn_bwd_dq_kernel<<<dim3(gq, N * H), 256, 0, (hipStream_t)stream>>>(
+      g, (const e16_t *)q, (const e16_t *)k, (const e16_t *)v, (const e16_t *)o, (const e16_t *)d_o, lse2, delta,
+      (e16_t *)dq, grad_strides[0], grad_strides[1]);
+  OMNIPQ_LAUNCH_CHECK();
+  attn_bwd_dkdv_kernel<true><<<dim3(gk, N * H), 256, 0, (hipStream_t)stream>>>(
+      g, (const e16_t *)q, (const e16_t *)k, (const e16_t *)v, nullptr, (const e16_t *)d_o, lse2, delta, (e16_t *)dk,
+      grad_strides[2], grad_strides[3], (e16_t *)dv, grad_strides[4], grad_strides[5]);
+  OMNIPQ_LAUNCH_CHECK();
+  return OMNIPQ_OK;
+}
+
+extern "C" int omnipq_attn_bwd_dq(int N, int H, int L, int S, int D, const void *q, const void *k, const void *v,
+                                  const void *o, const void *d_o, const long long *strides, const float *lse2,
+                                  float *delta, void *dq, const long long *grad_strides, float dropout_p,
+                                  const unsigned long long *seed_ptr, unsigned salt, void *stream) {
+  using namespace omnipq;
+  AttnArgs g;
+  if (!q || !k || !v || !o || !d_o || !strides || !lse2 || !delta || !dq || !grad_strides) return OMNIPQ_EINVAL;
+  const int rc = fill_args(g, N, H, L, S, D, strides, dropout_p, seed_ptr, salt);
+  if (rc) return rc;
+  if (const int rs = grad_strides_ok(grad_strides, 1, L, S, D)) return rs;
   attn_bwd_dq_kernel<<<dim3((L + 31) / 32, N * H), 256, 0, (hipStream_t)stream>>>(
       g, (const e16_t *)q, (const e16_t *)k, (const e16_t *)v, (const e16_t *)o, (const e16_t *)d_o, lse2, delta,
       (e16_t *)dq, grad_strides[0], grad_strides[1]);
   OMNIPQ_LAUNCH_CHECK();
-  attn_bwd_dkdv_kernel<<<dim3((S + 127) / 128, N * H), 256, 0, (hipStream_t)stream>>>(
-      g, (const e16_t *)q, (const e16_t *)k, (const e16_t *)v, (const e16_t *)d_o, lse2, delta, (e16_t *)dk,
-      grad_strides[2], grad_strides[3], (e16_t *)dv, grad_strides[4], grad_strides[5]);
+  return OMNIPQ_OK;
+}
+
+extern "C" int omnipq_attn_bwd_dkdv(int N, int H, int L, int S, int D, const void *q, const void *k, const void *v,
+                                    const void *o, const void *d_o, const long long *strides, const float *lse2, void *dk,
+                                    void *dv, const long long *grad_strides, float dropout_p,
+                                    const unsigned long long *seed_ptr, unsigned salt, void *stream) {
+  using namespace omnipq;
+  AttnArgs g;
+  if (!q || !k || !v || !o || !d_o || !strides || !lse2 || !dk || !dv || !grad_strides) return OMNIPQ_EINVAL;
+  const int rc = fill_args(g, N, H, L, S, D, strides, dropout_p, seed_ptr, salt);
+  if (rc) return rc;
+  if (const int rs = grad_strides_ok(grad_strides, 2, L, S, D)) return rs;
+  attn_bwd_dkdv_kernel<false><<<dim3((S + 127) / 128, N * H), 256, 0, (hipStream_t)stream>>>(
+      g, (const e16_t *)q, (const e16_t *)k, (const e16_t *)v, (const e16_t *)o, (const e16_t *)d_o, lse2, nullptr,
+      (e16_t *)dk, grad_strides[0], grad_strides[1], (e16_t *)dv, grad_strides[2], grad_strides[3]);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }

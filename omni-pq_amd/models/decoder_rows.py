@@ -375,13 +375,15 @@ def run(layer, query, key, query_pos, key_pos, kv=None):
                                            pdrop(layer.dropout1), q_pe, True, False)
 
     # cross attention: query x + q_pe, key = value = mem + k_pe (:208-213)
+    kv_stream = None
     if kv is None:
         kv = key_side(layer, key, key_pos)
     else:
         join_key_sides(query.device, kv[2] if len(kv) > 2 else None)
+        kv_stream = _side_stream(query.device)      # where kv's gradient is consumed: dK/dV is launched there in backward
     kv, (wq, bq) = kv[0], kv[1]
     q = linear(xq, wq, bq)
-    att = fused_attention.PackedAttention.apply(q, kv, Pq, Pk, B, H, float(ca.dropout) if training else 0.0)
+    att = fused_attention.PackedAttention.apply(q, kv, Pq, Pk, B, H, float(ca.dropout) if training else 0.0, kv_stream)
     y = linear(att, ca.out_proj.weight, ca.out_proj.bias)
     x32, x16, _ = AddDropoutLayerNorm.apply(x32, y, layer.norm2.weight, layer.norm2.bias, float(layer.norm2.eps),
                                             pdrop(layer.dropout2), None, True, True)

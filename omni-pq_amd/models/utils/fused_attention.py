@@ -13,6 +13,10 @@ import sa_fused
 from sa_fused import E16, _call, _lib, _p
 
 MAX_HEAD_DIM = 48
+# Cross attention whose key side was computed on a side stream (decoder_rows.precompute_key_sides): launch dK/dV on that
+# stream in backward -- nothing on the calling stream reads them, and their consumers run there already.  OFF: in the
+# captured step the six extra edges from the main stream into the key-side branch cost 3.2 ms.
+CROSS_DKDV_SIDE = False
 
 
 from dropout_state import STATE  # noqa: E402  (shared with the other dropout sites of the decoder)
@@ -94,7 +98,10 @@ class PackedAttention(torch.autograd.Function):
         a (N*L, 3E), b None        self attention on a packed q|k|v projection
         a (N*L, E),  b (N*S, 2E)   cross attention, b = packed k|v projection
     -> (N*L, E).  The gradient comes back in the same packed form (dq|dk|dv written side by side by the
-    kernels), so autograd sees one tensor in, one tensor out -- no split / cat around the call."""
+    kernels), so autograd sees one tensor in, one tensor out -- no split / cat around the call.
+    kv_stream (cross attention only): the stream `b` was produced on and its gradient is consumed on.  Backward then
+    issues dQ on the current stream and dK/dV on kv_stream (the two do not depend on each other), without joining:
+    the caller's graph already makes kv_stream's consumers of `db` wait for this node."""
 
     @staticmethod
     def _pointers(a, b, E, L, S):
@@ -105,8 +112,9 @@ class PackedAttention(torch.autograd.Function):
         return (a.data_ptr(), kb, kb + 2 * E), [E, L * E, 2 * E, S * 2 * E, 2 * E, S * 2 * E]
 
     @staticmethod
-    def forward(ctx, a, b, L, S, N, H, dropout_p):
+    def forward(ctx, a, b, L, S, N, H, dropout_p, kv_stream=None):
         ctx.e16 = E16.dtype
+        ctx.kv_stream = kv_stream if b is not None else None
         E = a.shape[1] // 3 if b is None else a.shape[1]
         D = E // H
         (qp, kp, vp), st = PackedAttention._pointers(a, b, E, L, S)
@@ -131,15 +139,27 @@ class PackedAttention(torch.autograd.Function):
         d_o = d_o.to(E16.dtype).contiguous()
         (qp, kp, vp), st = PackedAttention._pointers(a, b, E, L, S)
         da = torch.empty_like(a)
-        db = torch.empty_like(b) if b is not None else None
-        (dqp, dkp, dvp), gst = PackedAttention._pointers(da, db, E, L, S)
         delta = torch.empty_like(lse)
         strides = (ctypes.c_longlong * 8)(*(st + [E, L * E]))
-        gstrides = (ctypes.c_longlong * 6)(*gst)
-        _call(_lib.omnipq_attn_bwd, a, N, H, L, S, D, ctypes.c_void_p(qp), ctypes.c_void_p(kp), ctypes.c_void_p(vp),
-              _p(o), _p(d_o), strides, _p(lse), _p(delta), ctypes.c_void_p(dqp), ctypes.c_void_p(dkp),
-              ctypes.c_void_p(dvp), gstrides, dropout_p, _p(seed), salt)
-        return da, db, None, None, None, None, None
+        ptrs = (ctypes.c_void_p(qp), ctypes.c_void_p(kp), ctypes.c_void_p(vp), _p(o), _p(d_o), strides, _p(lse))
+        side = ctx.kv_stream if CROSS_DKDV_SIDE else None
+        if side is None:
+            db = torch.empty_like(b) if b is not None else None
+            (dqp, dkp, dvp), gst = PackedAttention._pointers(da, db, E, L, S)
+            _call(_lib.omnipq_attn_bwd, a, N, H, L, S, D, *ptrs, _p(delta), ctypes.c_void_p(dqp), ctypes.c_void_p(dkp),
+                  ctypes.c_void_p(dvp), (ctypes.c_longlong * 6)(*gst), dropout_p, _p(seed), salt)
+            return da, db, None, None, None, None, None, None
+        side.wait_stream(torch.cuda.current_stream(a.device))         # d_o (and, in eager mode, the allocator's reuse of db)
+        with torch.cuda.stream(side):
+            db = torch.empty_like(b)
+            (_, dkp, dvp), gst = PackedAttention._pointers(da, db, E, L, S)
+            _call(_lib.omnipq_attn_bwd_dkdv, a, N, H, L, S, D, *ptrs, ctypes.c_void_p(dkp), ctypes.c_void_p(dvp),
+                  (ctypes.c_longlong * 4)(*gst[2:]), dropout_p, _p(seed), salt)
+        for t in (a, b, o, d_o, lse):
+            t.record_stream(side)                                     # the saved references die when this node returns
+        _call(_lib.omnipq_attn_bwd_dq, a, N, H, L, S, D, *ptrs, _p(delta), _p(da), (ctypes.c_longlong * 2)(*gst[:2]),
+              dropout_p, _p(seed), salt)
+        return da, db, None, None, None, None, None, None
 
 
 def packed_usable(a, b, H):
