@@ -64,6 +64,14 @@ const char *omnipq_error_string(int code);
  * e.g. "omnipq_furthest_point_sampling_resume i iiiiipppup".  Written from these headers when the library is built, so a
  * binding declares its calls from the library it loaded instead of parsing a header that may belong to another build. */
 const char *omnipq_entry_point_signatures(void);
+/* What else crosses this boundary, sorted, one line each, written from these headers like the signatures:
+ *   define NAME value                       every `#define OMNIPQ_* <integer>` (a `u` suffix dropped)
+ *   struct name field:t field:t*n ...       every `typedef struct {...} omnipq_*;`, fields in declaration order
+ * t is a parameter letter above or L unsigned long long; every pointer field is p; *n is an array length (a define used as
+ * the dimension already resolved), e.g. "struct omnipq_mt_grads center:p*8 objectness_scores:p*8 ...".  A binding builds
+ * its descriptors and reads its limits from this text; the build asserts that it states the layout the compiler uses.
+ * Added under 5 (additive). */
+const char *omnipq_abi_records(void);
 /* Measurement helper: dst[0..bytes) = src[0..bytes) (bytes % 16 == 0) with the streaming shape that reaches this chip's
  * highest copy rate -- the "measured copy ceiling" bench.py reports next to the 8 TB/s datasheet peak. */
 int omnipq_copy_probe(const void *src, void *dst, long long bytes, void *stream);

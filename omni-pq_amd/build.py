@@ -8,6 +8,7 @@
 No torch, no hipify, no cmake: one hipcc invocation per translation unit and element type, one link each.
 hipcc cross-compiles gfx950 code objects on a machine without a GPU.
 """
+import ctypes
 import os
 import subprocess
 import sys
@@ -108,15 +109,117 @@ def entry_point_signatures():
     return "".join(line + "\n" for line in sorted(lines))
 
 
+_FIELDS = dict(_SCALARS, **{"unsigned long long": "L"})
+_FIELD_CTYPES = {"i": ctypes.c_int, "u": ctypes.c_uint, "l": ctypes.c_longlong, "L": ctypes.c_ulonglong, "f": ctypes.c_float,
+                 "d": ctypes.c_double, "p": ctypes.c_void_p}
+
+
+def _parse_declarator(text):
+    """`x`, `*x`, `y[N]` -> (field, is_pointer, dimension or None); None for anything else (`z[2][2]`, `(*f)(int)`)"""
+    import re
+    m = re.fullmatch(r"\s*((?:\*\s*)*)(\w+)\s*(?:\[\s*(\w+)\s*\])?\s*", text)
+    return m and (m.group(2), bool(m.group(1)), m.group(3))
+
+
+def _struct_fields(body, defines):
+    """`field:t` / `field:t*n` per field of a struct body without comments.  ValueError(field): its type has no letter."""
+    import re
+    for stmt in body.split(";"):
+        if not stmt.strip():
+            continue
+        # `const float *x, *y[N]`: the type stands once in front, every name carries its own `*` and `[n]`
+        head = re.match(r"(.*?)((?:\*\s*)*\w+\s*(?:\[.*\])?)$", stmt.split(",")[0].strip())
+        if not head:
+            raise ValueError(stmt.strip())
+        base = _FIELDS.get(" ".join(w for w in head.group(1).split() if w != "const"))
+        for text in [head.group(2)] + stmt.split(",")[1:]:
+            parsed = _parse_declarator(text)
+            if parsed is None:
+                raise ValueError(text.strip())
+            field, is_pointer, dim = parsed
+            letter = "p" if is_pointer else base
+            count = None if dim is None else int(dim) if dim.isdigit() else defines.get(dim)
+            if letter is None or (dim is not None and count is None):
+                raise ValueError(field)
+            yield f"{field}:{letter}" if dim is None else f"{field}:{letter}*{count}"
+
+
+def abi_records():
+    """What crosses the C ABI besides the calls, as sorted text: `define NAME value` per `#define OMNIPQ_* <decimal integer>` of
+    include/*.h (a `u` / `l` suffix dropped; include guards have no value and are not listed) and
+    `struct name field:t field:t*n ...` per `typedef struct {...} omnipq_*;`, fields in the header's order.  t is a letter of
+    entry_point_signatures() or L unsigned long long; every pointer is p; *n is an array length, a define already resolved.
+    Compiled into the library like the signatures (csrc/capi.hip: omnipq_abi_records) so that a binding builds its
+    ctypes.Structure classes from the library it loaded.  A field whose type is not in this list fails the build."""
+    import re
+    texts = []
+    inc = os.path.join(REPO, "include")
+    for header in sorted(f for f in os.listdir(inc) if f.endswith(".h")):
+        with open(os.path.join(inc, header)) as fh:
+            texts.append((header, re.sub(r"/\*.*?\*/", " ", fh.read(), flags=re.S)))
+    defines = {}
+    for header, text in texts:
+        for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(OMNIPQ_\w+)[ \t]+(-?\d+)[uUlL]*[ \t]*$", text, flags=re.M):
+            defines[m.group(1)] = int(m.group(2))
+    lines = [f"define {name} {value}" for name, value in defines.items()]
+    for header, text in texts:
+        for typedef in re.finditer(r"\btypedef\s+struct\b\s*\w*\s*\{(.*?)\}\s*(omnipq_\w+)\s*;", text, flags=re.S):
+            body, struct = typedef.groups()
+            try:
+                nested = re.search(r"\{[^{}]*\}\s*(\w*)", body)
+                if nested:
+                    raise ValueError(nested.group(1))
+                lines.append(" ".join([f"struct {struct}"] + list(_struct_fields(body, defines))))
+            except ValueError as bad:
+                raise RuntimeError(f"{header}: {struct}: field `{bad}` has no record letter") from None
+    return "".join(line + "\n" for line in sorted(lines))
+
+
+def record_struct(line):
+    """`struct name field:t[*n] ...` -> the ctypes.Structure of that record.  The build's copy of what a binding does with the
+    text (pointnet2/_ext.py: struct(), which cannot be imported here: it loads the library this build is about to make);
+    tests/test_capi_symbols.py holds the two to the same fields."""
+    _, name, *fields = line.split()
+    members = []
+    for field in fields:
+        fname, _, kind = field.partition(":")
+        letter, _, count = kind.partition("*")
+        members.append((fname, _FIELD_CTYPES[letter] * int(count) if count else _FIELD_CTYPES[letter]))
+    return type(name, (ctypes.Structure,), {"_fields_": members})
+
+
+def layout_checks(records):
+    """One static_assert per struct size and field offset of `records` (abi_records() text), the numbers taken from the
+    ctypes.Structure a binding builds from that text: compiled into csrc/capi.hip next to the C definitions, so a layout Python
+    would get wrong stops the build."""
+    out = []
+    for line in records.splitlines():
+        if line.startswith("struct "):
+            cls = record_struct(line)
+            out.append(f'static_assert(sizeof({cls.__name__}) == {ctypes.sizeof(cls)}, "{cls.__name__}: size");')
+            out += [f'static_assert(offsetof({cls.__name__}, {f}) == {getattr(cls, f).offset}, "{cls.__name__}.{f}: offset");'
+                    for f, _ in cls._fields_]
+    return "".join(s + "\n" for s in out)
+
+
+GENERATED = ("entry_points.inc", "abi_records.inc", "abi_layout_checks.inc")
+
+
+def _c_string(text):
+    return "".join(f'"{line}\\n"\n' for line in text.splitlines())
+
+
 def _write_generated():
-    """build/generated/entry_points.inc: the text above as C string literals, rewritten only when its content changes."""
+    """build/generated/: the two texts above as C string literals and the layout checks, each rewritten only when its content
+    changes."""
     gen = os.path.join(OBJDIR, "generated")
     os.makedirs(gen, exist_ok=True)
-    path = os.path.join(gen, "entry_points.inc")
-    text = "".join(f'"{line}\\n"\n' for line in entry_point_signatures().splitlines())
-    if not os.path.exists(path) or open(path).read() != text:
-        with open(path, "w") as fh:
-            fh.write(text)
+    records = abi_records()
+    for name, text in zip(GENERATED, (_c_string(entry_point_signatures()), _c_string(records), layout_checks(records))):
+        path = os.path.join(gen, name)
+        if not os.path.exists(path) or open(path).read() != text:
+            with open(path, "w") as fh:
+                fh.write(text)
     return gen
 
 
@@ -134,7 +237,7 @@ def build(force=False, verbose=False):
     inc = os.path.join(REPO, "include")
     headers += [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")]
     gen = _write_generated()
-    headers.append(os.path.join(gen, "entry_points.inc"))
+    headers += [os.path.join(gen, f) for f in GENERATED]
     procs, links = [], []
     for lib, sub, defines in VARIANTS:
         objdir = os.path.join(OBJDIR, sub)

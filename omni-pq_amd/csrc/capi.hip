@@ -1,5 +1,15 @@
 // Library-level entry points of libomnipq_pointops.so (see include/omnipq_pointops.h).
 #include "common.h"
+#include <stddef.h>
+// every public header: the layout checks below name every struct that crosses the C ABI
+#include "omnipq_attn.h"
+#include "omnipq_data.h"
+#include "omnipq_decoder.h"
+#include "omnipq_eval.h"
+#include "omnipq_f32.h"
+#include "omnipq_loss.h"
+#include "omnipq_optim.h"
+#include "omnipq_semi.h"
 
 extern "C" int omnipq_abi_version(void) { return OMNIPQ_ABI_VERSION; }
 
@@ -10,6 +20,18 @@ extern "C" const char *omnipq_entry_point_signatures(void) {
 #include "entry_points.inc"
       ;
 }
+
+// The integer defines and struct layouts of THIS build (format: include/omnipq_pointops.h), written by omni-pq_amd/build.py
+// from include/*.h like the signatures.
+extern "C" const char *omnipq_abi_records(void) {
+  return
+#include "abi_records.inc"
+      ;
+}
+
+// sizeof / offsetof of every struct above as the ctypes.Structure built from that text lays it out (build.py:
+// layout_checks): a field the text gets wrong stops the build here instead of moving a device pointer.
+#include "abi_layout_checks.inc"
 
 extern "C" const char *omnipq_error_string(int code) {
   switch (code) {

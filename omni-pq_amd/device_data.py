@@ -24,24 +24,16 @@ from pointnet2 import _ext
 
 _lib = _ext._lib
 
-MAX_NUM_OBJ, MAX_NUM_QUAD, MAX_NUM_HQUAD, NUM_PROPOSAL, MAX_INSTANCES = 64, 32, 4, 256, 1024      # include/omnipq_data.h
-META_INTS, LABEL_DOUBLES, PARAM_DOUBLES = 8, 752, 12
+MAX_NUM_OBJ, MAX_NUM_QUAD, MAX_NUM_HQUAD, NUM_PROPOSAL, MAX_INSTANCES, META_INTS, LABEL_DOUBLES, PARAM_DOUBLES = (
+    _ext.const("OMNIPQ_ASM_" + name) for name in ("MAX_OBJ", "MAX_QUAD", "MAX_HQUAD", "NUM_PROPOSAL", "MAX_INSTANCES",
+                                                  "META_INTS", "LABEL_DOUBLES", "PARAM_DOUBLES"))
 MEAN_COLOR_RGB = np.array([109.8, 97.2, 83.8])              # scannet_detection_dataset.py:34
 
-_P, _I, _L = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+_Bank = _ext.struct("omnipq_asm_bank")
+_Batch = _ext.struct("omnipq_asm_batch")
+_Out = _ext.struct("omnipq_asm_out")
 
-
-class _Bank(ctypes.Structure):           # omnipq_asm_bank
-    _fields_ = [("scenes", _I), ("pitch", _I), ("height_col", _I), ("rows_total", _L)] + \
-               [(n, _P) for n in ("points", "normals", "colors", "instance", "semantic", "row_offset", "meta", "labels")]
-
-
-class _Batch(ctypes.Structure):          # omnipq_asm_batch
-    _fields_ = [(n, _I) for n in ("b", "k", "flavour", "n_ids", "n_sizes")] + \
-               [(n, _P) for n in ("scene_slot", "params", "seed", "choices_in", "ema_choices_in", "nyu40ids", "mean_size")]
-
-
-# omnipq_asm_out, in the header's order: (key, trailing shape, dtype, flavours that carry it)
+# the arrays of omnipq_asm_out: (key, trailing shape, dtype, flavours that carry it)
 _f32, _i64, _i32 = torch.float32, torch.int64, torch.int32
 OUT_FIELDS = (("point_clouds", ("k", "pitch"), _f32, (0, 1)), ("vertex_normals", ("k", 3), _f32, (0, 1)),
               ("ema_point_clouds", ("k", "pitch"), _f32, (0, 1)), ("choices", ("k",), _i32, (0, 1)),
@@ -60,13 +52,8 @@ OUT_FIELDS = (("point_clouds", ("k", "pitch"), _f32, (0, 1)), ("vertex_normals",
               ("scale", (), _f32, (0, 1)), ("scan_idx", (), _i64, (0,)))
 # `choices` / `ema_choices` are extensions (the rows drawn); everything else is a key of the reference's item
 
-
-class _Out(ctypes.Structure):            # omnipq_asm_out
-    _fields_ = [(f[0], _P) for f in OUT_FIELDS]
-
-
-def _addr(struct):
-    return ctypes.c_void_p(ctypes.addressof(struct))
+if sorted(f[0] for f in OUT_FIELDS) != sorted(name for name, _ in _Out._fields_):
+    raise ImportError("device_data: OUT_FIELDS and the loaded library's omnipq_asm_out name different arrays")
 
 
 def rotz(t):
@@ -355,11 +342,12 @@ class SceneBank:
                        slots_dev.data_ptr(), params_dev.data_ptr(), self._seed.data_ptr(),
                        None if choices is None else choices.data_ptr(), None if ema_choices is None else ema_choices.data_ptr(),
                        None if ids is None else ids.data_ptr(), None if sizes is None else sizes.data_ptr())
-        outs = _Out(*[out[f[0]].data_ptr() if f[0] in out else None for f in OUT_FIELDS])
+        outs = _Out(**{f[0]: out[f[0]].data_ptr() for f in OUT_FIELDS if f[0] in out})
         ws = out.get("_workspace")
         if ws is None or ws.numel() < int(_lib.omnipq_assemble_workspace_bytes(b)):
             raise ValueError("assemble: out['_workspace'] is missing or too small (make_buffers)")
-        _ext._run(_lib.omnipq_assemble_batch, slots_dev, _addr(bank), _addr(batch), _addr(outs), ctypes.c_void_p(ws.data_ptr()))
+        _ext._run(_lib.omnipq_assemble_batch, slots_dev, ctypes.byref(bank), ctypes.byref(batch), ctypes.byref(outs),
+                  ctypes.c_void_p(ws.data_ptr()))
         # The launches hold raw pointers.  Caller-owned buffers keep what the launches read (a captured graph reads it again
         # on every replay).  Without `out` the slots, parameters and workspace made above are released when this returns: they
         # were allocated on the stream the launches were queued on, and the caching allocator hands a block out again only in

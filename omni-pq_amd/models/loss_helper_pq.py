@@ -48,49 +48,13 @@ GT_VOTE_FACTOR = 3                       # number of GT votes per point
 QUAD_CLS_WEIGHTS = [0.4, 0.6]
 NOT_SOLID_CLASSES = (5, 6, 8, 11)        # door, window, picture, curtain: `not_door_or_window` (:354-357)
 
-MAX_HEADS = 8
-_P = ctypes.c_void_p
-
-
-def _arr(n=MAX_HEADS):
-    return _P * n
-
-
-class _BoxDesc(ctypes.Structure):
-    _fields_ = [("heads", ctypes.c_int), ("b", ctypes.c_int), ("k", ctypes.c_int), ("k2", ctypes.c_int),
-                ("nh", ctypes.c_int), ("ns", ctypes.c_int), ("nc", ctypes.c_int),
-                ("objectness_scores", _arr()), ("center", _arr()), ("heading_scores", _arr()),
-                ("heading_residuals_normalized", _arr()), ("size_scores", _arr()),
-                ("size_residuals_normalized", _arr()), ("sem_cls_scores", _arr()),
-                ("label", _P), ("mask", _P), ("assignment", _P), ("counts", _P), ("gt_center", _P),
-                ("gt_heading_class", _P), ("gt_heading_residual", _P), ("gt_size_class", _P), ("gt_size_residual", _P),
-                ("gt_sem_cls", _P), ("mean_size", _P), ("w_background", ctypes.c_float), ("w_object", ctypes.c_float),
-                ("only_objectness", ctypes.c_int)]
-
-
-class _BoxGrads(ctypes.Structure):
-    _fields_ = [(n, _arr()) for n in ("objectness_scores", "center", "heading_scores", "heading_residuals_normalized",
-                                      "size_scores", "size_residuals_normalized", "sem_cls_scores")]
-
-
-class _QuadDesc(ctypes.Structure):
-    _fields_ = [("heads", ctypes.c_int), ("b", ctypes.c_int), ("k", ctypes.c_int), ("k2", ctypes.c_int),
-                ("quad_scores", _arr()), ("quad_center", _arr()), ("normal_vector", _arr()), ("quad_size", _arr()),
-                ("label", _P), ("mask", _P), ("assignment", _P), ("counts", _P), ("gt_center", _P), ("gt_normal", _P),
-                ("gt_size", _P), ("w_background", ctypes.c_float), ("w_quad", ctypes.c_float)]
-
-
-class _QuadGrads(ctypes.Structure):
-    _fields_ = [(n, _arr()) for n in ("quad_scores", "quad_center", "normal_vector", "quad_size")]
-
-
-class _PcDesc(ctypes.Structure):
-    _fields_ = [("b", ctypes.c_int), ("k", ctypes.c_int), ("k2", ctypes.c_int), ("ns", ctypes.c_int), ("q", ctypes.c_int),
-                ("center", _P), ("size_scores", _P), ("size_residuals", _P), ("object_label", _P),
-                ("object_assignment", _P), ("sem_cls_label", _P), ("mean_size64", _P), ("quad_center", _P),
-                ("normal_vector", _P), ("quad_size", _P), ("quad_label", _P), ("not_solid", ctypes.c_ulonglong)]
-
-
+MAX_HEADS = _ext.const("OMNIPQ_LOSS_MAX_HEADS")
+# the descriptors of include/omnipq_loss.h, laid out as the loaded library reports them
+_BoxDesc = _ext.struct("omnipq_box_rows_desc")
+_BoxGrads = _ext.struct("omnipq_box_rows_grads")
+_QuadDesc = _ext.struct("omnipq_quad_rows_desc")
+_QuadGrads = _ext.struct("omnipq_quad_rows_grads")
+_PcDesc = _ext.struct("omnipq_pc_desc")
 
 BOX_KEYS = ("objectness_scores", "center", "heading_scores", "heading_residuals_normalized", "size_scores",
             "size_residuals_normalized", "sem_cls_scores")

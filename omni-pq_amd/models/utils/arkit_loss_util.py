@@ -32,8 +32,8 @@ _lib = _ext._lib
 
 GATE = 0.1                             # :45; csrc/arkit_pc.hip: kArkGate
 COLLISION = 1e-4                       # loss_helper_pq.py:349; kArkHit
-MAX_BOXES = 256                        # include/omnipq_semi.h: OMNIPQ_ARKIT_MAX_BOXES
-RECORD_INTS = 5                        # OMNIPQ_ARKIT_RECORD_INTS
+MAX_BOXES = _ext.const("OMNIPQ_ARKIT_MAX_BOXES")
+RECORD_INTS = _ext.const("OMNIPQ_ARKIT_RECORD_INTS")
 RECORD_KEYS = ("gate", "rev", "inside", "live", "collisions")
 PREFIX = "last_"                       # :8
 PREDICTION_KEYS = ("quad_center", "normal_vector", "quad_size", "quad_scores")      # in the order of the C ABI

@@ -39,8 +39,8 @@ GM_CLIP = 0.85                         # quantile below which a kept point's ver
 T_STAR = 0.29961316955346434           # root of 40 e^(-19 t) = 0.45 t: what fit_gamma(a1=2, b1=20, a2=3, b2=1, weight=0.1) keeps
 MIN_KEPT = 300                         # fewer kept points: the scene contributes nothing (:78)
 DEFAULT_K = 10000                      # :176
-MAX_K = 15360                          # include/omnipq_semi.h: OMNIPQ_GM_MAX_K
-RECORD_FLOATS = 12                     # include/omnipq_semi.h: OMNIPQ_GM_RECORD_FLOATS
+MAX_K = _ext.const("OMNIPQ_GM_MAX_K")
+RECORD_FLOATS = _ext.const("OMNIPQ_GM_RECORD_FLOATS")
 SEED_SLOT = "gamma_mixture"
 
 

@@ -38,33 +38,25 @@ _lib = _ext._lib
 
 EMA_CLIP = 0.85                        # :17; csrc/consistency.hip: kMtClip
 PREFIXES = ("last_", "proposal_") + tuple(f"{i}head_" for i in range(5))      # :228
-MAX_PREFIXES = 8                       # include/omnipq_semi.h: OMNIPQ_MT_MAX_PREFIXES
-MAX_CLASSES = 64                       # OMNIPQ_MT_MAX_CLASSES
-MAX_K = 512                            # OMNIPQ_MT_MAX_K
-MAX_ROWS = 15360                       # OMNIPQ_MT_MAX_ROWS
-TERMS = 10                             # OMNIPQ_MT_TERMS
+MAX_PREFIXES = _ext.const("OMNIPQ_MT_MAX_PREFIXES")
+MAX_CLASSES = _ext.const("OMNIPQ_MT_MAX_CLASSES")
+MAX_K = _ext.const("OMNIPQ_MT_MAX_K")
+MAX_ROWS = _ext.const("OMNIPQ_MT_MAX_ROWS")
+TERMS = _ext.const("OMNIPQ_MT_TERMS")
 # the nine end_points keys of :258-267, in the order of the kernel's terms; terms[9] is the returned total
 TERM_KEYS = ("center_consistency_loss", "class_consistency_loss", "size_consistency_loss", "consistency_loss",
              "quad_center_consistency_loss_sum", "quad_class_consistency_loss_sum", "quad_normal_consistency_loss_sum",
              "quad_size_consistency_loss_sum", "quad_consistency_loss_sum")
-# per prefix, in the order of omnipq_mt_desc; the student's size_scores take no gradient (arg-max)
+# per prefix, the fields of omnipq_mt_desc (the teacher's with a `t_` in front) in the order the tensors are handed to
+# _Consistency; the student's size_scores take no gradient (arg-max)
 STUDENT_KEYS = ("center", "objectness_scores", "sem_cls_scores", "size_scores", "size_residuals", "quad_center", "quad_scores",
                 "normal_vector", "quad_size")
 TEACHER_KEYS = ("center", "sem_cls_scores", "size_scores", "size_residuals", "quad_center", "quad_scores", "normal_vector",
                 "quad_size")
 GRAD_KEYS = tuple(k for k in STUDENT_KEYS if k != "size_scores")
 
-_PTRS = ctypes.c_void_p * MAX_PREFIXES
-
-
-class _Desc(ctypes.Structure):         # omnipq_mt_desc
-    _fields_ = ([(n, ctypes.c_int) for n in ("prefixes", "b", "k", "nc", "ns")] + [(k, _PTRS) for k in STUDENT_KEYS] +
-                [("t_" + k, _PTRS) for k in TEACHER_KEYS] +
-                [(n, ctypes.c_void_p) for n in ("flip_x", "flip_y", "rot_mat", "scale", "mean_size")])
-
-
-class _Grads(ctypes.Structure):        # omnipq_mt_grads
-    _fields_ = [(k, _PTRS) for k in GRAD_KEYS]
+_Desc = _ext.struct("omnipq_mt_desc")
+_Grads = _ext.struct("omnipq_mt_grads")
 
 
 def _f32(t, name):
@@ -103,10 +95,6 @@ def _mean_size(config, device):
     return _mean_size_cache[key]
 
 
-def _addr(struct):
-    return ctypes.c_void_p(ctypes.addressof(struct))
-
-
 class _Consistency(torch.autograd.Function):
     @staticmethod
     def forward(ctx, shape, aug, teacher, *student):
@@ -125,7 +113,7 @@ class _Consistency(torch.autograd.Function):
         terms = torch.empty(TERMS, device=dev, dtype=torch.float32)
         nbytes = int(_lib.omnipq_mt_consistency_workspace_bytes(P, B, K))
         workspace = torch.empty(max(nbytes, 256), device=dev, dtype=torch.uint8)
-        _ext._run(_lib.omnipq_mt_consistency, tensors[0], _addr(desc), _ext._ptr(ema_center), _ext._ptr(assignment),
+        _ext._run(_lib.omnipq_mt_consistency, tensors[0], ctypes.byref(desc), _ext._ptr(ema_center), _ext._ptr(assignment),
                   _ext._ptr(confidence), _ext._ptr(workspace), _ext._ptr(terms))
         ctx.keep = (desc, tensors, teacher, aug, workspace)
         ctx.dtypes = [t.dtype for t in student]
@@ -145,7 +133,8 @@ class _Consistency(torch.autograd.Function):
             buf = torch.empty_like(t)
             getattr(grads, key)[i // len(STUDENT_KEYS)] = buf.data_ptr()
             out.append(buf)
-        _ext._run(_lib.omnipq_mt_consistency_grad, tensors[0], _addr(desc), _ext._ptr(workspace), _ext._ptr(g), _addr(grads))
+        _ext._run(_lib.omnipq_mt_consistency_grad, tensors[0], ctypes.byref(desc), _ext._ptr(workspace), _ext._ptr(g),
+                  ctypes.byref(grads))
         narrow = [i for i, (b, dt) in enumerate(zip(out, ctx.dtypes)) if b is not None and dt != torch.float32]
         if narrow:                                   # gradients in the inputs' dtype: one multi-tensor copy, as on the way in
             cast = [torch.empty(out[i].shape, device=out[i].device, dtype=ctx.dtypes[i]) for i in narrow]

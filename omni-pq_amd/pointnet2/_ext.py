@@ -12,6 +12,7 @@ There is no fallback: if the shared library is missing or a tensor is not on a G
 raises.
 """
 import ctypes
+import functools
 import os
 import threading
 
@@ -29,15 +30,16 @@ if not os.path.exists(_LIB_PATH):
 
 ABI_VERSION = 5          # include/omnipq_pointops.h: OMNIPQ_ABI_VERSION
 
-# omnipq_entry_point_signatures(): one letter per type (include/omnipq_pointops.h); `P` is `const omnipq_row_plan *`
+# omnipq_entry_point_signatures(): one letter per type (include/omnipq_pointops.h); `P` is `const omnipq_row_plan *`;
+# `L` occurs in omnipq_abi_records() only
 _CTYPE = {"i": ctypes.c_int, "u": ctypes.c_uint, "l": ctypes.c_longlong, "f": ctypes.c_float, "d": ctypes.c_double,
-          "p": ctypes.c_void_p, "P": ctypes.c_void_p, "v": None, "s": ctypes.c_char_p}
+          "p": ctypes.c_void_p, "P": ctypes.c_void_p, "v": None, "s": ctypes.c_char_p, "L": ctypes.c_ulonglong}
 
 
 def _load(path):
-    """-> (library, its signature text).  Every entry point the library lists gets its `restype` and `argtypes` here, once:
-    a plain Python number then arrives in the width the C side reads, a mistyped or missing argument raises before anything
-    is launched, and no caller declares anything."""
+    """-> (library, its signature text, its record text).  Every entry point the library lists gets its `restype` and
+    `argtypes` here, once: a plain Python number then arrives in the width the C side reads, a mistyped or missing argument
+    raises before anything is launched, and no caller declares anything."""
     lib = ctypes.CDLL(path)
     lib.omnipq_abi_version.restype = ctypes.c_int
     if lib.omnipq_abi_version() != ABI_VERSION:
@@ -49,7 +51,8 @@ def _load(path):
         fn = getattr(lib, name)
         fn.restype = _CTYPE[ret]
         fn.argtypes = [_CTYPE[c] for c in params]
-    return lib, text
+    lib.omnipq_abi_records.restype = ctypes.c_char_p
+    return lib, text, lib.omnipq_abi_records().decode()
 
 
 def _signatures(text):
@@ -62,14 +65,43 @@ def _signatures(text):
 # The library is built once per 16-bit element type (omni-pq_amd/build.py, csrc/common.h: e16_t): bfloat16 in
 # libomnipq_pointops.so -- which also serves every index / f32 operator below -- and IEEE half in its `_f16` twin.
 _LIB_F16_PATH = _LIB_PATH[:-3] + "_f16.so"
-_lib0, _SIGNATURES = _load(_LIB_PATH)        # element-type independent entry points (index ops, FPS state) always live here
+_lib0, _SIGNATURES, _RECORDS = _load(_LIB_PATH)    # element-type independent entry points (index ops, FPS state) live here
 _LIBS = {torch.bfloat16: _lib0}
 if os.path.exists(_LIB_F16_PATH):
-    _LIBS[torch.float16], _text = _load(_LIB_F16_PATH)
-    if _text != _SIGNATURES:
+    _LIBS[torch.float16], *_texts = _load(_LIB_F16_PATH)
+    if _texts != [_SIGNATURES, _RECORDS]:
         raise ImportError("pointnet2._ext: the bf16 and f16 libraries were built from different headers")
 # which entry points take a row plan in front of the stream: the loaded libraries say so themselves (build-time text)
 PLAN_AWARE = frozenset(name for name, _, params in _signatures(_SIGNATURES) if "P" in params)
+
+# omnipq_abi_records(): the structs and integer defines of include/*.h as the loaded library was built with them
+_RECORD_LINES = {tuple(line.split()[:2]): line.split()[2:] for line in _RECORDS.splitlines()}
+
+
+def _record(kind, name):
+    try:
+        return _RECORD_LINES[kind, name]
+    except KeyError:
+        raise KeyError(f"pointnet2._ext: the loaded library ({_LIB_PATH}) reports no {kind} {name}") from None
+
+
+def const(name):
+    """The integer the library's headers `#define` as `name`, e.g. const("OMNIPQ_MT_MAX_K")."""
+    return int(_record("define", name)[0])
+
+
+@functools.lru_cache(maxsize=None)
+def struct(name):
+    """The `ctypes.Structure` of the library's `typedef struct {...} name;`: fields in the header's order, `c_void_p` for
+    every pointer, arrays for arrays.  One class per name; resolve it once at import, not per call.  omni-pq_amd/build.py:
+    record_struct() is the same mapping on the build's side, where the compiler checks its sizes and offsets against the C
+    definitions (csrc/capi.hip)."""
+    fields = []
+    for field in _record("struct", name):
+        fname, _, kind = field.partition(":")
+        letter, _, count = kind.partition("*")
+        fields.append((fname, _CTYPE[letter] * int(count) if count else _CTYPE[letter]))
+    return type(name, (ctypes.Structure,), {"_fields_": fields})
 
 
 class _Elem16(threading.local):

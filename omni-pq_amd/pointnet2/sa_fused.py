@@ -49,13 +49,9 @@ def _call(fn, anchor, *args):
         _ext._run(fn, anchor, *args)
 
 
-class RowPlanArg(ctypes.Structure):
-    """include/omnipq_sa.h: omnipq_row_plan"""
-    _fields_ = [("rows_dev", ctypes.c_void_p), ("row_w", ctypes.c_void_p), ("goff", ctypes.c_void_p),
-                ("rows", ctypes.c_longlong), ("gs", ctypes.c_int), ("pool_gamma", ctypes.c_void_p)]
-
-
-PLAN_AWARE = _ext.PLAN_AWARE      # asked of the loaded library (omnipq_entry_point_signatures), not parsed from a header
+# asked of the loaded library (omnipq_abi_records, omnipq_entry_point_signatures), not parsed from a header
+RowPlanArg = _ext.struct("omnipq_row_plan")
+PLAN_AWARE = _ext.PLAN_AWARE
 
 
 # Measuring the SA stages INSIDE the replayed step (VERDICT r3 weak 7).  A hipGraph replay cannot host timing events
@@ -578,13 +574,7 @@ def _gemm_tn(A, B, M, N, P, colsum=None, below=None):
     return C
 
 
-class _TnProblem(ctypes.Structure):
-    """include/omnipq_sa.h: omnipq_tn_problem"""
-    _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("colsum", ctypes.c_void_p), ("out", ctypes.c_void_p),
-                ("M", ctypes.c_int), ("N", ctypes.c_int), ("P", ctypes.c_int), ("lda", ctypes.c_int), ("ldb", ctypes.c_int),
-                ("out_rows", ctypes.c_int), ("out_cols", ctypes.c_int), ("out_ld", ctypes.c_int),
-                ("flags", ctypes.c_int), ("rot", ctypes.c_int), ("ba", ctypes.c_void_p), ("bb", ctypes.c_void_p),
-                ("rows_dev", ctypes.c_void_p)]
+_TnProblem = _ext.struct("omnipq_tn_problem")
 
 
 _ZERO_TAILS = {}

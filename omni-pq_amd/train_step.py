@@ -19,6 +19,8 @@ the captured step as well (three launches at its end, hyper-parameters in device
 Launched kernel by kernel (`graph=False`, or under DDP) the same step is host-bound (about 2.3x slower at batch 8 x
 40 000 points on MI355X); the capture is what makes the 650 dependent launches of 3-150 us run back to back.
 """
+import gc
+
 import torch
 import torch.distributed as dist
 
@@ -320,6 +322,10 @@ class CapturedStep:
                 before_capture()
             torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
             sa_fused.reset_pools()
+            # A captured graph that died in a reference cycle (an earlier CapturedStep, say) must not be collected inside this
+            # capture: on ROCm its destructor synchronises the device, which a capture in progress refuses, and an error
+            # thrown from a destructor ends the process.  torch.cuda.graph itself no longer collects before it begins.
+            gc.collect()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 self.static_loss = self._body(self.cur, self.nxt if self.prefetch_at else None, self.lab, self.cur_t,

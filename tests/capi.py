@@ -68,6 +68,72 @@ def reported_signatures(lib_handle):
     return out
 
 
+def declared_records():
+    """({define: value}, {struct: [(field, letter, array length or None)]}) of the public headers, in the letters of
+    omnipq_abi_records() (include/omnipq_pointops.h): every `#define OMNIPQ_*` that has a value, every `typedef struct`.  The
+    tests' OWN reading, token by token -- not the function omni-pq_amd/build.py compiles into the library.  A value that is no
+    integer or a field type outside the letters raises here."""
+    scalars = {("int",): "i", ("unsigned",): "u", ("unsigned", "int"): "u", ("long", "long"): "l", ("float",): "f",
+               ("double",): "d", ("unsigned", "long", "long"): "L"}
+    texts = [re.sub(r"/\*.*?\*/", " ", open(os.path.join(INCLUDE, fn)).read(), flags=re.S)
+             for fn in sorted(os.listdir(INCLUDE)) if fn.endswith(".h")]
+    defines, structs = {}, {}
+    for text in texts:
+        for ln in text.splitlines():
+            toks = ln.split()
+            if len(toks) >= 3 and toks[0] == "#define" and toks[1].startswith("OMNIPQ_"):
+                assert len(toks) == 3 and toks[1] not in defines, ln
+                defines[toks[1]] = int(toks[2].rstrip("uU"))
+    for text in texts:
+        for chunk in text.split("typedef struct")[1:]:
+            body, _, tail = chunk.partition("}")
+            body = body.partition("{")[2]
+            name = tail.partition(";")[0].strip()
+            assert name.startswith("omnipq_") and "{" not in body and name not in structs, name
+            fields = structs[name] = []
+            for stmt in body.split(";"):
+                for c in "*[],":
+                    stmt = stmt.replace(c, f" {c} ")
+                toks = stmt.split()
+                if not toks:
+                    continue
+                n = 0
+                while toks[n] in ("const", "unsigned", "int", "long", "float", "double", "void", "char"):
+                    n += 1
+                base = tuple(t for t in toks[:n] if t != "const")
+                for decl in " ".join(toks[n:]).split(" , "):                 # `int a, b;` / `const float *x, *y;`
+                    d = decl.split()
+                    stars = d.count("*")
+                    assert d[:stars] == ["*"] * stars and len(d) - stars in (1, 4), (name, stmt)
+                    count = None
+                    if len(d) - stars == 4:
+                        assert d[stars + 1] == "[" and d[stars + 3] == "]", (name, stmt)
+                        count = int(d[stars + 2]) if d[stars + 2].isdigit() else defines[d[stars + 2]]
+                    fields.append((d[stars], "p" if stars else scalars[base], count))
+    return defines, structs
+
+
+def reported_records(lib_handle):
+    """the same pair as the loaded library reports it (omnipq_abi_records); every line must be well-formed and sorted"""
+    lib_handle.omnipq_abi_records.restype = ctypes.c_char_p
+    lines = lib_handle.omnipq_abi_records().decode().splitlines()
+    assert lines == sorted(lines)
+    defines, structs = {}, {}
+    for line in lines:
+        kind, name, *rest = line.split()
+        assert kind in ("define", "struct") and name not in defines and name not in structs, line
+        if kind == "define":
+            assert len(rest) == 1, line
+            defines[name] = int(rest[0])
+        else:
+            fields = structs[name] = []
+            for field in rest:
+                m = re.fullmatch(r"(\w+):([iulLfdp])(?:\*(\d+))?", field)
+                assert m, line
+                fields.append((m.group(1), m.group(2), int(m.group(3)) if m.group(3) else None))
+    return defines, structs
+
+
 _lib = None
 
 

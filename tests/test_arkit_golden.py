@@ -13,7 +13,6 @@ asserted to exceed 1e-4, fifty times that."""
 import ctypes
 import functools
 import os
-import re
 
 import numpy as np
 import pytest
@@ -130,8 +129,7 @@ def test_restatement_reproduces_the_reference():
 
 def test_module_constants_are_the_headers(built_lib):
     from models.utils import arkit_loss_util as ak
-    text = open(os.path.join(capi.INCLUDE, "omnipq_semi.h")).read()
-    defines = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define (OMNIPQ_ARKIT_\w+) (\d+)", text)}
+    defines = {name: v for name, v in capi.declared_records()[0].items() if name.startswith("OMNIPQ_ARKIT_")}
     assert defines == {"OMNIPQ_ARKIT_MAX_BOXES": ak.MAX_BOXES, "OMNIPQ_ARKIT_RECORD_INTS": ak.RECORD_INTS}
     assert ak.MAX_BOXES == 256 and ak.RECORD_KEYS == R.RECORD_KEYS and len(ak.RECORD_KEYS) == ak.RECORD_INTS == 5
     assert ak.GATE == R.GATE == 0.1 and ak.COLLISION == R.COLLISION == 1e-4

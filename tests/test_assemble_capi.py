@@ -41,24 +41,16 @@ def test_symbols_are_exported_and_typed(built_lib):
 
 
 def test_struct_layouts_match_the_header(built_lib):
-    """the ctypes mirrors have the header's fields in the header's order (names read from include/omnipq_data.h)"""
-    import os
-    import re
+    """the module's three descriptors have the header's fields in the header's order (include/omnipq_data.h as
+    capi.declared_records reads it: test_capi_symbols guards the whole report), and OUT_FIELDS names exactly the arrays of
+    omnipq_asm_out"""
     D, *_ = structs()
-    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(capi.INCLUDE, "omnipq_data.h")).read(), flags=re.S)
+    declared = capi.declared_records()[1]
+    kinds = {ctypes.c_void_p: "p", ctypes.c_longlong: "l", ctypes.c_int: "i"}
     for cls, name in ((D._Bank, "omnipq_asm_bank"), (D._Batch, "omnipq_asm_batch"), (D._Out, "omnipq_asm_out")):
-        body = re.search(r"typedef struct \{([^{}]*)\} " + name + ";", text).group(1)
-        fields = []
-        for stmt in body.split(";"):
-            words = stmt.replace("*", " * ").split()
-            if not words:
-                continue
-            kind = "p" if "*" in words else {"int": "i", "long": "l"}[words[0]]
-            names = [w.split()[-1] for w in stmt.replace("*", " ").split(",")]          # `int a, b, c;` declares three
-            fields += [(n, kind) for n in names]
-        kinds = {ctypes.c_void_p: "p", ctypes.c_longlong: "l", ctypes.c_int: "i"}
-        assert [(n, kinds[t]) for n, t in cls._fields_] == fields, name
+        assert [(n, kinds[t], None) for n, t in cls._fields_] == declared[name], name
     assert len(D._Out._fields_) == 31
+    assert sorted(f[0] for f in D.OUT_FIELDS) == sorted(n for n, _ in D._Out._fields_) and len(D.OUT_FIELDS) == 31
     assert (D.META_INTS, D.LABEL_DOUBLES, D.PARAM_DOUBLES) == (8, 64 * 7 + 32 * 8 + 48, 12)
 
 

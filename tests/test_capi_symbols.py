@@ -147,6 +147,86 @@ def test_build_refuses_a_type_without_a_signature_letter(built_lib, tmp_path, mo
         omnipq_build.entry_point_signatures()
 
 
+def test_build_refuses_a_struct_field_without_a_record_letter(built_lib, tmp_path, monkeypatch):
+    """... and the same for what omni-pq_amd/build.py reports of structs and defines: the listed field types, several names per
+    declaration, an array dimensioned by a define; a field of any other type fails with the struct and the field named."""
+    import pytest
+    import build as omnipq_build
+    inc = tmp_path / "include"
+    inc.mkdir()
+    monkeypatch.setattr(omnipq_build, "REPO", str(tmp_path))
+    (inc / "a.h").write_text("#ifndef OMNIPQ_A_H\n#define OMNIPQ_A_H\n#define OMNIPQ_N 3   /* x */\n#define OMNIPQ_FLAG 2u\n"
+                             "typedef struct omnipq_tag {\n  int a, b;  /* two */\n  const float *x, *y[OMNIPQ_N];\n"
+                             "  unsigned long long w; long long v; float f[2]; const void *q;\n} omnipq_rec;\n#endif\n")
+    assert omnipq_build.abi_records() == ("define OMNIPQ_FLAG 2\ndefine OMNIPQ_N 3\n"
+                                          "struct omnipq_rec a:i b:i x:p y:p*3 w:L v:l f:f*2 q:p\n")
+    for body, field in (("int a; short bad_one;", "bad_one"), ("int a; struct { int c; } bad_two;", "bad_two"),
+                        ("omnipq_rec bad_three;", "bad_three"), ("float bad_four[OMNIPQ_UNKNOWN];", "bad_four"),
+                        ("int a, bad_five[2][2];", "bad_five")):
+        (inc / "b.h").write_text("typedef struct { " + body + " } omnipq_worse;\n")
+        with pytest.raises(RuntimeError, match=f"omnipq_worse.*{field}"):
+            omnipq_build.abi_records()
+
+
+def test_layout_checks_refuse_a_layout_the_text_does_not_state(built_lib, tmp_path, monkeypatch):
+    """The static_asserts build.py writes from the reported text (compiled into csrc/capi.hip of both libraries) hold for the
+    header they were written from and stop the compiler once two fields of different width change places.  Host compiler
+    only: the translation unit has no device code."""
+    import subprocess
+    import build as omnipq_build
+    inc = tmp_path / "include"
+    inc.mkdir()
+    monkeypatch.setattr(omnipq_build, "REPO", str(tmp_path))
+    (inc / "a.h").write_text("typedef struct { int n; const float *x; float w; } omnipq_rec;\n")
+    checks = omnipq_build.layout_checks(omnipq_build.abi_records())
+    assert checks.count("static_assert(") == 4 and "sizeof(omnipq_rec) == 24" in checks
+    assert "offsetof(omnipq_rec, x) == 8" in checks and "offsetof(omnipq_rec, w) == 16" in checks
+    (tmp_path / "checks.inc").write_text(checks)
+    (tmp_path / "tu.cpp").write_text('#include <stddef.h>\n#include "include/a.h"\n#include "checks.inc"\nint main() { return 0; }\n')
+    cmd = [omnipq_build.hipcc(), "-x", "c++", "-std=c++17", "-fsyntax-only", "tu.cpp"]
+    done = subprocess.run(cmd, cwd=tmp_path, capture_output=True, text=True)
+    assert done.returncode == 0, done.stderr
+    (inc / "a.h").write_text("typedef struct { const float *x; int n; float w; } omnipq_rec;\n")
+    done = subprocess.run(cmd, cwd=tmp_path, capture_output=True, text=True)
+    assert done.returncode != 0 and "omnipq_rec.x: offset" in done.stderr and "omnipq_rec.n: offset" in done.stderr
+
+
+_FIELD_CTYPE = {"i": ctypes.c_int, "u": ctypes.c_uint, "l": ctypes.c_longlong, "L": ctypes.c_ulonglong, "f": ctypes.c_float,
+                "d": ctypes.c_double, "p": ctypes.c_void_p}
+
+
+def test_library_reports_the_structs_and_defines_its_headers_declare(built_lib):
+    """Every `typedef struct` and every valued `#define OMNIPQ_*` of include/*.h is reported by both libraries as the headers
+    state it (read by tests/capi.py, not by the build), nothing else is reported, and the binding's struct() / const() return
+    exactly these.  This is the one guard of every descriptor and limit the Python modules take from the library."""
+    import pytest
+    defines, structs = capi.declared_records()
+    assert len(structs) == 12 and len(defines) == 29 and len(structs["omnipq_asm_out"]) == 31
+    assert defines["OMNIPQ_MT_MAX_K"] == 512 and defines["OMNIPQ_ABI_VERSION"] == 5
+    assert structs["omnipq_pc_desc"][-1] == ("not_solid", "L", None) and structs["omnipq_mt_grads"][0] == ("center", "p", 8)
+    for path in both(built_lib):
+        got_defines, got_structs = capi.reported_records(ctypes.CDLL(path))
+        assert got_defines == defines, path
+        assert sorted(set(got_structs) ^ set(structs)) == [], path
+        assert {n: got_structs[n] for n in structs if got_structs[n] != structs[n]} == {}, path
+    import pointnet2_utils
+    ext = pointnet2_utils._load_ext()
+    assert {name: ext.const(name) for name in defines} == defines
+    for name, fields in structs.items():
+        cls = ext.struct(name)
+        assert cls is ext.struct(name) and issubclass(cls, ctypes.Structure)
+        assert cls._fields_ == [(f, _FIELD_CTYPE[t] * n if n else _FIELD_CTYPE[t]) for f, t, n in fields], name
+    assert ctypes.sizeof(ext.struct("omnipq_mt_desc")) == 24 + 17 * 8 * 8 + 5 * 8
+    assert ctypes.sizeof(ext.struct("omnipq_mt_grads")) == 8 * 8 * 8
+    pc = ext.struct("omnipq_pc_desc")
+    assert pc._fields_[-1] == ("not_solid", ctypes.c_ulonglong)
+    assert pc.not_solid.offset == ctypes.sizeof(pc) - 8 == max(getattr(pc, f).offset for f, _ in pc._fields_)
+    for ask, name in ((ext.const, "OMNIPQ_MT_MAX_Q"), (ext.struct, "omnipq_mt_descr"), (ext.const, "omnipq_mt_desc"),
+                      (ext.struct, "OMNIPQ_MT_MAX_K")):
+        with pytest.raises(KeyError, match="reports no"):
+            ask(name)
+
+
 def test_binding_refuses_miscounted_and_mistyped_calls(built_lib):
     """Through the binding a call one argument short or one long raises TypeError, a pointer where the header says `int`
     raises ctypes.ArgumentError, and a plain Python int arrives whole in a `long long` parameter -- through an untyped handle

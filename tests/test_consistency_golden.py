@@ -14,7 +14,6 @@ rounding; every margin is asserted to exceed 1e-4, fifty times that."""
 import ctypes
 import functools
 import os
-import re
 
 import numpy as np
 import pytest
@@ -122,13 +121,13 @@ def test_k256_assigns_some_student_rows_several_times_and_some_never():
 
 def test_module_constants_are_the_headers(built_lib):
     from models.utils import mean_teacher_consistency_util as mt
-    text = open(os.path.join(capi.INCLUDE, "omnipq_semi.h")).read()
-    defines = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define (OMNIPQ_MT_\w+) (\d+)", text)}
+    defines = {name: v for name, v in capi.declared_records()[0].items() if name.startswith("OMNIPQ_MT_")}
     assert defines == {"OMNIPQ_MT_MAX_PREFIXES": mt.MAX_PREFIXES, "OMNIPQ_MT_MAX_CLASSES": mt.MAX_CLASSES,
                        "OMNIPQ_MT_MAX_K": mt.MAX_K, "OMNIPQ_MT_MAX_ROWS": mt.MAX_ROWS, "OMNIPQ_MT_TERMS": mt.TERMS}
     assert mt.MAX_PREFIXES == 8 and mt.EMA_CLIP == 0.85 and mt.PREFIXES == mt_inputs.PREFIXES and len(mt.PREFIXES) == 7
     assert mt.TERM_KEYS == R.TERMS and mt.GRAD_KEYS == mt_inputs.GRAD_KEYS
-    # the ctypes mirrors of the two structs: five ints, 17 + 8 pointer arrays, five pointers
+    assert (mt.MAX_PREFIXES, mt.MAX_CLASSES, mt.MAX_K, mt.MAX_ROWS, mt.TERMS) == (8, 64, 512, 15360, 10)
+    # the two structs: five ints, 17 + 8 pointer arrays, five pointers
     assert ctypes.sizeof(mt._Desc) == 24 + 17 * 8 * 8 + 5 * 8 and ctypes.sizeof(mt._Grads) == 8 * 8 * 8
     with pytest.raises(RuntimeError, match="CUDA"):
         S, T, _ = mt_inputs.make((1, 2, 2, 2))

@@ -118,6 +118,41 @@ def test_replayed_captured_step_equals_the_eager_step():
 
 
 @pytest.mark.gpu
+def test_dead_cycles_are_collected_before_the_capture_begins_not_inside_it():
+    """What died in a reference cycle before a CapturedStep is built -- an earlier stepper with its captured graph, say -- is
+    collected before the capture begins: on ROCm the destructor of a captured graph synchronises the device, which a capture
+    in progress refuses.  torch.cuda.graph itself does not collect.  The cycle here holds a plain object whose finalizer
+    notes whether a capture was in progress; the automatic collector is off, so only the stepper's own collection finds it."""
+    import gc
+    import weakref
+    sys.path.insert(0, REPO)
+    import bench
+    import synth
+    import train_step
+    dev = torch.device("cuda", 0)
+    pc = synth.make_clouds(60, 2, 20000, kind="room").to(dev)
+    net = bench.build_model(0).to(dev).train()
+
+    class Node:
+        pass
+
+    seen = []
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        a, b = Node(), Node()
+        a.other, b.other = b, a
+        weakref.finalize(a, lambda: seen.append(torch.cuda.is_current_stream_capturing()))
+        del a, b
+        st = train_step.CapturedStep(net, lambda ep, labels: bench.loss_of(ep), {"point_clouds": pc})
+    finally:
+        if was_enabled:
+            gc.enable()
+    assert st.launch == "hipGraph replay"
+    assert seen == [False]
+
+
+@pytest.mark.gpu
 def test_captured_step_trains_through_zero_grad_and_keeps_the_teacher_semantics():
     """(a) `optimizer.zero_grad()` (set_to_none=True, torch's default) before every replay must not orphan the
     graph's static gradient buffers -- the weights have to move; (b) the warm-up / capture runs on the example batch leave
