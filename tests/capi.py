@@ -149,6 +149,14 @@ def P(t):
     return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
 
 
+def lib_of(dtype):
+    """(library built for the 16-bit element type `dtype`, every entry point typed from the signatures it reports; the
+    binding module) -- (None, module) when this build has no library for that type (pointnet2/_ext.py: _LIBS)"""
+    import sa_fused
+    ext = sa_fused._ext
+    return ext._LIBS.get(dtype), ext
+
+
 def stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 

@@ -1,7 +1,7 @@
 """GPU: the row-major decoder layer (models/decoder_rows.py + csrc/decoder_ops.hip) against PyTorch.
 
 * add + dropout + LayerNorm kernel, forward and backward, vs torch f32 LayerNorm on the same inputs -- with
-  the dropout mask the kernel actually drew (recovered from a probe call with the same seed and salt);
+  the dropout mask the hash of (seed, salt, index) prescribes (restated in tests/decoder_reference.py);
 * ReLU + dropout of the feed-forward, same way;
 * the whole TransformerDecoderLayer: hand-written path under bf16 autocast vs the module's own PyTorch path
   in f32 (dropout off, BatchNorm of the position embeddings in train mode), outputs and parameter gradients.
@@ -28,16 +28,13 @@ def rel_l2(a, b):
     return float((a - b).norm() / (b.norm() + 1e-30))
 
 
-def _mask_from_probe(R, C, p, salt):
-    """keep mask of the LayerNorm dropout for (current seed, salt): x = 0, y = 1 -> r in {0, 1/(1-p)}."""
-    import decoder_rows
+def _restated_mask(R, C, p, salt):
+    """keep mask of the LayerNorm dropout for (current seed, salt) from the hash as tests/decoder_reference.py restates it
+    (csrc/common.h: dec_seed / dec_hash, index = row * C + c) -- not from the kernel under test."""
+    import decoder_reference
     import dropout_state
-    x = torch.zeros(R, C, device=dev())
-    y = torch.ones(R, C, device=dev(), dtype=torch.bfloat16)
-    one, zero = torch.ones(C, device=dev()), torch.zeros(C, device=dev())
-    dropout_state.STATE.salt = salt - 1
-    out32, _, _ = decoder_rows.AddDropoutLayerNorm.apply(x, y, one, zero, 1e-5, p, None, True, False)
-    return out32 > 0          # kept entries sit above the row mean
+    seed = int(dropout_state.seed(dev()).item())
+    return decoder_reference.keep_mask(seed, salt, p, R, C).to(dev())
 
 
 @pytest.mark.parametrize("R,C,p,with_pe", [(300, 288, 0.0, True), (4096, 288, 0.1, False), (37, 1024, 0.3, True),
@@ -54,7 +51,7 @@ def test_add_dropout_layernorm_matches_torch(R, C, p, with_pe):
     dropout_state.STATE.reset()
     torch.manual_seed(3)
     salt = 17
-    mask = _mask_from_probe(R, C, p, salt) if p > 0 else torch.ones(R, C, dtype=torch.bool, device=dev())
+    mask = _restated_mask(R, C, p, salt) if p > 0 else torch.ones(R, C, dtype=torch.bool, device=dev())
     if p > 0 and R * C >= 10000:
         assert abs(float(mask.float().mean()) - (1 - p)) < 0.03
     dropout_state.STATE.salt = salt - 1
