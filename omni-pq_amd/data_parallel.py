@@ -59,9 +59,8 @@ class GradientBuckets:
         if self.early_done or not EARLY_BUCKET:
             return
         mine = {id(p) for p in self.buckets[0]}
-        assign = getattr(dfr, "_assign", None) or []
-        take = [(p, g) for p, g in assign if id(p) in mine]
-        dfr._assign = [(p, g) for p, g in assign if id(p) not in mine]
+        take = [(p, g) for p, g in dfr._assign if id(p) in mine]
+        dfr._assign = [(p, g) for p, g in dfr._assign if id(p) not in mine]
         self.flat[0] = self._pack(self.buckets[0], take, self._packed[0])
         self._hold = [p.grad for p in self.buckets[0]]
         for p in self.buckets[0]:

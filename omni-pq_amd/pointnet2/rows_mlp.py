@@ -379,7 +379,7 @@ def _weight_grad(ctx, l, dcur, Xin, below, dfr, needs_input_grad, grads):
     wt, bt = ctx.targets[l] if (dfr is not None and ctx.targets is not None) else (None, None)
     if wt is not None and needs_input_grad[3 + 4 * l] and (
             not want_bias or (sa_fused.bias_target_ok(bt, lay.C, lay.Cp) and needs_input_grad[4 + 4 * l])):
-        dfr.add(dcur, Xin, lay.Cp, lay.K, N, wt, (lay.C, lay.wk), bt if want_bias else None, below)
+        dfr.add(dcur, Xin, lay.Cp, lay.K, N, wt, sa_fused.Crop(lay.C, lay.wk), bt if want_bias else None, below)
         return
     bsum = None
     if want_bias:

@@ -28,6 +28,8 @@ import torch
 import torch.distributed as dist
 
 import pointnet2_utils
+import wgrads
+from wgrads import Crop, bias_target_ok, cat_params, grad_target, joint_params        # noqa: F401  (re-exported)
 
 _ext = pointnet2_utils._load_ext()      # always the product binding, whatever pointnet2_utils._ext is
 _lib = _ext._lib
@@ -577,155 +579,19 @@ def _gemm_tn(A, B, M, N, P, colsum=None, below=None):
 _TnProblem = _ext.struct("omnipq_tn_problem")
 
 
-_ZERO_TAILS = {}
+def empty_f32(shape, device):
+    """the deferred weight gradients' memory that nothing clears (tests poison it)"""
+    return torch.empty(shape, device=device, dtype=torch.float32)
 
 
-def cat_params(tensors, dim=0, pad_to=None):
-    """torch.cat of parameters along dim 0 (the output heads of a prediction head share one GEMM) that remembers
-    its parts, so that `deferred_wgrads` can hand each part its rows of the joint gradient.  pad_to: append zeros up
-    to that many rows in the same launch (a bias vector for a padded GEMM)."""
-    assert dim == 0
-    rows = sum(t.shape[0] for t in tensors)
-    if pad_to is not None and pad_to > rows:
-        tail = _ZERO_TAILS.get((tensors[0].device, tensors[0].dtype))
-        if tail is None or tail.numel() < pad_to - rows:
-            tail = _ZERO_TAILS[(tensors[0].device, tensors[0].dtype)] = torch.zeros(
-                max(64, pad_to - rows), device=tensors[0].device, dtype=tensors[0].dtype)
-        out = torch.cat(list(tensors) + [tail[:pad_to - rows]], 0)
-    else:
-        out = torch.cat(tensors, 0)
-    parts, r = [], 0
-    for t in tensors:
-        parts.append((t, r, r + t.shape[0]))
-        r += t.shape[0]
-    out.omnipq_parts = parts
-    return out
-
-
-class _JointRows(torch.autograd.Function):
-    """The joint buffer as the concatenation of its parts for autograd: no kernel in either direction (forward returns the
-    buffer the parameters already live in, backward hands each parameter its rows of the joint gradient as a view)."""
-
-    @staticmethod
-    def forward(ctx, joint, *parts):
-        ctx.e16 = E16.dtype
-        ctx.meta = [(p.shape, p.shape[0]) for p in parts]
-        # inside deferred_wgrads the consumer returns no gradient for the joint matrix: an undefined gradient must stay
-        # undefined (the default would hand this node a zero tensor, and every parameter a zero .grad to be added to later)
-        ctx.set_materialize_grads(False)
-        return joint.view(joint.shape)
-
-    @staticmethod
-    def backward(ctx, g):
-        E16.select(ctx.e16)
-        if g is None:
-            return (None,) * (1 + len(ctx.meta))
-        out, r = [], 0
-        for shape, n in ctx.meta:
-            out.append(g[r:r + n].reshape(shape))
-            r += n
-        return (None, *out)
-
-
-def joint_params(owner, name, params, pad_to=None):
-    """cat_params without the per-step copy: the parameters (the 1x1 output heads of a prediction head, which share one
-    GEMM) are re-seated ONCE as row ranges of a joint buffer kept on `owner` -- `param.data` becomes a view of it, so
-    optimizer steps, load_state_dict and the EMA update write straight into the joint matrix -- and every later call only
-    checks the pointers.  A module moved or copied since (`.to()`, deepcopy) fails the check and is re-seated.  The result
-    carries the same `omnipq_parts` as cat_params (deferred weight gradients find their targets) and, outside
-    `deferred_wgrads`, routes the joint gradient back to the parameters through autograd as views.
-    pad_to: rows of zeros appended once (a bias vector for a padded GEMM)."""
-    cache = owner.__dict__.setdefault("_omnipq_joint", {})
-    rows = sum(p.shape[0] for p in params)
-    total = pad_to if (pad_to is not None and pad_to > rows) else rows
-    inner = tuple(params[0].shape[1:])
-    width = 1
-    for d in inner:
-        width *= d
-    joint = cache.get(name)
-
-    def seated():
-        if joint is None or joint.shape[0] != total or joint.device != params[0].device or joint.dtype != params[0].dtype:
-            return False
-        off = 0
-        for p in params:
-            if not p.is_contiguous() or tuple(p.shape[1:]) != inner or \
-                    p.data_ptr() != joint.data_ptr() + off * width * joint.element_size():
-                return False
-            off += p.shape[0]
-        return True
-
-    if not seated():
-        with torch.no_grad():
-            joint = torch.zeros((total,) + inner, device=params[0].device, dtype=params[0].dtype)
-            off = 0
-            for p in params:
-                joint[off:off + p.shape[0]].copy_(p.detach())
-                p.data = joint[off:off + p.shape[0]]
-                off += p.shape[0]
-        cache[name] = joint
-    flat = [p for p in params]
-    out = _JointRows.apply(joint, *flat) if torch.is_grad_enabled() and any(p.requires_grad for p in flat) else joint
-    parts, r = [], 0
-    for p in params:
-        parts.append((p, r, r + p.shape[0]))
-        r += p.shape[0]
-    out.omnipq_parts = parts
-    return out
-
-
-def grad_target(t):
-    """Where a gradient of `t` may be written behind autograd's back, or None:
-    ("param", parameter, element offset)   `t` is a leaf Parameter or a contiguous view of a contiguous one (a row
-                                           range of a packed projection weight);
-    ("parts", [(tensor, r0, r1), ...])     `t` = cat_params(...) of such tensors (each part owns rows r0:r1)."""
-    if t is None:
-        return None
-    if isinstance(t, torch.nn.Parameter):
-        return ("param", t, 0) if t.is_contiguous() and t.requires_grad else None
-    parts = getattr(t, "omnipq_parts", None)
-    if parts is not None:
-        sub = [(grad_target(q), r0, r1) for q, r0, r1 in parts]
-        if all(g is not None and g[0] == "param" for g, _, _ in sub):
-            return ("parts", [(g[1], g[2], r0, r1) for g, r0, r1 in sub])
-        return None
-    base = t._base
-    if isinstance(base, torch.nn.Parameter) and base.requires_grad and base.is_contiguous() and t.is_contiguous():
-        return ("param", base, t.storage_offset() - base.storage_offset())
-    return None
-
-
-def bias_target_ok(bt, C, Cp):
-    """The kernel adds Cp (padded) column sums: straight into a row range of a packed bias only if nothing is
-    padded; whole parameters and concatenations get a scratch vector and take views of it."""
-    return bt is not None and (Cp == C or bt[0] == "parts" or (bt[2] == 0 and bt[1].numel() == C))
-
-
-# Parameters of every DistributedDataParallel module that has run a forward pass in this process.  DDP reduces gradients
-# from per-parameter autograd hooks; a gradient written behind autograd's back never reaches them, so the ranks would
-# silently train on their local gradients.  A global forward pre-hook records DDP-wrapped parameters; deferred_wgrads
-# refuses them (use data_parallel.GradientBuckets on the bare module, or stay outside deferred_wgrads under DDP).
-_DDP_PARAM_IDS = set()
-
-
-def _note_ddp(module, _args):
-    if isinstance(module, torch.nn.parallel.DistributedDataParallel):
-        for p in module.parameters():
-            _DDP_PARAM_IDS.add(id(p))
-
-
-torch.nn.modules.module.register_module_forward_pre_hook(_note_ddp)
-
-
-def _refuse_ddp(wt):
-    if not _DDP_PARAM_IDS or wt is None:
-        return
-    params = [wt[1]] if wt[0] == "param" else [q[0] for q in wt[1]]
-    if any(id(p) in _DDP_PARAM_IDS for p in params):
-        raise RuntimeError(
-            "sa_fused.deferred_wgrads: this parameter belongs to a DistributedDataParallel module -- its gradient would "
-            "bypass DDP's reduction hooks.  Run backward outside deferred_wgrads under DDP, or keep the module bare and "
-            "reduce with data_parallel.GradientBuckets")
+def _plan_buffer(b, dev):
+    """a wgrads.Buffer in device memory: in its parameter's shape and on its device, scratch flat"""
+    shape, device = ((b.numel,), dev) if b.param is None else (b.param.shape, b.param.device)
+    if b.kind == "empty":
+        return empty_f32(shape, device)
+    if b.kind == "pooled":
+        return zeros_f32(b.numel, device).view(shape)
+    return torch.zeros(shape, device=device, dtype=torch.float32)
 
 
 class deferred_wgrads:
@@ -747,11 +613,14 @@ class deferred_wgrads:
     def __enter__(self):
         if deferred_wgrads.active is not None:
             raise RuntimeError("deferred_wgrads blocks do not nest")
-        self.items = []             # (dY, X, M, N, P, weight target, (cout, cin[, rot]), bias target | None, affine | None, row plan | None)
-        self.sa_items = []          # the same for the SA stages' layers: a grouped launch of their own (see add_sa)
+        self.items = []             # wgrads.Item: the per-point layers
+        self.sa_items = []          # wgrads.Item: the SA stages' layers, a grouped launch of their own (see add_sa)
         self.ln_items = []          # (partials [blocks][2C], blocks, C, gamma, beta): LayerNorm parameter gradients
         self.dz_items = []          # (arguments of last_wgrad_dz, weight target, stage label): last layers without dY (LAST_NO_DY)
         self.producers = set()      # streams other than the flushing one on which collected operands were produced
+        self._inflight = []         # what early flushes have launched on: alive until the block ends
+        self._assign = []           # (parameter, f32 gradient) computed so far: `.grad` is touched when the block ends
+        self._side_streams = []     # the streams early flushes ran on
         deferred_wgrads.active = self
         return self
 
@@ -768,24 +637,23 @@ class deferred_wgrads:
 
     def add(self, dY, X, M, N, P, wt, crop, bt, below=None):
         """below: X is that layer's pre-BN output and stands for relu(below.a * X + below.b)"""
-        _refuse_ddp(wt)
+        wgrads._refuse_ddp(wt)
         self._note_producer(dY)
-        self.items.append((dY, X, M, N, P, wt, crop, bt, None if below is None else (below.a, below.b), None))
+        self.items.append(wgrads.Item(dY, X, M, N, P, wt, crop, bt, None if below is None else (below.a, below.b)))
 
     def add_sa(self, dY, X, M, N, P, wt, crop, below=None, blk=None):
         """A layer of a fused SA stage (up to a million positions): collected apart from the per-point layers and run
         as ONE grouped launch for all stages when the block ends.  One by one these GEMMs are split into ~512
         workgroups each -- two per CU, the launch's tail and its slab reduction paid 14 times per step; together
-        they fill the chip with ~4000 workgroups cut for balance.  crop = (cout, cin, rot): see omnipq_tn_problem."""
-        _refuse_ddp(wt)
+        they fill the chip with ~4000 workgroups cut for balance.  blk: the stage's row plan (_Plan), or None."""
+        wgrads._refuse_ddp(wt)
         self._note_producer(dY)
-        # blk: the stage's row plan (_Plan: the positions in use live in device memory), or None
-        self.sa_items.append((dY, X, M, N, P, wt, crop, None, None if below is None else (below.a, below.b), blk))
+        self.sa_items.append(wgrads.Item(dY, X, M, N, P, wt, crop, None, None if below is None else (below.a, below.b), blk))
 
     def add_dz(self, args, wt, stage):
         """The last layer of a planned SA stage (LAST_NO_DY): its weight gradient is launched with the other SA stages' when
         the block ends (last_wgrad_dz: its own launch, the operands are generated)."""
-        _refuse_ddp(wt)
+        wgrads._refuse_ddp(wt)
         self._note_producer(args[0])
         self.dz_items.append((args, wt, stage))
 
@@ -798,10 +666,10 @@ class deferred_wgrads:
             self.flush()
         # early flushes run on side streams: join them on BOTH paths (after an exception their launches must not
         # outlive the operands this block releases below)
-        for st in getattr(self, "_side_streams", ()):
+        for st in self._side_streams:
             torch.cuda.current_stream(st.device).wait_stream(st)
         if et is None:
-            for param, g in getattr(self, "_assign", ()):          # .grad is complete after the block
+            for param, g in self._assign:          # .grad is complete after the block
                 self._accumulate(param, g)
         self.items = None
         self.sa_items = None
@@ -809,6 +677,7 @@ class deferred_wgrads:
         self.ln_items = None
         self._inflight = None
         self._assign = None
+        self._side_streams = None
         return False
 
     def _wait_producers(self, stream):
@@ -827,11 +696,10 @@ class deferred_wgrads:
         cur = torch.cuda.current_stream(stream.device)
         stream.wait_stream(cur)
         self._wait_producers(stream)
-        self.__dict__.setdefault("_inflight", []).extend(self.items)
+        self._inflight.extend(self.items)
         self._inflight.extend(self.ln_items)
-        streams = self.__dict__.setdefault("_side_streams", [])
-        if stream not in streams:
-            streams.append(stream)
+        if stream not in self._side_streams:
+            self._side_streams.append(stream)
         with torch.cuda.stream(stream):
             self.flush()
             self.items = []
@@ -843,7 +711,6 @@ class deferred_wgrads:
         """All LayerNorm parameter gradients collected so far: ONE reduction launch per 32 of them into one flat
         zero-initialised buffer; the parameters get views of it when the block ends."""
         todo, self.ln_items = self.ln_items, []
-        assign = self.__dict__.setdefault("_assign", [])
         for i0 in range(0, len(todo), 32):
             chunk = todo[i0:i0 + 32]
             n = len(chunk)
@@ -855,11 +722,11 @@ class deferred_wgrads:
             outs, off = (ctypes.c_void_p * n)(), 0
             for i, (_, _, C, gamma, beta) in enumerate(chunk):
                 outs[i] = flat.data_ptr() + 4 * off
-                assign.append((gamma, flat[off:off + C].view(gamma.shape)))
-                assign.append((beta, flat[off + C:off + 2 * C].view(beta.shape)))
+                self._assign.append((gamma, flat[off:off + C].view(gamma.shape)))
+                self._assign.append((beta, flat[off + C:off + 2 * C].view(beta.shape)))
                 off += 2 * C
             _call(_lib.omnipq_layernorm_param_reduce, flat, n, parts, blocks, chans, outs)
-            self.__dict__.setdefault("_inflight", []).extend(chunk)      # the partials stay alive until the block ends
+            self._inflight.extend(chunk)      # the partials stay alive until the block ends
 
     def flush(self):
         if self.ln_items:
@@ -875,126 +742,44 @@ class deferred_wgrads:
             items, self.sa_items = self.sa_items, []
             with _tagged("@sa"):
                 self._flush_items(items)
-            self.__dict__.setdefault("_inflight", []).extend(items)
+            self._inflight.extend(items)
         if self.dz_items:
             todo, self.dz_items = self.dz_items, []
-            assign = self.__dict__.setdefault("_assign", [])
             for args, wt, stage in todo:
                 Y2, below, hot, plan, S, C3, C2, P, alpha, beta, Wp = args
                 with _tagged("@sa", stage), _row_plan(plan, P):
                     buf = last_wgrad_dz(Y2, below, hot, plan, S, C3, C2, P, alpha, beta, Wp)
-                assign.append((wt[1], buf.view(wt[1].shape)))
-            self.__dict__.setdefault("_inflight", []).extend(todo)
+                self._assign.append((wt.param, buf.view(wt.param.shape)))
+            self._inflight.extend(todo)
 
     def _flush_items(self, items):
-        dev = items[0][0].device
-        whole = {}              # id(param) -> [param, f32 buffer of its shape, offsets written so far]
-        pieces = []             # (param, f32 view of a scratch buffer) assigned / accumulated afterwards
-        again = []              # (destination view, scratch): second use of the same weight in the graph
+        """One grouped launch: wgrads.place() says where every gradient lands; allocate that, launch, add, note for .grad."""
+        dev = items[0].dY.device
+        plan = wgrads.place(items)
+        bufs = [_plan_buffer(b, dev) for b in plan.buffers]
 
-        # which packed weights are covered completely by the row ranges collected (q | k,v of a cross-attention):
-        # those buffers need no clearing
-        covered = {}
-        for (_, _, _, _, _, wt, crop, _, _, _) in items:
-            cout, cin = crop[0], crop[1]
-            if wt[0] == "param":
-                # (crop of five: a column range [off, off + cin) of a matrix of pitch ld -- see the loop below)
-                covered.setdefault(id(wt[1]), {})[(wt[2], crop[3] if len(crop) > 3 else 0)] = cout * cin
-        complete = {k for k, v in covered.items() if sum(v.values()) == next(
-            it[5][1] for it in items if it[5][0] == "param" and id(it[5][1]) == k).numel()}
-
-        def buffer_of(param, full, pooled=False):
-            ent = whole.get(id(param))
-            if ent is None:
-                # a gradient assembled from several row ranges starts from zero unless they cover it; one written
-                # whole needs no clearing; small vectors that the kernel ADDS to come from the zero pool
-                if full or id(param) in complete:
-                    buf = torch.empty(param.shape, device=param.device, dtype=torch.float32)
-                elif pooled:
-                    buf = zeros_f32(param.numel(), param.device).view(param.shape)
-                else:
-                    buf = torch.zeros(param.shape, device=param.device, dtype=torch.float32)
-                ent = whole[id(param)] = [param, buf, set()]
-            return ent
+        def span(s):
+            return bufs[s.buf].view(-1)[s.off:s.off + s.n]
 
         probs = (_TnProblem * len(items))()
-        for i, (dY, X, M, N, P, wt, crop, bt, aff, blk) in enumerate(items):
-            cout, cin = crop[0], crop[1]
-            q = probs[i]
-            q.rows_dev = 0 if blk is None else blk.rows_dev.data_ptr()
-            q.rot = crop[2] if len(crop) > 2 else 0
-            q.A, q.B = dY.data_ptr(), X.data_ptr()
-            q.ba, q.bb = (0, 0) if aff is None else (aff[0].data_ptr(), aff[1].data_ptr())
-            q.M, q.N, q.P, q.lda, q.ldb = M, N, P, dY.stride(0), X.stride(0)
-            q.out_rows, q.out_cols, q.out_ld, q.flags, q.colsum = cout, cin, cin, 0, 0
-            if wt[0] == "param" and len(crop) > 3:
-                # a COLUMN range of the parameter's matrix: crop = (rows, columns, rot, first column, pitch).  Several
-                # problems cover one gradient (the hoisted first layer of an SA stage: features | coordinates)
-                _, wp, woff = wt
-                ent = buffer_of(wp, False)
-                key = (woff, crop[3])
-                assert key not in ent[2], "column ranges of one weight must be disjoint"
-                ent[2].add(key)
-                q.out_ld = crop[4]
-                q.out = ent[1].data_ptr() + 4 * (woff + crop[3])
-            elif wt[0] == "param":
-                _, wp, woff = wt
-                ent = buffer_of(wp, woff == 0 and cout * cin == wp.numel())
-                if woff in ent[2]:
-                    # the same weight used twice in the graph: its second gradient goes to a buffer of its own and
-                    # is added afterwards (two problems of one grid must not touch the same output)
-                    extra = torch.empty(cout * cin, device=dev, dtype=torch.float32)
-                    again.append((ent[1].view(-1)[woff:woff + cout * cin], extra))
-                    q.out = extra.data_ptr()
-                else:
-                    ent[2].add(woff)
-                    q.out = ent[1].data_ptr() + 4 * woff
-            else:
-                scratch = torch.empty((cout, cin), device=dev, dtype=torch.float32)
-                q.out = scratch.data_ptr()
-                for wp, woff, r0, r1 in wt[1]:
-                    self._piece(pieces, whole, wp, woff, scratch[r0:r1])
-            if bt is None:
-                continue
-            if bt[0] == "param" and not (bt[2] == 0 and bt[1].numel() == cout):
-                bent = buffer_of(bt[1], False, pooled=True)       # row range of a packed bias (M == cout: nothing padded)
-                bent[2].add(bt[2])
-                q.colsum = bent[1].data_ptr() + 4 * bt[2]
-                continue
-            scratch = zeros_f32(M, dev)              # column sums are ADDED by the kernel: from zero
-            q.colsum = scratch.data_ptr()
-            if bt[0] == "param":
-                self._piece(pieces, whole, bt[1], 0, scratch[:cout])
-            else:
-                for bp, boff, r0, r1 in bt[1]:
-                    self._piece(pieces, whole, bp, boff, scratch[r0:r1])
-        ws = torch.empty((int(_lib.omnipq_gemm_tn_grouped_workspace_floats(len(items), ctypes.byref(probs))),),
-                         device=dev, dtype=torch.float32)
+        for q, it, pr in zip(probs, items, plan.problems):
+            q.rows_dev = 0 if it.blk is None else it.blk.rows_dev.data_ptr()
+            q.rot = pr.rot
+            q.A, q.B = it.dY.data_ptr(), it.X.data_ptr()
+            q.ba, q.bb = (0, 0) if it.aff is None else (it.aff[0].data_ptr(), it.aff[1].data_ptr())
+            q.M, q.N, q.P, q.lda, q.ldb = it.M, it.N, it.P, it.dY.stride(0), it.X.stride(0)
+            q.out_rows, q.out_cols, q.out_ld, q.flags = pr.out_rows, pr.out_cols, pr.out_ld, 0
+            q.out = bufs[pr.out.buf].data_ptr() + 4 * pr.out.off
+            q.colsum = 0 if pr.colsum is None else bufs[pr.colsum.buf].data_ptr() + 4 * pr.colsum.off
+        ws = empty_f32((int(_lib.omnipq_gemm_tn_grouped_workspace_floats(len(items), ctypes.byref(probs))),), dev)
         _call(_lib.omnipq_gemm_tn_grouped, ws, len(items), ctypes.byref(probs), _p(ws))
-        for dst, extra in again:
-            dst.add_(extra)
-        for param, view in pieces:
-            if param is None:                        # rows of a scratch result into a buffer assigned below
-                view[0].add_(view[1].reshape(-1))
+        for dst, src in plan.adds:
+            span(dst).add_(span(src))
         # `.grad` is touched only when the block ends (after the side streams have been joined): autograd may still
         # accumulate into the same parameter later in this backward pass, on the caller's stream
-        assign = self.__dict__.setdefault("_assign", [])
-        for param, buf, _ in whole.values():
-            assign.append((param, buf))
-        for param, view in pieces:
-            if param is not None:
-                assign.append((param, view.view(param.shape)))
-
-    @staticmethod
-    def _piece(pieces, whole, param, off, view):
-        """`view` (rows of a scratch result) is the gradient of param's elements [off, off + view.numel())."""
-        if off == 0 and view.numel() == param.numel() and id(param) not in whole:
-            pieces.append((param, view))
-        else:
-            ent = whole.get(id(param))
-            if ent is None:
-                ent = whole[id(param)] = [param, torch.zeros(param.shape, device=param.device, dtype=torch.float32), set()]
-            pieces.append((None, (ent[1].view(-1)[off:off + view.numel()], view)))
+        for param, s in plan.assigns:
+            whole = plan.buffers[s.buf].param is param
+            self._assign.append((param, bufs[s.buf] if whole else span(s).view(param.shape)))
 
     @staticmethod
     def _accumulate(param, g):
@@ -1563,7 +1348,7 @@ def _last_bwd_no_dy(ctx, g_out, grads, dfr):
     if want_w:
         wt = ctx.wtargets[L - 1] if (dfr is not None and SA_WGRADS_GROUPED) else None
         src, blw = (X2, None) if X2 is not None else (below.Y, below)
-        if wt is not None and wt[0] == "param" and wt[2] == 0 and wt[1].numel() == C3 * C2:
+        if wt is not None and wt.covers(C3 * C2):
             dfr.add_dz((src, blw, hot, plan, S, C3, C2, P, ab[0], ab[1], last.Wp), wt, ctx.stage_label)
         else:
             grads[3 * (L - 1)] = last_wgrad_dz(src, blw, hot, plan, S, C3, C2, P, ab[0], ab[1], last.Wp).view(C3, C2, 1, 1)
@@ -1582,9 +1367,9 @@ def _layer_wgrad(ctx, l, dY, grads, dfr):
     wt = ctx.wtargets[l] if (dfr is not None and SA_WGRADS_GROUPED) else None
     if wt is not None and ctx.needs_input_grad[9 + 3 * l]:
         if l == 0:
-            dfr.add_sa(dY, Xin, lay.C, lay.K, g.P, wt, (lay.C, g.cin_raw + 3, 3 | (g.cin << 8)), blk=ctx.plan)
+            dfr.add_sa(dY, Xin, lay.C, lay.K, g.P, wt, Crop(lay.C, g.cin_raw + 3, rot=3 | (g.cin << 8)), blk=ctx.plan)
         else:
-            dfr.add_sa(dY, Xin, lay.C, lay.K, g.P, wt, (lay.C, lay.K), below, blk=ctx.plan)
+            dfr.add_sa(dY, Xin, lay.C, lay.K, g.P, wt, Crop(lay.C, lay.K), below, blk=ctx.plan)
         return
     dWp = _gemm_tn(dY, Xin, lay.C, lay.K, g.P, below=below)      # [Cout][K]
     wk = g.cin + 3 if l == 0 else lay.K
@@ -1684,8 +1469,8 @@ def _tail_on_source(ctx, dY, grads, dfr):
         if wt is not None:
             # the parameter's columns are [xyz(3) | features(cin)] (pointnet2_utils.py:357-359): two problems of the grouped
             # launch write the two column ranges of one gradient buffer
-            dfr.add_sa(dZ, feat2d, C1, cin, B * N, wt, (C1, cin, 0, 3, ld))
-            dfr.add_sa(dY, Xrel, C1, 8, P, wt, (C1, 3, 0, 0, ld), blk=plan)
+            dfr.add_sa(dZ, feat2d, C1, cin, B * N, wt, Crop(C1, cin, col0=3, ld=ld))
+            dfr.add_sa(dY, Xrel, C1, 8, P, wt, Crop(C1, 3, col0=0, ld=ld), blk=plan)
         else:
             dWf = _gemm_tn(dZ, feat2d, C1, cin, B * N)
             dWx = _gemm_tn(dY, Xrel, C1, 8, P)              # (inside backward()'s _row_plan block: the rows in use)

@@ -184,11 +184,11 @@ def _worker(rank, world, port, out_dir):
         with sa_fused.deferred_wgrads() as blk2:
             w = net.fp.mlp.layer0.conv.weight            # `net` ran a forward pass under DDP above
             try:
-                blk2.add(None, None, 8, 8, 8, ("param", w, 0), (8, 8), None)
+                blk2.add(None, None, 8, 8, 8, sa_fused.grad_target(w), sa_fused.Crop(8, 8), None)
                 raise AssertionError("a DDP-wrapped parameter was accepted")
             except RuntimeError as err:
                 assert "DistributedDataParallel" in str(err)
-            blk2.add(torch.zeros(8, 8), torch.zeros(8, 8), 8, 8, 8, ("param", two.head.weight, 0), (8, 8), None)
+            blk2.add(torch.zeros(8, 8), torch.zeros(8, 8), 8, 8, 8, sa_fused.grad_target(two.head.weight), sa_fused.Crop(8, 8), None)
             blk2.items.clear()                           # (nothing to launch on the CPU)
 
         # 3) the statistics all-reduce of the fused SA stage (SyncBatchNorm semantics)

@@ -377,3 +377,130 @@ def test_bench_dump_outputs_writes_float_arrays_and_samples_the_same_elements(tm
     cap = bench.dump_outputs(str(tmp_path / "c"), arrays)
     assert cap < bench.DUMP_SAMPLE
     assert sum(os.path.getsize(tmp_path / "c" / n) for n in os.listdir(tmp_path / "c")) <= 200_000
+
+
+def _placement_invariants(name, items, pl):
+    """The four invariants of a wgrads.Placement, from the placement alone (and, for the last one, how often the items collect
+    each element: wgrads_cases.collected).  They also bound every region by its buffer."""
+    import wgrads_cases
+    written = [torch.zeros(b.numel, dtype=torch.int64) for b in pl.buffers]        # direct writes per element, then + adds
+
+    def region(buf, idx):
+        assert int(idx.min()) >= 0 and int(idx.max()) < pl.buffers[buf].numel, (name, "a region leaves its buffer")
+        written[buf].index_add_(0, idx.reshape(-1), torch.ones(idx.numel(), dtype=torch.int64))
+
+    for pr in pl.problems:
+        r, c = torch.meshgrid(torch.arange(pr.out_rows), torch.arange(pr.out_cols), indexing="ij")
+        region(pr.out.buf, pr.out.off + r * pr.out_ld + c)
+        if pr.colsum is not None:
+            # colsum starts at zero
+            assert pl.buffers[pr.colsum.buf].kind in ("zeros", "pooled"), (name, "column sums are added to uncleared memory")
+            region(pr.colsum.buf, pr.colsum.off + torch.arange(pr.colsum.n))
+    # disjoint outputs (out regions and colsum ranges of the launch, all together)
+    assert all(int(w.max()) <= 1 for w in written), (name, "two problems of one launch share an output element")
+    # `empty` fully written
+    for b, w in zip(pl.buffers, written):
+        assert b.kind in ("empty", "zeros", "pooled")
+        assert b.kind != "empty" or int(w.min()) == 1, (name, "an uncleared buffer is not written completely")
+    # contributions match collections
+    for dst, src in pl.adds:
+        assert dst.n == src.n and src.off + src.n <= pl.buffers[src.buf].numel and dst.off + dst.n <= pl.buffers[dst.buf].numel
+        written[dst.buf][dst.off:dst.off + dst.n] += written[src.buf][src.off:src.off + src.n]
+    assert len({id(p) for p, _ in pl.assigns}) == len(pl.assigns), (name, "a parameter is assigned twice in one flush")
+    want = wgrads_cases.collected(items, ones=True)
+    assert {id(p) for p, _ in pl.assigns} == set(want), name
+    for param, s in pl.assigns:
+        assert s.n == param.numel(), name
+        got = written[s.buf][s.off:s.off + s.n]
+        assert torch.equal(got, want[id(param)][1].long()), (name, "contributions differ from collections", got)
+        owner = pl.buffers[s.buf].param            # a buffer made for a parameter goes to that parameter, whole
+        assert owner is None or (owner is param and s.off == 0), name
+
+
+def test_place_rules(built_lib):
+    """wgrads.place: where the deferred weight gradients of one grouped launch land, decided from host facts alone -- one case
+    per rule (tests/wgrads_cases.py), parameters on the CPU, nothing launched:
+      a) a whole parameter: one `empty` buffer, assigned directly;
+      b) two row ranges that cover a packed (24, 8) weight: one `empty` buffer, nothing cleared;  c) one of them alone: `zeros`;
+      d) the same row range twice: an extra `empty` scratch and one add of it, in that order;
+      e) a joint weight of three parts: a whole unseen parameter is a view of the scratch, a row range of a packed one is added
+         into a `zeros` buffer (e2: so is a whole parameter that the launch has met on its own);
+      f) two column ranges of one (16, 7) matrix: one buffer at pitch 7; a repeated first column raises;
+      g) rot = 3 | cin << 8 reaches the problem untouched;
+      h) bias forms: whole (padded or not) -> a `pooled` scratch of M and a view; row ranges of a packed bias -> one `pooled`
+         buffer, colsum at the offsets; a padded joint bias -> a `pooled` scratch of M, parts [r0:r1].
+    Every case satisfies _placement_invariants."""
+    import wgrads
+    import wgrads_cases
+    from wgrads import Buffer, Crop, Span
+    cases = wgrads_cases.cases()
+    pls = {}
+    for name, case in cases.items():
+        pls[name] = wgrads.place(case.items)
+        _placement_invariants(name, case.items, pls[name])
+        assert len(pls[name].problems) == len(case.items)
+        for it, pr in zip(case.items, pls[name].problems):
+            assert (pr.out_rows, pr.out_cols, pr.rot) == (it.crop.rows, it.crop.cols, it.crop.rot), name
+            assert pr.out_ld == (it.crop.cols if it.crop.ld is None else it.crop.ld), name
+            assert (pr.colsum is None) == (it.bt is None), name
+
+    def params(name):
+        return cases[name].params
+
+    pl, (w,) = pls["a_whole"], params("a_whole")
+    assert pl.buffers == [Buffer("empty", 128, w)] and pl.adds == [] and pl.problems[0].out == Span(0, 0)
+    assert pl.assigns == [(w, Span(0, 0, 128))]
+    pl, (w,) = pls["b_ranges_cover"], params("b_ranges_cover")
+    assert pl.buffers == [Buffer("empty", 192, w)] and pl.adds == [] and pl.assigns == [(w, Span(0, 0, 192))]
+    assert [pr.out for pr in pl.problems] == [Span(0, 0), Span(0, 64)]
+    pl, (w,) = pls["c_one_range"], params("c_one_range")
+    assert pl.buffers == [Buffer("zeros", 192, w)] and pl.adds == [] and pl.problems[0].out == Span(0, 0)
+    pl, (w,) = pls["d_range_twice"], params("d_range_twice")
+    assert pl.buffers == [Buffer("zeros", 192, w), Buffer("empty", 128)]
+    assert [pr.out for pr in pl.problems] == [Span(0, 64), Span(1, 0, 128)]
+    assert pl.adds == [(Span(0, 64, 128), Span(1, 0, 128))] and pl.assigns == [(w, Span(0, 0, 192))]
+    pl, (a, packed, b) = pls["e_joint"], params("e_joint")
+    assert pl.buffers == [Buffer("empty", 17 * 8), Buffer("zeros", 192, packed)] and pl.problems[0].out == Span(0)
+    assert pl.adds == [(Span(1, 64, 64), Span(0, 32, 64))]
+    assert pl.assigns == [(packed, Span(1, 0, 192)), (a, Span(0, 0, 32)), (b, Span(0, 96, 40))]      # whole buffers first
+    pl, (a, packed, b) = pls["e2_joint_part_seen"], params("e2_joint_part_seen")
+    assert pl.buffers == [Buffer("empty", 40, b), Buffer("empty", 17 * 8), Buffer("zeros", 192, packed)]
+    assert pl.adds == [(Span(2, 64, 64), Span(1, 32, 64)), (Span(0, 0, 40), Span(1, 96, 40))]
+    assert pl.assigns == [(b, Span(0, 0, 40)), (packed, Span(2, 0, 192)), (a, Span(1, 0, 32))]
+    pl, (w,) = pls["f_columns"], params("f_columns")
+    assert pl.buffers == [Buffer("empty", 112, w)] and pl.adds == [] and pl.assigns == [(w, Span(0, 0, 112))]
+    assert [(pr.out, pr.out_ld) for pr in pl.problems] == [(Span(0, 3), 7), (Span(0, 0), 7)]
+    twice = wgrads_cases.Case(sa=True)
+    twice.add(16, 8, w, Crop(16, 4, col0=3, ld=7)).add(16, 8, w, Crop(16, 4, col0=3, ld=7))
+    with pytest.raises(AssertionError, match="column ranges of one weight must be disjoint"):
+        wgrads.place(twice.items)
+    assert pls["g_rot"].problems[0].rot == 3 | 8 << 8 == 2051 and pls["g_rot"].buffers[0].kind == "empty"
+    for name, M, C in (("h1_bias_whole", 16, 16), ("h1_bias_whole_padded", 32, 20)):
+        pl, (w, b) = pls[name], params(name)
+        assert pl.buffers == [Buffer("empty", C * 8, w), Buffer("pooled", M)] and pl.problems[0].colsum == Span(1, 0, M)
+        assert pl.adds == [] and pl.assigns == [(w, Span(0, 0, C * 8)), (b, Span(1, 0, C))]
+    pl, (w, b) = pls["h2_bias_ranges"], params("h2_bias_ranges")
+    assert pl.buffers == [Buffer("empty", 192, w), Buffer("pooled", 24, b)] and pl.adds == []
+    assert [pr.colsum for pr in pl.problems] == [Span(1, 0, 8), Span(1, 8, 16)]
+    pl, ps = pls["h3_bias_joint_padded"], params("h3_bias_joint_padded")
+    assert pl.buffers == [Buffer("empty", 17 * 8), Buffer("pooled", 32)] and pl.problems[0].colsum == Span(1, 0, 32)
+    assert pl.adds == [] and [s for _, s in pl.assigns[3:]] == [Span(1, 0, 4), Span(1, 4, 8), Span(1, 12, 5)]
+    assert all(p is q for (p, _), q in zip(pl.assigns, ps))
+
+
+def test_bias_target_ok_truth_table(built_lib):
+    """wgrads.bias_target_ok: the kernel adds Cp (padded) column sums, so a row range of a packed bias can take them directly
+    only when nothing is padded; a whole parameter and a joint bias get a scratch vector, padded or not."""
+    import sa_fused
+    import wgrads
+    whole, packed = torch.nn.Parameter(torch.zeros(20)), torch.nn.Parameter(torch.zeros(60))
+    joint = wgrads.cat_params([torch.nn.Parameter(torch.zeros(n)) for n in (4, 8, 8)], pad_to=32)
+    forms = {"whole": wgrads.grad_target(whole), "range": wgrads.grad_target(packed[20:40]),
+             "first range": wgrads.grad_target(packed[0:20]), "joint": wgrads.grad_target(joint)}
+    assert forms["whole"].single and forms["range"] == wgrads.Target(packed, 20) and not forms["joint"].single
+    assert [(r0, r1) for _, _, r0, r1 in forms["joint"].parts] == [(0, 4), (4, 12), (12, 20)]
+    assert sa_fused.bias_target_ok is wgrads.bias_target_ok and sa_fused.grad_target is wgrads.grad_target
+    assert {k: wgrads.bias_target_ok(t, 20, 20) for k, t in forms.items()} == dict.fromkeys(forms, True)
+    assert {k: wgrads.bias_target_ok(t, 20, 32) for k, t in forms.items()} == {
+        "whole": True, "range": False, "first range": False, "joint": True}
+    assert not wgrads.bias_target_ok(None, 20, 20) and not wgrads.bias_target_ok(None, 20, 32)
