@@ -18,7 +18,8 @@
  *             element by element.
  *   chunks    nchunks x int32[2] = { record, chunk of `chunk_elems` elements of it }; chunk_elems is a multiple of 1024.
  *   hyper     (ngroups + 1) rows of 8 doubles.  Row g < ngroups: { lr, beta1, beta2, eps, weight_decay, 0, 0, 0 } of
- *             parameter group g; row ngroups: { max_norm, grad_scale, 0, ... }.  Doubles, because torch.optim.AdamW
+ *             parameter group g; row ngroups: { max_norm, grad_scale, ema_decay, 0, ... } (ema_decay is read
+ *             by omnipq_adamw_ema_finalize only).  Doubles, because torch.optim.AdamW
  *             evaluates 1 - beta2, 1 - lr * weight_decay, lr / (1 - beta1^t) and sqrt(1 - beta2^t) in double precision
  *             before it rounds them to the tensors' f32.
  *   partials  nchunks doubles (scratch).
@@ -39,6 +40,29 @@
  * On an applying call result[0..3] mean what they mean above; on any other call only result[0] (the norm of grad_scale times
  * the running sum) is written.  The sum is overwritten, not added to, when micro == 0: no zeroing launch, and a non-finite value
  * left behind by a skipped step cannot leak into the next one.
+ *
+ * Mean-teacher weight averaging (the reference's update_ema_variables, train.py:435-439, called after optimizer.step() at
+ * train.py:576) inside the same launches is the omnipq_adamw_ema_* pair; the squared-norm launch is the one above, unchanged.
+ *     alpha = min(1 - 1 / (global_step + 1), decay);   ema = alpha * ema + (1 - alpha) * param
+ * alpha changes with every step, so it cannot be a kernel argument of a captured launch: the finalise launch forms it from a
+ * device word and the update launch reads it, like the bias corrections.
+ *   hyper     row ngroups, slot 2: ema_decay (a double like the rest of the row).
+ *   ema_state int64[1]: the global_step the NEXT averaging will use.  Written by thread 0 of the finalise launch only, with an
+ *             ordinary store.
+ *   ema_coef  float[2] = { alpha, beta }, written by the finalise launch for the update launch.  In f64:
+ *             a = fmin(1 - 1 / (double)(global_step + 1), decay); alpha = (float)a, beta = (float)(1 - a) -- the two roundings
+ *             the float arguments of omnipq_ema_update (omnipq_sa.h) go through when Python doubles reach them.
+ *   ema_ptrs  nrec device pointers: entry i is the teacher's tensor paired with records[i].param (contiguous f32 of the same
+ *             numel, 4-byte aligned).  A parallel array: the 48-byte record does not change.
+ *   ema_only  n_only packed 24-byte records { float *ema; const float *param; int64_t numel; } (the segment layout of
+ *             omnipq_ema_update) with only_chunks, n_only_chunks x int32[2] = { record, chunk of `chunk_elems` elements of it }:
+ *             the pairs whose student parameter is not in `records` because it has no gradient.  The reference averages every
+ *             parameter, whether or not it received a gradient.
+ * An APPLYING call is every call of the plain family and the accum_steps-th micro-batch of the accumulating one.  It always
+ * averages: a step skipped for a non-finite gradient norm leaves p, m and v alone and still averages the teacher with the
+ * unchanged p, as a training loop on the separate call does (train.py:576 does not look at the norm).  Any other micro-batch
+ * touches neither the teacher nor ema_state.  Per element: t = ema * alpha rounded to f32, then ema = fmaf(beta, p_new, t) --
+ * the arithmetic of omnipq_ema_update, so the teacher holds the same bits as after that call on the updated parameters.
  *
  * `.grad` is READ-ONLY here: the clipped (and un-scaled) gradient g' = grad_scale * clip_coef * g exists in registers
  * only and is never written back.  Nothing in the reference reads the gradients after train.py:564; a caller that wants the
@@ -97,6 +121,29 @@ int omnipq_adamw_accum_finalize(int nchunks, const double *partials, const doubl
 int omnipq_adamw_accum_update(int nrec, int nchunks, const void *records, const int *chunks, int chunk_elems,
                               const float *exp_avg_base, const float *acc_base, const long long *accum, const float *coef,
                               const float *result, void *stream);
+
+/* HOST arrays, nothing is launched: OMNIPQ_EINVAL for a null or misaligned teacher pointer among the nrec entries of
+ * ema_ptrs_host, for an ema_only record with a null or misaligned pointer or a negative numel, and for an only_chunks entry that
+ * names no record or lies past its record's last element. */
+int omnipq_adamw_check_ema_table(int nrec, const void *ema_ptrs_host, int n_only, const void *ema_only_host,
+                                 int n_only_chunks, const int *only_chunks_host, int chunk_elems);
+
+/* omnipq_adamw_finalize (accum == NULL; accum_steps must then be 1) or omnipq_adamw_accum_finalize (accum != NULL) plus, on
+ * an applying call and whether or not the norm is finite: g = ema_state[0], ema_coef = { alpha, beta } of global_step g and
+ * the decay in hyper, ema_state[0] = g + 1.  A micro-batch that is not the applying one touches neither. */
+int omnipq_adamw_ema_finalize(int nchunks, const double *partials, const double *hyper, int ngroups, int accum_steps,
+                              long long *counters, long long *accum, long long *ema_state, float *result, float *coef,
+                              float *ema_coef, void *stream);
+
+/* omnipq_adamw_update (accum == NULL) or omnipq_adamw_accum_update (accum != NULL: exp_avg_base and acc_base are then
+ * required) over nchunks workgroups, each of which also averages the teacher's copy of its chunk with the p it has just
+ * computed, plus n_only_chunks workgroups that average the chunks of ema_only with p as it is in memory.  The teacher's chunk
+ * moves as 16-byte vectors where it shares p's phase modulo 16 bytes (a deep copy does) and through 4-byte-aligned accesses
+ * where it does not.  apply == 0: a no-op.  result[2] (found_nonfinite) set: p, m and v stay, every workgroup averages. */
+int omnipq_adamw_ema_update(int nrec, int nchunks, const void *records, const void *ema_ptrs, const int *chunks,
+                            int chunk_elems, int n_only, int n_only_chunks, const void *ema_only, const int *only_chunks,
+                            const float *exp_avg_base, const float *acc_base, const long long *accum, const float *coef,
+                            const float *ema_coef, const float *result, void *stream);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,11 @@
 // bytes per parameter; 4 and 4 on the first micro-batch, which overwrites), the finalise launch counts micro-batches in a device
 // word and marks the k-th call as the applying one, and the update reads the accumulator where it read the gradient.  The
 // templates below are the ONE body behind both families of entry points.
+//
+// Mean-teacher weight averaging (reference train.py:435-439 and :576) rides on the same launches (kEma): the finalise launch
+// forms alpha = min(1 - 1/(global_step + 1), decay) from a device word and advances it, the update launch holds the new p in
+// registers and reads and writes the teacher's copy next to it (8 more bytes per parameter instead of a launch of 12), and a
+// few more workgroups average the parameters that have no gradient.
 #include <math.h>
 
 #include "common.h"
@@ -169,12 +174,15 @@ __global__ __launch_bounds__(kAdamThreads) void adamw_grad_sqnorm_kernel(const A
   adamw_sqnorm_chunk<kAccum>(r.grad + base, sum, first, len, gs, partials + blockIdx.x);
 }
 
-template <bool kAccum>
+// ema_state (kEma): int64[1] = the global_step the NEXT averaging uses; ema_coef: float[2] = { alpha, beta } for the update
+template <bool kAccum, bool kEma>
 __global__ __launch_bounds__(kAdamThreads) void adamw_finalize_kernel(int nchunks, const double *__restrict__ partials,
                                                                      const double *__restrict__ hyper, int ngroups,
                                                                      int accum_steps, long long *__restrict__ counters,
                                                                      long long *__restrict__ accum,
-                                                                     float *__restrict__ result, float *__restrict__ coef) {
+                                                                     long long *__restrict__ ema_state,
+                                                                     float *__restrict__ result, float *__restrict__ coef,
+                                                                     float *__restrict__ ema_coef) {
   double acc = 0.0;
   for (int i = (int)threadIdx.x; i < nchunks; i += kAdamThreads) acc += partials[i];
   const double sum = block_sum_f64(acc);
@@ -195,6 +203,15 @@ __global__ __launch_bounds__(kAdamThreads) void adamw_finalize_kernel(int nchunk
     }
     accum[0] = 0;
     accum[1] = 1;
+  }
+  if (kEma) {
+    // every applying call averages, a skipped one included (train.py:576 does not look at the norm): alpha in f64, then the
+    // two roundings to f32 that the arguments of omnipq_ema_update go through
+    const long long step = ema_state[0];
+    const double a = fmin(1.0 - 1.0 / (double)(step + 1), last[2]);
+    ema_coef[0] = (float)a;
+    ema_coef[1] = (float)(1.0 - a);
+    ema_state[0] = step + 1;
   }
   // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1, in the norm's f32
   float clip = 1.f;
@@ -241,26 +258,145 @@ __device__ __forceinline__ void adam1(float &p, float g, float &m, float &v, con
   p = __builtin_fmaf(-c.step, m / denom, pd);
 }
 
+// the teacher's record of a parameter that is not in the optimiser's table: the segment layout of omnipq_ema_update
+struct EmaOnlyRec {
+  float *ema;
+  const float *param;
+  long long numel;
+};
+
+// one element of the reference's update_ema_variables, rounded like ema_update_kernel (sa_stage.hip): t = e * alpha in f32,
+// then one fused multiply-add
+__device__ __forceinline__ float ema1(float e, float p, float alpha, float beta) {
+  const float t = e * alpha;
+  return __builtin_fmaf(beta, p, t);
+}
+
+// four floats at a 4-byte-aligned address: one 16-byte access where the caller knows the address to be 16-byte aligned
+__device__ __forceinline__ adam_f32x4 load_f32x4(const float *q, bool aligned16) {
+  if (aligned16) return *(const adam_f32x4 *)q;
+  const adam_f32x4_any a = *(const adam_f32x4_any *)q;
+  return adam_f32x4{a.e[0], a.e[1], a.e[2], a.e[3]};
+}
+
+__device__ __forceinline__ void store_f32x4(float *q, adam_f32x4 x, bool aligned16) {
+  if (aligned16) {
+    *(adam_f32x4 *)q = x;
+    return;
+  }
+  adam_f32x4_any a;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) a.e[k] = x[k];
+  *(adam_f32x4_any *)q = a;
+}
+
+// the averaging alone over one chunk, p as it is in memory: one coalesced dword per lane
+__device__ __forceinline__ void ema_chunk(float *__restrict__ e, const float *__restrict__ p, int len, float alpha,
+                                          float beta) {
+  for (int i = (int)threadIdx.x; i < len; i += kAdamThreads) e[i] = ema1(e[i], p[i], alpha, beta);
+}
+
+// The 16-byte vectors of one chunk: p, g, m and v start on a 16-byte boundary, four vectors of each per thread and trip.
+// kEma: the teacher's vector of a pass is loaded behind that pass's stores of p, m and v, into the registers its gradient has
+// left -- held next to P, G, M and V from the start, the sixteen registers of E would cost a wave per SIMD.  kAligned: e
+// shares that boundary; otherwise it moves through 4-byte-aligned accesses.
+template <bool kEma, bool kAligned>
+__device__ __forceinline__ void adam_vectors(float *p, const float *g, float *m, float *v, float *e, int nvec,
+                                             const AdamCoef &c, float alpha, float beta) {
+  const int tid = (int)threadIdx.x;
+  adam_f32x4 *pv = (adam_f32x4 *)p;
+  const adam_f32x4 *gv = (const adam_f32x4 *)g;
+  adam_f32x4 *mv = (adam_f32x4 *)m;
+  adam_f32x4 *vv4 = (adam_f32x4 *)v;
+  for (int j0 = 0; j0 < nvec; j0 += 4 * kAdamThreads) {
+    adam_f32x4 P[4], G[4], M[4], V[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int j = j0 + u * kAdamThreads + tid;
+      if (j < nvec) {
+        P[u] = pv[j];
+        G[u] = gv[j];
+        M[u] = mv[j];
+        V[u] = vv4[j];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int j = j0 + u * kAdamThreads + tid;
+      if (j < nvec) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float pe = P[u][k], me = M[u][k], ve = V[u][k];
+          adam1(pe, G[u][k], me, ve, c);
+          P[u][k] = pe;
+          M[u][k] = me;
+          V[u][k] = ve;
+        }
+        pv[j] = P[u];
+        mv[j] = M[u];
+        vv4[j] = V[u];
+        if (kEma) {
+          adam_f32x4 E = load_f32x4(e + 4 * (size_t)j, kAligned);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) E[k] = ema1(E[k], P[u][k], alpha, beta);
+          store_f32x4(e + 4 * (size_t)j, E, kAligned);
+        }
+      }
+    }
+  }
+}
+
 // kAccum: the gradient is the chunk's segment of the accumulator (same offsets as exp_avg: always the vector path), and a
-// call that finalise did not mark as the applying one changes nothing
-template <bool kAccum>
+// call that finalise did not mark as the applying one changes nothing.
+// kEma: workgroup c < nchunks also averages the teacher's copy ema_ptrs[record] of its chunk with the p it has just computed;
+// workgroups from nchunks on average the chunks of `only` (parameters without a gradient).  A step skipped for a non-finite
+// norm still averages, with p read from memory.  The teacher's chunk moves as 16-byte vectors where it shares p's phase and
+// through 4-byte-aligned accesses where it does not; p, g, m and v keep their path either way.
+template <bool kAccum, bool kEma>
 __global__ __launch_bounds__(kAdamThreads) void adamw_update_kernel(const AdamRec *__restrict__ recs,
+                                                                   float *const *__restrict__ ema_ptrs, int nchunks,
                                                                    const int *__restrict__ chunks, int chunk,
+                                                                   const EmaOnlyRec *__restrict__ only,
+                                                                   const int *__restrict__ only_chunks,
                                                                    const float *exp_avg_base, const float *sum_base,
                                                                    const long long *__restrict__ accum,
                                                                    const float *__restrict__ coef,
+                                                                   const float *__restrict__ ema_coef,
                                                                    const float *__restrict__ result) {
   if (kAccum && accum[1] == 0) return;           // not the k-th micro-batch
-  if (result[2] != 0.f) return;                  // non-finite gradient norm: the whole step is skipped
+  const bool skipped = result[2] != 0.f;         // non-finite gradient norm: the whole step is skipped
+  if (!kEma && skipped) return;
+  float alpha = 0.f, beta = 0.f;
+  if (kEma) {
+    alpha = ema_coef[0];
+    beta = ema_coef[1];
+    if ((int)blockIdx.x >= nchunks) {
+      const int *ok = only_chunks + 2 * (size_t)((int)blockIdx.x - nchunks);
+      const EmaOnlyRec o = only[ok[0]];
+      const long long obase = (long long)ok[1] * chunk;
+      const long long oleft = o.numel - obase;
+      const int olen = oleft < (long long)chunk ? (int)oleft : chunk;
+      if (olen > 0) ema_chunk(o.ema + obase, o.param + obase, olen, alpha, beta);
+      return;
+    }
+  }
   const int *ck = chunks + 2 * (size_t)blockIdx.x;
   const AdamRec r = recs[ck[0]];
   const long long base = (long long)ck[1] * chunk;
   const long long left = r.numel - base;
   const int len = left < (long long)chunk ? (int)left : chunk;
   if (len <= 0) return;
+  float *p = r.param + base;
+  float *e = nullptr;
+  if (kEma) {
+    e = ema_ptrs[ck[0]] + base;
+    if (skipped) {
+      ema_chunk(e, p, len, alpha, beta);
+      return;
+    }
+  }
   const float *cf = coef + 8 * (size_t)r.group;
   const AdamCoef c = {cf[0], cf[1], cf[2], cf[3], cf[4], cf[5], cf[6], cf[7], result[3]};
-  float *p = r.param + base;
   const float *g = (kAccum ? sum_base + (r.exp_avg - exp_avg_base) : r.grad) + base;
   float *m = r.exp_avg + base;
   float *v = r.exp_avg_sq + base;
@@ -269,7 +405,7 @@ __global__ __launch_bounds__(kAdamThreads) void adamw_update_kernel(const AdamRe
   if (phase16(g) != ph || phase16(m) != ph || phase16(v) != ph) {
     // the four tensors do not share a phase modulo 16 bytes: element by element (still one coalesced dword per lane)
     for (int i0 = 0; i0 < len; i0 += 4 * kAdamThreads) {
-      float pp[4], gg[4], mm[4], vv[4];
+      float pp[4], gg[4], mm[4], vv[4], ee[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int i = i0 + u * kAdamThreads + tid;
@@ -278,6 +414,7 @@ __global__ __launch_bounds__(kAdamThreads) void adamw_update_kernel(const AdamRe
           gg[u] = g[i];
           mm[u] = m[i];
           vv[u] = v[i];
+          if (kEma) ee[u] = e[i];
         }
       }
 #pragma unroll
@@ -288,6 +425,7 @@ __global__ __launch_bounds__(kAdamThreads) void adamw_update_kernel(const AdamRe
           p[i] = pp[u];
           m[i] = mm[u];
           v[i] = vv[u];
+          if (kEma) e[i] = ema1(ee[u], pp[u], alpha, beta);
         }
       }
     }
@@ -308,42 +446,15 @@ __global__ __launch_bounds__(kAdamThreads) void adamw_update_kernel(const AdamRe
       p[i] = pp;
       m[i] = mm;
       v[i] = vv;
+      if (kEma) e[i] = ema1(e[i], pp, alpha, beta);
     }
   }
-  adam_f32x4 *pv = (adam_f32x4 *)(p + head);
-  const adam_f32x4 *gv = (const adam_f32x4 *)(g + head);
-  adam_f32x4 *mv = (adam_f32x4 *)(m + head);
-  adam_f32x4 *vv4 = (adam_f32x4 *)(v + head);
-  for (int j0 = 0; j0 < nvec; j0 += 4 * kAdamThreads) {
-    adam_f32x4 P[4], G[4], M[4], V[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int j = j0 + u * kAdamThreads + tid;
-      if (j < nvec) {
-        P[u] = pv[j];
-        G[u] = gv[j];
-        M[u] = mv[j];
-        V[u] = vv4[j];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int j = j0 + u * kAdamThreads + tid;
-      if (j < nvec) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float pe = P[u][e], me = M[u][e], ve = V[u][e];
-          adam1(pe, G[u][e], me, ve, c);
-          P[u][e] = pe;
-          M[u][e] = me;
-          V[u][e] = ve;
-        }
-        pv[j] = P[u];
-        mv[j] = M[u];
-        vv4[j] = V[u];
-      }
-    }
-  }
+  // (the choice is uniform over the workgroup; it is made HERE, outside the loop: a branch on it inside the four passes made
+  // the compiler carry copies of P, M and V across it -- 182 registers, two waves per SIMD)
+  if (kEma && phase16(e) != ph)
+    adam_vectors<kEma, false>(p + head, g + head, m + head, v + head, e + head, nvec, c, alpha, beta);
+  else
+    adam_vectors<kEma, true>(p + head, g + head, m + head, v + head, kEma ? e + head : nullptr, nvec, c, alpha, beta);
 }
 
 static bool bad_chunk(int chunk_elems) { return chunk_elems <= 0 || (chunk_elems % kAdamQuantum) != 0; }
@@ -388,8 +499,8 @@ extern "C" int omnipq_adamw_finalize(int nchunks, const double *partials, const 
                                      long long *counters, float *result, float *coef, void *stream) {
   if (nchunks < 0 || ngroups < 1) return OMNIPQ_EINVAL;
   if (!hyper || !counters || !result || !coef || (nchunks > 0 && !partials)) return OMNIPQ_EINVAL;
-  adamw_finalize_kernel<false><<<1, kAdamThreads, 0, (hipStream_t)stream>>>(nchunks, partials, hyper, ngroups, 1, counters,
-                                                                            nullptr, result, coef);
+  adamw_finalize_kernel<false, false><<<1, kAdamThreads, 0, (hipStream_t)stream>>>(
+      nchunks, partials, hyper, ngroups, 1, counters, nullptr, nullptr, result, coef, nullptr);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }
@@ -400,8 +511,9 @@ extern "C" int omnipq_adamw_update(int nrec, int nchunks, const void *records, c
   if (!coef || !result) return OMNIPQ_EINVAL;
   if (nrec == 0 || nchunks == 0) return OMNIPQ_OK;
   if (!records || !chunks) return OMNIPQ_EINVAL;
-  adamw_update_kernel<false><<<nchunks, kAdamThreads, 0, (hipStream_t)stream>>>((const AdamRec *)records, chunks, chunk_elems,
-                                                                               nullptr, nullptr, nullptr, coef, result);
+  adamw_update_kernel<false, false><<<nchunks, kAdamThreads, 0, (hipStream_t)stream>>>(
+      (const AdamRec *)records, nullptr, nchunks, chunks, chunk_elems, nullptr, nullptr, nullptr, nullptr, nullptr, coef, nullptr,
+      result);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }
@@ -426,8 +538,8 @@ extern "C" int omnipq_adamw_accum_finalize(int nchunks, const double *partials, 
                                            void *stream) {
   if (nchunks < 0 || ngroups < 1 || accum_steps < 1) return OMNIPQ_EINVAL;
   if (!hyper || !counters || !accum || !result || !coef || (nchunks > 0 && !partials)) return OMNIPQ_EINVAL;
-  adamw_finalize_kernel<true><<<1, kAdamThreads, 0, (hipStream_t)stream>>>(nchunks, partials, hyper, ngroups, accum_steps,
-                                                                           counters, accum, result, coef);
+  adamw_finalize_kernel<true, false><<<1, kAdamThreads, 0, (hipStream_t)stream>>>(
+      nchunks, partials, hyper, ngroups, accum_steps, counters, accum, nullptr, result, coef, nullptr);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }
@@ -439,8 +551,75 @@ extern "C" int omnipq_adamw_accum_update(int nrec, int nchunks, const void *reco
   if (!exp_avg_base || !acc_base || !accum || !coef || !result) return OMNIPQ_EINVAL;
   if (nrec == 0 || nchunks == 0) return OMNIPQ_OK;
   if (!records || !chunks) return OMNIPQ_EINVAL;
-  adamw_update_kernel<true><<<nchunks, kAdamThreads, 0, (hipStream_t)stream>>>(
-      (const AdamRec *)records, chunks, chunk_elems, exp_avg_base, acc_base, accum, coef, result);
+  adamw_update_kernel<true, false><<<nchunks, kAdamThreads, 0, (hipStream_t)stream>>>(
+      (const AdamRec *)records, nullptr, nchunks, chunks, chunk_elems, nullptr, nullptr, exp_avg_base, acc_base, accum, coef,
+      nullptr, result);
+  OMNIPQ_LAUNCH_CHECK();
+  return OMNIPQ_OK;
+}
+
+// ---- mean-teacher weight averaging inside the finalise and update launches ------------------------------------------------
+
+extern "C" int omnipq_adamw_check_ema_table(int nrec, const void *ema_ptrs_host, int n_only, const void *ema_only_host,
+                                            int n_only_chunks, const int *only_chunks_host, int chunk_elems) {
+  static_assert(sizeof(EmaOnlyRec) == 24, "the ema_only record is the segment layout of omnipq_ema_update");
+  if (nrec < 0 || n_only < 0 || n_only_chunks < 0 || bad_chunk(chunk_elems)) return OMNIPQ_EINVAL;
+  if ((nrec > 0 && !ema_ptrs_host) || (n_only > 0 && !ema_only_host) || (n_only_chunks > 0 && !only_chunks_host))
+    return OMNIPQ_EINVAL;
+  const uintptr_t *ptrs = (const uintptr_t *)ema_ptrs_host;
+  for (int i = 0; i < nrec; ++i)
+    if (!ptrs[i] || (ptrs[i] & 3u) != 0) return OMNIPQ_EINVAL;
+  const EmaOnlyRec *only = (const EmaOnlyRec *)ema_only_host;
+  for (int i = 0; i < n_only; ++i) {
+    const EmaOnlyRec &o = only[i];
+    if (!o.ema || !o.param || o.numel < 0) return OMNIPQ_EINVAL;
+    if ((((uintptr_t)o.ema | (uintptr_t)o.param) & 3u) != 0) return OMNIPQ_EINVAL;
+  }
+  for (int i = 0; i < n_only_chunks; ++i) {
+    const int rec = only_chunks_host[2 * (size_t)i], c = only_chunks_host[2 * (size_t)i + 1];
+    if (rec < 0 || rec >= n_only || c < 0) return OMNIPQ_EINVAL;
+    if ((long long)c * chunk_elems >= only[rec].numel) return OMNIPQ_EINVAL;
+  }
+  return OMNIPQ_OK;
+}
+
+extern "C" int omnipq_adamw_ema_finalize(int nchunks, const double *partials, const double *hyper, int ngroups,
+                                         int accum_steps, long long *counters, long long *accum, long long *ema_state,
+                                         float *result, float *coef, float *ema_coef, void *stream) {
+  if (nchunks < 0 || ngroups < 1 || accum_steps < 1) return OMNIPQ_EINVAL;
+  if (!hyper || !counters || !ema_state || !result || !coef || !ema_coef || (nchunks > 0 && !partials)) return OMNIPQ_EINVAL;
+  if (!accum && accum_steps != 1) return OMNIPQ_EINVAL;
+  if (accum)
+    adamw_finalize_kernel<true, true><<<1, kAdamThreads, 0, (hipStream_t)stream>>>(
+        nchunks, partials, hyper, ngroups, accum_steps, counters, accum, ema_state, result, coef, ema_coef);
+  else
+    adamw_finalize_kernel<false, true><<<1, kAdamThreads, 0, (hipStream_t)stream>>>(
+        nchunks, partials, hyper, ngroups, 1, counters, nullptr, ema_state, result, coef, ema_coef);
+  OMNIPQ_LAUNCH_CHECK();
+  return OMNIPQ_OK;
+}
+
+extern "C" int omnipq_adamw_ema_update(int nrec, int nchunks, const void *records, const void *ema_ptrs, const int *chunks,
+                                       int chunk_elems, int n_only, int n_only_chunks, const void *ema_only,
+                                       const int *only_chunks, const float *exp_avg_base, const float *acc_base,
+                                       const long long *accum, const float *coef, const float *ema_coef, const float *result,
+                                       void *stream) {
+  if (nrec < 0 || nchunks < 0 || n_only < 0 || n_only_chunks < 0 || bad_chunk(chunk_elems)) return OMNIPQ_EINVAL;
+  if (!coef || !ema_coef || !result) return OMNIPQ_EINVAL;
+  if (accum && (!exp_avg_base || !acc_base)) return OMNIPQ_EINVAL;
+  if ((nrec > 0 && (!records || !ema_ptrs)) || (nchunks > 0 && (!chunks || nrec == 0))) return OMNIPQ_EINVAL;
+  if ((n_only > 0 && !ema_only) || (n_only_chunks > 0 && (!only_chunks || n_only == 0))) return OMNIPQ_EINVAL;
+  if ((long long)nchunks + n_only_chunks > 0x7fffffffLL) return OMNIPQ_EINVAL;
+  const int grid = nchunks + n_only_chunks;
+  if (grid == 0) return OMNIPQ_OK;
+  if (accum)
+    adamw_update_kernel<true, true><<<grid, kAdamThreads, 0, (hipStream_t)stream>>>(
+        (const AdamRec *)records, (float *const *)ema_ptrs, nchunks, chunks, chunk_elems, (const EmaOnlyRec *)ema_only,
+        only_chunks, exp_avg_base, acc_base, accum, coef, ema_coef, result);
+  else
+    adamw_update_kernel<false, true><<<grid, kAdamThreads, 0, (hipStream_t)stream>>>(
+        (const AdamRec *)records, (float *const *)ema_ptrs, nchunks, chunks, chunk_elems, (const EmaOnlyRec *)ema_only,
+        only_chunks, nullptr, nullptr, nullptr, coef, ema_coef, result);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }

@@ -7,6 +7,11 @@ updated by ONE launch (`omnipq_ema_update`, 3 x 71 MB of HBM traffic for PQ-Tran
 instead of two elementwise launches per parameter tensor (~620).  The device-side table of (ema, param, numel)
 is built once per model pair and follows in-place parameter updates (addresses do not change); replaced
 parameters rebuild it.
+
+alpha is an ARGUMENT of that launch, so it cannot be part of a captured step.  Where the optimiser is
+`optim.FusedAdamW`, `attach_teacher(model, ema_model, alpha)` (`train_step.CapturedStep(ema_in_step=True)`)
+runs the same arithmetic inside the optimiser's own update launch, with alpha formed on the device from a
+step count that lives there: the same bits, no launch and no host call per step.
 """
 import os
 import sys

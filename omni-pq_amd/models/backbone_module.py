@@ -15,6 +15,8 @@ for _p in (_ROOT, os.path.join(_ROOT, "pointnet2")):
     if _p not in sys.path:
         sys.path.append(_p)
 
+import weakref  # noqa: E402
+
 from pointnet2_modules import PointnetSAModuleVotes, PointnetFPModule  # noqa: E402
 import pointnet2_utils  # noqa: E402
 
@@ -23,6 +25,33 @@ GROUP_AHEAD = True          # prefetched sampling chains also make the stages' c
 # (name, npoint, radius, nsample)
 _SA_GEOMETRY = (("sa1", 2048, 0.2, 64), ("sa2", 1024, 0.4, 32), ("sa3", 512, 0.8, 16),
                 ("sa4", 256, 1.2, 16))
+
+_STEP_STREAMS = []          # (weak reference to the owner, or None for a stream that lives as long as the process; stream)
+
+
+def new_step_stream(device, owner=None, avoid=()):
+    """A side stream for work that is forked off INSIDE a training step: the sampling chains here, the decoder's
+    (decoder_rows._side_stream), a model's weight-gradient flushes (PQ_Transformer._flush_stream).  torch hands streams out of a
+    pool of 32 per device, round-robin: a new Stream object can BE an earlier one.  That is harmless between two forks of one
+    step -- except for a sampling stream: the plan of the first captured batch is launched BEFORE the capture and its events are
+    waited for inside it, and once the same underlying stream has been pulled into the capture by another fork (the teacher's
+    forward in front of the student's, say) or is the capture stream itself, that wait is refused
+    (hipErrorStreamCaptureIsolation: the event's stream is capturing, the event is not part of the capture) and the capture is
+    lost.  So every stream handed out here is none of `avoid`, not the stream torch captures graphs on, and none of the streams
+    handed out earlier whose owner is still alive.  owner: the module the stream belongs to (held weakly)."""
+    _STEP_STREAMS[:] = [(o, s) for o, s in _STEP_STREAMS if o is None or o() is not None]
+    taken = {s.cuda_stream for _, s in _STEP_STREAMS}
+    taken |= {s.cuda_stream for s in avoid if s is not None}
+    cap = getattr(torch.cuda.graph, "default_capture_stream", None)
+    if cap is not None:
+        taken.add(cap.cuda_stream)
+    stream = torch.cuda.Stream(device=device)
+    for _ in range(64):
+        if stream.cuda_stream not in taken:
+            break
+        stream = torch.cuda.Stream(device=device)
+    _STEP_STREAMS.append((None if owner is None else weakref.ref(owner), stream))
+    return stream
 
 
 class Pointnet2Backbone(nn.Module):
@@ -67,23 +96,10 @@ class Pointnet2Backbone(nn.Module):
             state.pop(k, None)
         return state
 
-    @staticmethod
-    def _new_stream(device, avoid=()):
-        """A stream for a sampling chain that is neither one of `avoid` nor the stream torch captures graphs on.  torch
-        hands streams out of a pool of 32 per device, round-robin: a new Stream object can BE an earlier one.  The plan of the
-        first captured batch is launched before the capture and its events are waited for inside it; when the sampling stream
-        is the capture stream itself that wait is refused (hipErrorStreamCaptureIsolation: the event's stream is capturing,
-        the event is not part of the capture) and the capture is lost."""
-        taken = {s.cuda_stream for s in avoid if s is not None}
-        cap = getattr(torch.cuda.graph, "default_capture_stream", None)
-        if cap is not None:
-            taken.add(cap.cuda_stream)
-        stream = torch.cuda.Stream(device=device)
-        for _ in range(64):
-            if stream.cuda_stream not in taken:
-                break
-            stream = torch.cuda.Stream(device=device)
-        return stream
+    def _new_stream(self, device, avoid=()):
+        """A stream for a sampling chain that is neither one of `avoid`, nor a side stream another part of a step was given,
+        nor the stream torch captures graphs on (new_step_stream)."""
+        return new_step_stream(device, owner=self, avoid=avoid)
 
     def _side_stream(self, device):
         if self._side is None or self._side.device != device:

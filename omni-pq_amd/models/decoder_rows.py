@@ -251,7 +251,8 @@ def _side_stream(device):
     key = (device, torch.cuda.current_stream(device).cuda_stream)
     s = _SIDE.get(key)
     if s is None:
-        s = _SIDE[key] = torch.cuda.Stream(device)
+        from backbone_module import new_step_stream          # (not one of the sampling streams: see there)
+        s = _SIDE[key] = new_step_stream(device)
     return s
 
 

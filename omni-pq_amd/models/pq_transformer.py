@@ -24,7 +24,7 @@ for _p in (_HERE, _ROOT, os.path.join(_ROOT, "pointnet2")):
     if _p not in sys.path:
         sys.path.append(_p)
 
-from backbone_module import Pointnet2Backbone  # noqa: E402
+from backbone_module import Pointnet2Backbone, new_step_stream  # noqa: E402
 from transformer import TransformerDecoderLayer  # noqa: E402
 import transformer as transformer_mod  # noqa: E402
 import decoder_rows  # noqa: E402
@@ -764,7 +764,7 @@ class PQ_Transformer(nn.Module):
             return self.backbone._side_stream(device)
         streams = self.__dict__.setdefault("_omnipq_flush_streams", {})
         if device not in streams:
-            streams[device] = torch.cuda.Stream(device=device)
+            streams[device] = new_step_stream(device, owner=self)
         return streams[device]
 
     def _apply(self, fn, *args, **kwargs):

@@ -24,6 +24,12 @@ per MICRO-batch; each call is the same three launches (the omnipq_adamw_accum_* 
 f32 accumulator laid out like `exp_avg`, and every k-th call clips and applies the SUM -- the reference does not divide its
 loss by step_freq either; `grad_scale = 1 / k` gives the mean.  The micro-batch counter is a device word the launches read, so
 one captured graph serves every micro-batch; `micro` / `is_update_step` mirror it on the host without reading the device.
+
+Mean-teacher weight averaging (the reference's update_ema_variables, train.py:435-439 and :576): `attach_teacher(model,
+ema_model, decay)` makes every applying step average the teacher inside the finalise and update launches -- still three
+launches, 8 more bytes per parameter instead of a fourth launch of 12.  alpha = min(1 - 1/(global_step + 1), decay) is formed
+on the device from a step count that lives there, so a captured launch averages with the alpha of its own step; the teacher
+holds the bits `ema.update_ema_variables` would have left after the step.
 """
 import ctypes
 import os
@@ -39,6 +45,7 @@ for _p in (_HERE, os.path.join(_HERE, "pointnet2")):
 
 RECORD = np.dtype([("param", "<u8"), ("grad", "<u8"), ("exp_avg", "<u8"), ("exp_avg_sq", "<u8"), ("numel", "<i8"),
                    ("group", "<i4"), ("reserved", "<i4")])          # include/omnipq_optim.h: 48 bytes
+EMA_ONLY = np.dtype([("ema", "<u8"), ("param", "<u8"), ("numel", "<i8")])      # include/omnipq_optim.h: 24 bytes
 ROW = 8                  # doubles per hyper-parameter row, floats per coefficient row
 CHUNK = 4096             # elements per workgroup (a multiple of 1024); tools/bench_optimizer.py --chunks measures others
 _STAGES = 4              # pinned staging rows in rotation: a row is rewritten only after its own copy has completed
@@ -55,7 +62,8 @@ def _ptr(t):
 
 class _Table:
     """The device tables of one (parameter, gradient) address set."""
-    __slots__ = ("key", "shape_key", "records", "chunks", "partials", "nrec", "nchunks")
+    __slots__ = ("key", "shape_key", "records", "chunks", "partials", "nrec", "nchunks",
+                 "ema_ptrs", "ema_only", "only_chunks", "n_only", "n_only_chunks")     # the teacher's side (attach_teacher)
 
 
 class FusedAdamW(torch.optim.Optimizer):
@@ -102,6 +110,10 @@ class FusedAdamW(torch.optim.Optimizer):
             self.acc = torch.zeros(total + 4, dtype=torch.float32, device=dev)
             self.accum = torch.zeros(2, dtype=torch.int64, device=dev)
         self._micro, self._applied = 0, False
+        # mean-teacher averaging inside the launches (attach_teacher): nothing is allocated until a teacher is attached
+        self._teacher = None
+        self.ema_decay = 0.0
+        self.ema_state = self.ema_coef = None
         ngroups = len(self.param_groups)
         self.counters = torch.zeros(2, dtype=torch.int64, device=dev)             # t, skipped
         self.result = torch.zeros(4, dtype=torch.float32, device=dev)             # total_norm, clip_coef, found_nonfinite, g coefficient
@@ -171,7 +183,67 @@ class FusedAdamW(torch.optim.Optimizer):
         self._micro = (self._micro + 1) % self.accum_steps
         self._applied = self._micro == 0
 
+    # ---- the mean teacher ------------------------------------------------------------------------------------------------------
+    def attach_teacher(self, model, ema_model, decay, global_step=1):
+        """From now on every APPLYING step()/launch() also averages `ema_model` towards `model`, inside the finalise and update
+        launches (include/omnipq_optim.h: omnipq_adamw_ema_*): the reference's update_ema_variables(model, ema_model, decay,
+        global_step) of train.py:435-439 and :576 with the bits of ema.update_ema_variables called after the step, and
+        global_step counted on the device -- a captured launch() takes the alpha of its own step on every replay.  The pairs are
+        zip(ema_model.parameters(), model.parameters()), as in ema.py; a parameter without a gradient is averaged too, and so
+        is every parameter on a step that is skipped for a non-finite gradient norm.  With accum_steps = k only the k-th
+        micro-batch averages and counts.  global_step: the value the FIRST averaging uses; 1 is the reference's first
+        (train.py increments model.i in front of the call), a resumed run passes its own or calls set_global_step().
+        `ema_decay` may be changed at any time, sync_hyperparameters() stages it like max_norm.  Attach before a capture: a
+        captured launch keeps the tables and entry points it was recorded with."""
+        decay = float(decay)
+        if not 0.0 <= decay <= 1.0:
+            raise ValueError(f"FusedAdamW.attach_teacher: decay must be in [0, 1], not {decay!r}")
+        if isinstance(global_step, bool) or not isinstance(global_step, (int, np.integer)) or global_step < 0:
+            raise ValueError("FusedAdamW.attach_teacher: global_step must be an integer >= 0")
+        teacher, student = list(ema_model.parameters()), list(model.parameters())
+        if len(teacher) != len(student):
+            raise ValueError(f"FusedAdamW.attach_teacher: the teacher has {len(teacher)} parameters, the model {len(student)}")
+        for e, p in zip(teacher, student):
+            if p not in self._offset:
+                raise ValueError("FusedAdamW.attach_teacher: the model has a parameter this optimiser does not own "
+                                 f"(shape {tuple(p.shape)})")
+            if e.dtype != torch.float32 or not e.is_contiguous() or e.shape != p.shape or e.device != p.device:
+                raise ValueError("FusedAdamW.attach_teacher: every teacher parameter must be a contiguous float32 tensor of its "
+                                 f"partner's shape on its partner's device (got {e.dtype}, {tuple(e.shape)} on {e.device} for "
+                                 f"{tuple(p.shape)} on {p.device})")
+        self._teacher = list(zip(teacher, student))
+        self.ema_decay = decay
+        self.ema_state = torch.full((1,), int(global_step), dtype=torch.int64, device=self.device)
+        self.ema_coef = torch.zeros(2, dtype=torch.float32, device=self.device)          # alpha, beta of the last averaging
+        self._table_hit = None
+        self.sync_hyperparameters()
+
+    def detach_teacher(self):
+        """Back to the launches of an optimiser that never had a teacher; the teacher's weights stay as they are."""
+        self._teacher = None
+        self.ema_decay = 0.0
+        self.ema_state = self.ema_coef = None
+        self._table_hit = None
+        self.sync_hyperparameters()
+
+    @property
+    def global_step(self):
+        """the global_step the NEXT averaging will use (reads the device); None without a teacher.  It is the model's `i` of the
+        reference, not optimiser state: state_dict() does not carry it, a resumed run hands it to attach_teacher() or
+        set_global_step()."""
+        return None if self.ema_state is None else int(self.ema_state[0])
+
+    def set_global_step(self, i):
+        if self.ema_state is None:
+            raise RuntimeError("FusedAdamW.set_global_step: no teacher is attached")
+        if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or i < 0:
+            raise ValueError("FusedAdamW.set_global_step: an integer >= 0")
+        with torch.no_grad():
+            self.ema_state.fill_(int(i))
+
     def state_dict(self):
+        """torch.optim.AdamW's state_dict, with or without a teacher: global_step, the decay and the teacher's weights belong
+        to the model pair and its training loop, not to the optimiser."""
         t = float(self.t)                          # the one host read of the device counter
         for st in self.state.values():
             if "step" in st:
@@ -212,11 +284,11 @@ class FusedAdamW(torch.optim.Optimizer):
         rows = np.zeros((len(self.param_groups) + 1, ROW), dtype=np.float64)
         for i, g in enumerate(self.param_groups):
             rows[i, :5] = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
-        rows[-1, :2] = (self.max_norm, self.grad_scale)
+        rows[-1, :3] = (self.max_norm, self.grad_scale, float(self.ema_decay))
         return rows
 
     def sync_hyperparameters(self):
-        """Stage the rows {lr, beta1, beta2, eps, weight_decay} of every param_group and {max_norm, grad_scale} to the device
+        """Stage the rows {lr, beta1, beta2, eps, weight_decay} of every param_group and {max_norm, grad_scale, ema_decay} to the device
         when a host value has changed since the last call: pinned staging tensor, non-blocking copy on the current stream, no
         host read of the device.  An LR scheduler keeps working on `param_groups`; step() calls this, and so does
         CapturedStep.step() in front of its replay.  -> True when rows were sent."""
@@ -261,16 +333,42 @@ class FusedAdamW(torch.optim.Optimizer):
             raise RuntimeError(f"omnipq_adamw_check_table failed: {ext._lib0.omnipq_error_string(rc).decode()} ({rc})")
         return rec, chunks
 
+    def _teacher_key(self):
+        return None if self._teacher is None else tuple((e.data_ptr(), p.data_ptr(), e.numel()) for e, p in self._teacher)
+
+    def _host_teacher_tables(self, active):
+        """-> (the teacher's pointer per record of `active`, the {ema, param, numel} records of the pairs whose parameter has no
+        gradient, their chunk list), validated by the library"""
+        ext = _ext()
+        partner = {p: e for e, p in self._teacher}
+        ptrs = np.asarray([partner[p].data_ptr() for _, p in active], dtype=np.uint64)
+        in_table = {p for _, p in active}
+        rest = [(e, p) for e, p in self._teacher if p not in in_table]
+        only = np.zeros(len(rest), dtype=EMA_ONLY)
+        chunks = []
+        for i, (e, p) in enumerate(rest):
+            only[i] = (e.data_ptr(), p.data_ptr(), e.numel())
+            chunks += [(i, c) for c in range((e.numel() + self.chunk_elems - 1) // self.chunk_elems)]
+        chunks = np.asarray(chunks, dtype=np.int32).reshape(-1, 2)
+        rc = ext._lib0.omnipq_adamw_check_ema_table(len(ptrs), ptrs.ctypes.data_as(ctypes.c_void_p), len(only),
+                                                    only.ctypes.data_as(ctypes.c_void_p), int(chunks.shape[0]),
+                                                    chunks.ctypes.data_as(ctypes.c_void_p), self.chunk_elems)
+        if rc != 0:
+            raise RuntimeError(f"omnipq_adamw_check_ema_table failed: {ext._lib0.omnipq_error_string(rc).decode()} ({rc})")
+        return ptrs, only, chunks
+
     def _table(self, capturing=False):
         """The device table, cached and keyed on the (parameter, gradient) addresses (like ema._table).  capturing: nothing may
         be uploaded now -- the launches are recorded against the table buffers of the last eager step, which must cover the same
         parameters, and `retarget()` writes the addresses of the captured gradients into them once the capture has ended."""
         active = self._active()
-        key = tuple((p.data_ptr(), p.grad.data_ptr(), p.numel()) for _, p in active)
+        # (the teacher's addresses are part of both keys: another teacher is another table, never a re-targeted one)
+        tkey = self._teacher_key()
+        key = (tuple((p.data_ptr(), p.grad.data_ptr(), p.numel()) for _, p in active), tkey)
         hit = self._table_hit
         if hit is not None and hit.key == key:
             return hit
-        shape_key = tuple((p.data_ptr(), p.numel(), gi) for gi, p in active)
+        shape_key = (tuple((p.data_ptr(), p.numel(), gi) for gi, p in active), tkey)
         if self._micro != 0 and hit is not None and hit.shape_key != shape_key:
             # a parameter that was absent at micro == 0 would add into whatever an earlier step left in its accumulator
             raise RuntimeError(f"FusedAdamW: the set of parameters with gradients changed after {self._micro} of "
@@ -293,6 +391,15 @@ class FusedAdamW(torch.optim.Optimizer):
         hit.records = torch.from_numpy(rec.view(np.uint8).copy()).to(self.device)
         hit.chunks = torch.from_numpy(chunks.copy()).to(self.device)
         hit.partials = torch.zeros(max(hit.nchunks, 1), dtype=torch.float64, device=self.device)
+        hit.ema_ptrs = hit.ema_only = hit.only_chunks = None
+        hit.n_only = hit.n_only_chunks = 0
+        if self._teacher is not None:
+            ptrs, only, only_chunks = self._host_teacher_tables(active)
+            hit.n_only, hit.n_only_chunks = len(only), int(only_chunks.shape[0])
+            hit.ema_ptrs = torch.from_numpy(ptrs.view(np.uint8).copy()).to(self.device)
+            if hit.n_only:
+                hit.ema_only = torch.from_numpy(only.view(np.uint8).copy()).to(self.device)
+                hit.only_chunks = torch.from_numpy(only_chunks.copy()).to(self.device)
         self._table_hit = hit
         self.table_builds += 1
         return hit
@@ -313,6 +420,27 @@ class FusedAdamW(torch.optim.Optimizer):
         if tab.nrec == 0:
             return self.grad_total_norm
         lib, ng = ext._lib0, len(self.param_groups)
+        if self._teacher is not None:
+            # the same three launches with the teacher's averaging inside the last two (accum is None: the plain family)
+            if self.accum_steps > 1:
+                ext._run(lib.omnipq_adamw_accum_sqnorm, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.chunks),
+                         self.chunk_elems, _ptr(self._hyper), ng, _ptr(self.exp_avg), _ptr(self.acc), _ptr(self.accum),
+                         _ptr(tab.partials))
+            else:
+                ext._run(lib.omnipq_adamw_grad_sqnorm, self.result, tab.nrec, tab.nchunks, _ptr(tab.records),
+                         _ptr(tab.chunks), self.chunk_elems, _ptr(self._hyper), ng, _ptr(tab.partials))
+            ext._run(lib.omnipq_adamw_ema_finalize, self.result, tab.nchunks, _ptr(tab.partials), _ptr(self._hyper), ng,
+                     self.accum_steps, _ptr(self.counters), _ptr(self.accum), _ptr(self.ema_state), _ptr(self.result),
+                     _ptr(self._coef), _ptr(self.ema_coef))
+            ext._run(lib.omnipq_adamw_ema_update, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.ema_ptrs),
+                     _ptr(tab.chunks), self.chunk_elems, tab.n_only, tab.n_only_chunks, _ptr(tab.ema_only),
+                     _ptr(tab.only_chunks), _ptr(self.exp_avg), _ptr(self.acc), _ptr(self.accum), _ptr(self._coef),
+                     _ptr(self.ema_coef), _ptr(self.result))
+            if self.accum_steps > 1:
+                self.replayed()
+            else:
+                self._applied = True
+            return self.grad_total_norm
         if self.accum_steps > 1:
             ext._run(lib.omnipq_adamw_accum_sqnorm, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.chunks),
                      self.chunk_elems, _ptr(self._hyper), ng, _ptr(self.exp_avg), _ptr(self.acc), _ptr(self.accum),
@@ -352,15 +480,19 @@ class FusedAdamW(torch.optim.Optimizer):
     # ---- save / restore (CapturedStep's warm-up and capture runs must leave no trace) ---------------------------------------
     def _saved_tensors(self):
         return (self.exp_avg, self.exp_avg_sq, self.counters, self.result) + \
-            ((self.acc, self.accum) if self.accum_steps > 1 else ())
+            ((self.acc, self.accum) if self.accum_steps > 1 else ()) + \
+            ((self.ema_state, self.ema_coef) + tuple(e for e, _ in self._teacher) if self._teacher is not None else ())
 
     def snapshot(self):
         """moments, counters and -- the warm-up and capture runs advance them too -- the accumulator, the device micro-batch
-        counter and its host mirror"""
+        counter and its host mirror; with a teacher attached its global_step, coefficients and weights as well"""
         return [t.detach().clone() for t in self._saved_tensors()] + [(self._micro, self._applied)]
 
     def restore(self, saved):
+        tensors = self._saved_tensors()
+        if len(tensors) != len(saved) - 1:
+            raise RuntimeError("FusedAdamW.restore: a teacher was attached or detached since the snapshot was taken")
         with torch.no_grad():
-            for t, s in zip(self._saved_tensors(), saved):
+            for t, s in zip(tensors, saved):
                 t.copy_(s)
         self._micro, self._applied = saved[-1]

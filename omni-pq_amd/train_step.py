@@ -64,6 +64,13 @@ class CapturedStep:
                      after `optimizer.step()`, where the reference calls update_ema_variables (train.py:560-576) -- one
                      launch, alpha = min(1 - 1/(global_step + 1), ema) evaluated per call.  `ema` = the decay (a
                      (decay, step) pair is accepted for old callers; its step is ignored).
+    ema_in_step      False (default): as above.  True (needs `teacher`, a scalar `ema` and optimizer=optim.FusedAdamW): the
+                     averaging runs INSIDE the step, in the optimizer's finalise and update launches
+                     (optimizer.attach_teacher(net, teacher, ema) is called here): alpha is formed on the device from a step
+                     count that lives there, so every replay averages with its own alpha, on applying steps only.  The order
+                     is the reference's -- the teacher's forward runs on the old weights, the averaging follows the update.
+                     update_teacher() then raises; the first averaging uses global_step 1 (optimizer.set_global_step(i)
+                     for a resumed run).  Building the stepper changes neither the teacher nor the global step.
     world / buckets  data parallelism: `buckets` = data_parallel.GradientBuckets(net, world, group) or None (single rank).
     defer            False: leave the weight gradients to autograd (needed under DistributedDataParallel).
     lookahead        1 (default): the sampling chain of the NEXT batch runs underneath this step, so one step contains a whole
@@ -106,7 +113,7 @@ class CapturedStep:
     def __init__(self, net, criterion, example_inputs, example_labels=None, *, model=None, amp_dtype=torch.bfloat16,
                  loss_scale=1.0, graph=True, prefetch="forward", fps_footprint=None, teacher=None, teacher_example=None,
                  ema=None, buckets=None, defer=True, warmup=3, distributed=False, before_capture=None,
-                 teacher_to_criterion=False, lookahead=1, head_rounds=None, optimizer=None, step_freq=1):
+                 teacher_to_criterion=False, lookahead=1, head_rounds=None, optimizer=None, step_freq=1, ema_in_step=False):
         if optimizer is not None:
             import optim
             if not isinstance(optimizer, optim.FusedAdamW):
@@ -150,6 +157,13 @@ class CapturedStep:
             raise TypeError("CapturedStep(ema=...): pass the decay alone and call update_teacher(global_step) after "
                             "optimizer.step(); the (decay, step) pair of earlier versions is no longer accepted")
         self.ema = ema
+        self.ema_in_step = bool(ema_in_step)
+        if self.ema_in_step:
+            if teacher is None or optimizer is None or isinstance(ema, bool) or not isinstance(ema, (int, float)):
+                raise ValueError("CapturedStep(ema_in_step=True): the teacher is averaged by the optimizer's own launches, so it "
+                                 "needs teacher=, a scalar ema= decay and optimizer=optim.FusedAdamW(...)")
+            # before the warm-up: its eager steps build the tables the captured launches read
+            optimizer.attach_teacher(net, teacher, ema)
         self.teacher_to_criterion = bool(teacher_to_criterion)
         self.teacher_end_points = None
         self._grads = None             # graph mode: (parameter, static gradient tensor) pairs, re-attached after every replay
@@ -272,6 +286,9 @@ class CapturedStep:
         reference's update_ema_variables (train.py:435-439), to be called where the reference calls it -- after
         optimizer.step() (train.py:560-576).  One launch on the current stream, outside the captured step: alpha is a
         kernel ARGUMENT and changes with every call, which a replayed launch could not follow."""
+        if self.ema_in_step:
+            raise RuntimeError("CapturedStep.update_teacher: this stepper was built with ema_in_step=True -- every applying step "
+                               "averages the teacher inside the optimizer's launches, a second averaging would count twice")
         if self.teacher is None or self.ema is None:
             return None
         self._steps_unaveraged = 0
@@ -289,7 +306,8 @@ class CapturedStep:
         keep = [(b, b.detach().clone()) for m in (net, teacher) if m is not None for b in m.buffers()]
         opt_saved = None
         if self.optimizer is not None:
-            # ... and so is what the in-graph optimizer does to the parameters, its moments and its counters
+            # ... and so is what the in-graph optimizer does to the parameters, its moments and its counters (ema_in_step: to
+            # the teacher's parameters and the global step as well -- optimizer.snapshot() carries them)
             keep += [(p, p.detach().clone()) for g in self.optimizer.param_groups for p in g["params"]]
             opt_saved = self.optimizer.snapshot()
             self.optimizer.sync_hyperparameters()
@@ -370,7 +388,7 @@ class CapturedStep:
             raise ValueError("CapturedStep.step: after_next_inputs needs a stepper built with lookahead=2")
         # will this call apply the (accumulated) gradients?  Known up front: the optimizer mirrors its device counter
         applies = self.optimizer is None or self.optimizer.micro == self.step_freq - 1
-        if self.teacher is not None and self.ema is not None and applies:
+        if self.teacher is not None and self.ema is not None and applies and not self.ema_in_step:
             self._steps_unaveraged = getattr(self, "_steps_unaveraged", 0) + 1
             if self._steps_unaveraged == 4:
                 import warnings

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """What the three weight-changing lines of the training step (train.py:562-566) cost on the procedural PQ_Transformer with the
-reference's two parameter groups (train.py:364-374), seven ways, all live in one process and taking turns:
+reference's two parameter groups (train.py:364-374), eleven ways, all live in one process and taking turns:
 
     (a) torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW as train.py constructs it        what a user ran before optim.py
     (b) the same with fused=True
@@ -12,6 +12,12 @@ reference's two parameter groups (train.py:364-374), seven ways, all live in one
     (g) the same accumulation from the host: a replayed CapturedStep without optimiser, the 519 gradient tensors copied
         (first micro-batch) or added (second, torch._foreach_add_) into tensors of the caller's, FusedAdamW.step() on the
         sum every second call; one iteration = one micro-batch
+    (h) optim.FusedAdamW.step() with an attached teacher (attach_teacher): the mean-teacher weight averaging of
+        train.py:435-439 inside the same three launches -- 36 bytes per parameter
+    (i) optim.FusedAdamW.step() followed by ema.update_ema_variables: the averaging as a fourth launch -- 40 bytes per parameter
+    (j) the mean-teacher step (student forward + backward, teacher forward, clip + AdamW, averaging) as ONE replay:
+        CapturedStep(teacher=..., optimizer=FusedAdamW, ema_in_step=True)
+    (k) the same step as a replay followed by stepper.update_teacher(global_step)
 
 Every case is timed `--rounds` times (>= 5), interleaved, over a window of `--iters` iterations that ends in a device
 synchronise: WALL time per iteration, median and spread (max - min) over the rounds.  A last pass runs a few iterations of
@@ -188,6 +194,55 @@ def main():
             opt_g.step()
     cases["g_replay_accumulating_from_the_host"] = run_g
 
+    # ---- the mean teacher: averaging inside the optimiser's launches (h, j) against the separate launch (i, k) --------------
+    import ema
+    EMA_DECAY = 0.999
+
+    def teacher_of(net):
+        t = copy.deepcopy(net)
+        for p in t.parameters():
+            p.requires_grad_(False)
+            p.grad = None
+        return t
+
+    net_h = with_static_grads(copy.deepcopy(base))
+    teacher_h = teacher_of(net_h)
+    opt_h = optim.FusedAdamW(groups(net_h), lr=LR, weight_decay=WD, max_norm=CLIP)
+    opt_h.attach_teacher(net_h, teacher_h, EMA_DECAY)
+    cases["h_fused_adamw_with_teacher_eager"] = opt_h.step
+    net_i = with_static_grads(copy.deepcopy(base))
+    teacher_i = teacher_of(net_i)
+    opt_i = optim.FusedAdamW(groups(net_i), lr=LR, weight_decay=WD, max_norm=CLIP)
+    count.update(i=0, j=0, k=0)
+
+    def run_i():
+        count["i"] += 1
+        opt_i.step()
+        ema.update_ema_variables(net_i, teacher_i, EMA_DECAY, count["i"])
+    cases["i_fused_adamw_then_ema_update_eager"] = run_i
+
+    net_j = copy.deepcopy(base)
+    teacher_j = teacher_of(net_j).train()
+    opt_j = optim.FusedAdamW(groups(net_j), lr=LR, weight_decay=WD, max_norm=CLIP)
+    st_j = train_step.CapturedStep(net_j, criterion, {"point_clouds": pool[0]}, teacher=teacher_j, ema=EMA_DECAY, optimizer=opt_j,
+                                   ema_in_step=True)
+    net_k = copy.deepcopy(base)
+    teacher_k = teacher_of(net_k).train()
+    opt_k = optim.FusedAdamW(groups(net_k), lr=LR, weight_decay=WD, max_norm=CLIP)
+    st_k = train_step.CapturedStep(net_k, criterion, {"point_clouds": pool[0]}, teacher=teacher_k, ema=EMA_DECAY, optimizer=opt_k)
+    assert st_j.launch == st_k.launch == "hipGraph replay"
+
+    def run_j():
+        count["j"] += 1
+        st_j.step(None, None, next_inputs=pool[count["j"] % len(pool)])
+    cases["j_mean_teacher_replay_averaging_inside"] = run_j
+
+    def run_k():
+        count["k"] += 1
+        st_k.step(None, None, next_inputs=pool[count["k"] % len(pool)])
+        st_k.update_teacher(count["k"])
+    cases["k_mean_teacher_replay_then_update_teacher"] = run_k
+
     walls = {k: [] for k in cases}
     for rnd in range(args.rounds):
         for name, fn in cases.items():
@@ -201,10 +256,13 @@ def main():
             walls[name].append((time.perf_counter() - t0) * 1e3 / args.iters)
             print(f"round {rnd} {name:40s} {walls[name][-1]:8.4f} ms wall per iteration", flush=True)
     assert opt_f.t == opt_g.t == count["f"] // 2 == count["g"] // 2, (opt_f.t, opt_g.t, count)
-    for name, opt in list(fused.items()) + [("d", opt_d), ("f", opt_f), ("g", opt_g)]:
+    assert opt_h.global_step == 1 + opt_h.t and opt_j.global_step == 1 + count["j"] == 1 + opt_j.t, (opt_h.t, opt_j.t, count)
+    for name, opt in list(fused.items()) + [("d", opt_d), ("f", opt_f), ("g", opt_g), ("h", opt_h), ("i", opt_i), ("j", opt_j),
+                                            ("k", opt_k)]:
         assert opt.skipped == 0, f"{name}: {opt.skipped} steps were skipped for a non-finite gradient norm -- not a measurement"
     assert torch.isfinite(st_d.static_loss).item() and torch.isfinite(st_e.static_loss).item()
     assert torch.isfinite(st_f.static_loss).item() and torch.isfinite(st_g.static_loss).item()
+    assert torch.isfinite(st_j.static_loss).item() and torch.isfinite(st_k.static_loss).item()
     import pointnet2_utils
     pointnet2_utils._ext.fps_check()
 
@@ -225,6 +283,15 @@ def main():
     out["requirements"] = [verdict("c_fused_adamw_eager", "a_torch_adamw_clip"),
                            verdict("d_replay_with_fused_adamw_inside", "e_replay_then_torch_adamw_clip"),
                            verdict("f_replay_accumulating_in_the_graph", "g_replay_accumulating_from_the_host")]
+
+    def not_slower(new, old):
+        """the in-launch averaging must not be slower than the separate launch by more than the spread of the latter's rounds"""
+        n, o = out["cases"][new], out["cases"][old]
+        return {"new": new, "old": old, "gain_ms": round(o["wall_ms_median"] - n["wall_ms_median"], 4),
+                "old_spread_ms": o["wall_ms_spread"],
+                "holds": bool(n["wall_ms_median"] - o["wall_ms_median"] <= o["wall_ms_spread"])}
+    out["not_slower"] = [not_slower("h_fused_adamw_with_teacher_eager", "i_fused_adamw_then_ema_update_eager"),
+                         not_slower("j_mean_teacher_replay_averaging_inside", "k_mean_teacher_replay_then_update_teacher")]
     print(json.dumps(out), flush=True)           # (kept even if the profiler pass below does not come back)
 
     if not args.no_kernel_time:
@@ -243,14 +310,26 @@ def main():
                 c[f"{key}_fraction_of_6.25_TBps_copy_ceiling"] = round(rate / 6.25e12, 4)
                 print(f"{name:40s} {need / 1e6:.0f} MB / {key} time = {rate / 1e12:.3f} TB/s = {rate / 8e12:.1%} of 8 TB/s, "
                       f"{rate / 6.25e12:.1%} of the 6.25 TB/s copy ceiling", flush=True)
+    # the averaging inside the launches (h: the norm reads g, the update reads p, g, m, v, e and writes p, m, v, e) and as a
+    # fourth launch (i: 32 bytes as in (c), then e and p read and e written)
+    for name, per_param in (("h_fused_adamw_with_teacher_eager", 36), ("i_fused_adamw_then_ema_update_eager", 40)):
+        c = out["cases"][name]
+        c["bytes_needed"] = per_param * nparam
+        for key, t in (("wall", c["wall_ms_median"]), ("kernel", c["kernel_ms"])):
+            if t:
+                rate = per_param * nparam / (t * 1e-3)
+                c[f"{key}_bytes_per_s"] = round(rate, 0)
+                c[f"{key}_fraction_of_6.25_TBps_copy_ceiling"] = round(rate / 6.25e12, 4)
+                print(f"{name:40s} {per_param * nparam / 1e6:.0f} MB ({per_param} B per parameter) / {key} time = "
+                      f"{rate / 1e12:.3f} TB/s = {rate / 6.25e12:.1%} of the 6.25 TB/s copy ceiling", flush=True)
     if not args.no_kernel_time:
         # the accumulate launch alone, on a non-first micro-batch: 12 bytes per parameter
-        net_h = with_static_grads(copy.deepcopy(base))
-        opt_h = optim.FusedAdamW(groups(net_h), lr=LR, weight_decay=WD, max_norm=CLIP, accum_steps=10 ** 6)
+        net_acc = with_static_grads(copy.deepcopy(base))
+        opt_acc = optim.FusedAdamW(groups(net_acc), lr=LR, weight_decay=WD, max_norm=CLIP, accum_steps=10 ** 6)
         for _ in range(args.warmup):
-            opt_h.step()
-        ms = kernel_time_ms(opt_h.step, 20, match="adamw_grad_sqnorm_kernel")
-        assert opt_h.t == 0 and 0 < opt_h.micro < 10 ** 6
+            opt_acc.step()
+        ms = kernel_time_ms(opt_acc.step, 20, match="adamw_grad_sqnorm_kernel")
+        assert opt_acc.t == 0 and 0 < opt_acc.micro < 10 ** 6
         acc = {"bytes_needed": 12 * nparam, "kernel_ms": None if ms is None else round(ms, 4)}
         if ms:
             rate = 12 * nparam / (ms * 1e-3)
