@@ -11,7 +11,7 @@ import torch.nn.functional as F  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
-for _p in (_ROOT, os.path.join(_ROOT, "pointnet2")):
+for _p in (_HERE, _ROOT, os.path.join(_ROOT, "pointnet2")):
     if _p not in sys.path:
         sys.path.append(_p)
 
@@ -19,12 +19,16 @@ import weakref  # noqa: E402
 
 from pointnet2_modules import PointnetSAModuleVotes, PointnetFPModule  # noqa: E402
 import pointnet2_utils  # noqa: E402
+import chain_plan  # noqa: E402
+from chain_plan import Ahead, ChainPlan, ExtraLevel, Head, Pending, Tail  # noqa: E402
 
 GROUP_AHEAD = True          # prefetched sampling chains also make the stages' centres / ball queries / row plans (see _launch_plan)
 
 # (name, npoint, radius, nsample)
 _SA_GEOMETRY = (("sa1", 2048, 0.2, 64), ("sa2", 1024, 0.4, 32), ("sa3", 512, 0.8, 16),
                 ("sa4", 256, 1.2, 16))
+_SA_NAMES = tuple(g[0] for g in _SA_GEOMETRY)
+_FP_PAIRS = ((2, 3), (1, 2))        # (unknown stage, known stage) of fp1: sa3 <- sa4 and fp2: sa2 <- sa3
 
 _STEP_STREAMS = []          # (weak reference to the owner, or None for a stream that lives as long as the process; stream)
 
@@ -69,7 +73,7 @@ class Pointnet2Backbone(nn.Module):
             setattr(self, name, PointnetSAModuleVotes(npoint=npoint, radius=radius, nsample=nsample,
                                                       mlp=[ci] + cm + [co], use_xyz=True,
                                                       normalize_xyz=True))
-        for name_ in ("sa1", "sa2", "sa3", "sa4"):
+        for name_ in _SA_NAMES:
             getattr(self, name_).omnipq_stage = name_      # label of the stage in per-stage timings (sa_fused.run)
         self.fp1 = PointnetFPModule(mlp=[256 * width + 256 * width, 256 * width, 256 * width])
         self.fp2 = PointnetFPModule(mlp=[256 * width + 256 * width, 256 * width, 288])
@@ -81,9 +85,10 @@ class Pointnet2Backbone(nn.Module):
     # they run on a side stream: the sa1 pass can be started one batch ahead (`prefetch`), the
     # later ones overlap with the MLP of the previous layer.  Results are identical to calling
     # furthest_point_sample inside each SA layer (reference pointnet2_modules.py:233-236).
-    _plan = None
+    _plan = None            # chain_plan.ChainPlan of the chain in flight
+    _pending = None         # chain_plan.Pending: the chain that starts inside the next forward()
     _side = None
-    _extra = None
+    _extra = None           # chain_plan.ExtraLevel of the batch just run through forward() (take_extra)
     # optional extra level of the plan: {"sa2": npoint} = also sample npoint of the sa2 centres (the model's
     # FPSModule on the seeds, pq_transformer.py:211-212, is such a coordinate-only sampling)
     plan_extra = None
@@ -113,8 +118,8 @@ class Pointnet2Backbone(nn.Module):
     # level at round k instead of sampling from 0.  Everything behind sa1's picks is the same code.  Indices are identical:
     # _ext.furthest_point_sampling_resume continues a sampling from exactly that state.
     _head_side = None
-    _head = None            # host record of the head in flight: {"rounds", "event", "key", "trusted"}
-    _tail = None            # ... of the handed-over state the next resumed chain continues: {"rounds", "key", "trusted"}
+    _head = None            # chain_plan.Head: the head in flight
+    _tail = None            # chain_plan.Tail: the handed-over state the next resumed chain continues
     resumed_levels = 0      # sa1 levels that continued a head (launched or captured) -- for tests and A/B scripts
 
     def _head_stream(self, device):
@@ -163,7 +168,7 @@ class Pointnet2Backbone(nn.Module):
             ext.furthest_point_sampling_resume(xyz, st["head_idx"], st["head_temp"], 0, rounds, small_footprint=footprint == "small")
             ev = torch.cuda.Event()
             ev.record(side)
-        self._head = {"rounds": rounds, "event": ev, "key": self._key(pointcloud), "trusted": trusted, "src": pointcloud}
+        self._head = Head(rounds, ev, self._key(pointcloud), trusted, pointcloud)
 
     def hand_over_head(self):
         """Head state -> tail state on the current stream (temp and idx[:, :rounds]: 1.3 MB at 8 x 40 000 points), ordered
@@ -171,14 +176,23 @@ class Pointnet2Backbone(nn.Module):
         head, self._head = self._head, None
         if head is None:
             raise RuntimeError("hand_over_head: no head was sampled (prefetch_head)")
-        st = self._split_buffers(head["src"])
-        cur = torch.cuda.current_stream(head["src"].device)
-        cur.wait_event(head["event"])
-        k = head["rounds"]
+        st = self._split_buffers(head.src)
+        cur = torch.cuda.current_stream(head.src.device)
+        cur.wait_event(head.event)
+        k = head.rounds
         with torch.no_grad():
             st["tail_temp"].copy_(st["head_temp"])
             st["tail_idx"][:, :k].copy_(st["head_idx"][:, :k])
-        self._tail = {"rounds": k, "key": head["key"], "trusted": head["trusted"]}
+        self._tail = Tail(k, head.key, head.trusted)
+
+    def _take_tail(self, pointcloud, trusted):
+        """The handed-over tail state if it is this cloud's (or vouched for), else None: the level is sampled from 0."""
+        tail, self._tail = self._tail, None
+        if tail is not None and not (tail.trusted or trusted or tail.key == self._key(pointcloud)):
+            tail = None                    # the head of some other cloud
+        if tail is not None:
+            self.resumed_levels += 1
+        return tail
 
     @staticmethod
     def _key(xyz_src):
@@ -191,190 +205,139 @@ class Pointnet2Backbone(nn.Module):
         bufs = self.__dict__.setdefault("_plan_bufs", {})
         if key not in bufs:
             bufs[key] = [torch.zeros((pointcloud.shape[0], getattr(self, n).npoint), device=pointcloud.device,
-                                     dtype=torch.int32) for n in ("sa1", "sa2", "sa3", "sa4")]
+                                     dtype=torch.int32) for n in _SA_NAMES]
         return bufs[key]
 
     # Grouping ahead of the stages (round 5).  The centres, the ball-query indices and the row plan of a stage depend on
     # coordinates only, like the sampling itself: a chain started by prefetch() appends them for all four stages (gather_xyz,
     # ball query, the plan's three small kernels: ~0.25 ms and ~14 launches that otherwise sit on the main stream between the
-    # stages' GEMMs) and leaves them in ONE flat persistent buffer; forward() takes it with one copy and hands every stage its
-    # views on the index tensor (`inds.omnipq_group`).  Same kernels, same inputs: identical results.  Switch: GROUP_AHEAD.
+    # stages' GEMMs) and leaves them in ONE flat persistent buffer (chain_plan.chain_layout says where); forward() takes it
+    # with one copy and hands every stage its chain_plan.StageAhead on the index tensor (`inds.omnipq_stage_ahead`).  Same
+    # kernels, same inputs: identical results.  Switch: GROUP_AHEAD.
 
-    def _group_layout(self, B, n_points):
-        """-> (total int32 words, [(name, M, S, n_src, off_xyz, off_idx, off_plan | None)])"""
+    def _chain_layout(self, B, n_points):
+        """Where the pieces of a chain launched NOW lie: sa_fused's switches are read here, at launch time."""
         import sa_fused
-        r4 = lambda n: (n + 3) // 4 * 4
-        off, levels, n_src = 0, [], n_points
-        for name in ("sa1", "sa2", "sa3", "sa4"):
-            mod = getattr(self, name)
-            M, S = mod.npoint, mod.nsample
-            P = B * M * S
-            o_inds, off = off, off + r4(B * M)
-            o_xyz, off = off, off + r4(B * M * 3)
-            o_idx, off = off, off + r4(P)
-            o_plan = None
-            if sa_fused.plan_static_ok(S, P):
-                o_plan, off = off, off + sum(sa_fused.plan_words(B, M, P))
-            o_csr = None
-            if name != "sa1":           # stages with features: the CSR "which grouped positions read point k" of their backward
-                o_csr, off = off, off + r4(B * (n_src + 1)) + r4(P)
-            levels.append((name, M, S, n_src, o_xyz, o_idx, o_plan, o_csr, o_inds))
-            n_src = M
-        # the two feature-propagation modules (fp1: sa3 <- sa4, fp2: sa2 <- sa3): 3-NN weights / indices and the CSR of their
-        # backward, per (unknown level, known level)
-        fps = []
-        for u, k in ((2, 3), (1, 2)):
-            n, m = levels[u][1], levels[k][1]
-            o_w, off = off, off + r4(B * n * 3)
-            o_i, off = off, off + r4(B * n * 3)
-            o_o, off = off, off + r4(B * (m + 1))
-            o_r, off = off, off + r4(B * n * 3)
-            fps.append((u, k, n, m, o_w, o_i, o_o, o_r))
-        # the sampled indices themselves (copied in at the end of the chain) and the extra level's
-        extra = None
-        if self.plan_extra:
-            (ename, en), = list(self.plan_extra.items())[:1]
-            extra = (ename, en, off)
-            off += r4(B * en)
-        return off, levels, fps, extra
+        stages = tuple((n, getattr(self, n).npoint, getattr(self, n).nsample) for n in _SA_NAMES)
+        planned = tuple(sa_fused.plan_static_ok(S, B * M * S) for _, M, S in stages)
+        words = tuple(sum(sa_fused.plan_words(B, M, B * M * S)) for _, M, S in stages)
+        extra = next(iter(self.plan_extra.items())) if self.plan_extra else None
+        return chain_plan.chain_layout(B, n_points, stages, planned, words, _FP_PAIRS, extra, sa_fused.PLAN_GROUP)
 
-    def _group_views(self, flat, B, n_points, layout=None):
-        """flat int32 -> ([(centres (B,M,3) f32, idx (B,M,S) i32, plan state (flat i32) | None, (offsets, order) | None)] per stage,
-        [(unknown level, known level, weight (B,n,3) f32, idx (B,n,3) i32, offsets (B,m+1), order (B,3n))] per FP module)"""
-        import sa_fused
-        # layout: the one the buffer was FILLED with (kept in the plan: a switch flipped between a chain's launch and the
-        # forward that consumes it must not move the pieces)
-        total, levels, fp_layout, extra_layout = layout if layout is not None else self._group_layout(B, n_points)
-        out = []
-        r4 = lambda n: (n + 3) // 4 * 4
-        for name, M, S, n_src, o_xyz, o_idx, o_plan, o_csr, o_inds in levels:
-            P = B * M * S
-            cen = flat[o_xyz:o_xyz + B * M * 3].view(torch.float32).view(B, M, 3)
-            idx = flat[o_idx:o_idx + P].view(B, M, S)
-            st = None if o_plan is None else flat[o_plan:o_plan + sum(sa_fused.plan_words(B, M, P))]
-            csr = None
-            if o_csr is not None:
-                o2 = o_csr + r4(B * (n_src + 1))
-                csr = (flat[o_csr:o_csr + B * (n_src + 1)].view(B, n_src + 1), flat[o2:o2 + P].view(B, M * S))
-            out.append((cen, idx, st, csr, flat[o_inds:o_inds + B * M].view(B, M)))
-        fp_views = []
-        for u, k, n, m, o_w, o_i, o_o, o_r in fp_layout:
-            fp_views.append((u, k, flat[o_w:o_w + B * n * 3].view(torch.float32).view(B, n, 3),
-                                   flat[o_i:o_i + B * n * 3].view(B, n, 3), flat[o_o:o_o + B * (m + 1)].view(B, m + 1),
-                                   flat[o_r:o_r + B * n * 3].view(B, n * 3)))
-        extra = None if extra_layout is None else \
-            (extra_layout[0], flat[extra_layout[2]:extra_layout[2] + B * extra_layout[1]].view(B, extra_layout[1]))
-        return out, fp_views, extra
+    def _ahead_buffer(self, pointcloud):
+        """-> (the persistent flat buffer of this batch shape, the layout of a chain launched now)"""
+        B, n = pointcloud.shape[0], pointcloud.shape[1]
+        key = ("group", B, n, str(pointcloud.device))
+        store = self.__dict__.setdefault("_plan_bufs", {})
+        layout = self._chain_layout(B, n)
+        if key not in store or store[key].numel() < layout.total:
+            store[key] = torch.zeros((layout.total,), device=pointcloud.device, dtype=torch.int32)
+        return store[key], layout
 
     def _launch_plan(self, pointcloud, trusted=False, small=False, group=False, resume=False):
-        """FPS chain for `pointcloud` on the side stream -> {"key", "inds": [4 x (B,npoint) int32],
-        "events": [4 x Event]}; the caller's stream has to wait on events[i] before using inds[i].
-        group: also the stages' centres / ball queries / row plans (GROUP_AHEAD) -> plan["group"] = (flat buffer, event).
+        """FPS chain for `pointcloud` on the side stream -> ChainPlan; the caller's stream has to wait on events[i] before
+        using inds[i].
+        group: also the stages' centres / ball queries / row plans (GROUP_AHEAD) -> ChainPlan.ahead.
         resume: the sa1 level continues the handed-over tail state (see prefetch_head) instead of sampling from 0."""
-        tail = None
-        if resume:
-            tail, self._tail = self._tail, None
-            if tail is not None and not (tail["trusted"] or trusted or tail["key"] == self._key(pointcloud)):
-                tail = None                    # the head of some other cloud: sample this one from 0
-            if tail is not None:
-                self.resumed_levels += 1
+        tail = self._take_tail(pointcloud, trusted) if resume else None
         main = torch.cuda.current_stream(pointcloud.device)
         side = self._side_stream(pointcloud.device)
         side.wait_stream(main)
         bufs = self._plan_buffers(pointcloud)
-        plan = {"key": self._key(pointcloud), "inds": [], "events": [], "src": pointcloud, "trusted": trusted,
-                "extra": None, "group": None}
+        key = self._key(pointcloud)
         ext = pointnet2_utils._ext
-        group = bool(group) and GROUP_AHEAD and hasattr(ext, "set_timing_sink")
-        gflat, gviews, gfp, gsrc = None, None, None, []
-        if group:
-            B0, n0 = pointcloud.shape[0], pointcloud.shape[1]
-            gkey = ("group", B0, n0, str(pointcloud.device))
-            store = self.__dict__.setdefault("_plan_bufs", {})
-            glayout = self._group_layout(B0, n0)
-            if gkey not in store or store[gkey].numel() < glayout[0]:
-                store[gkey] = torch.zeros((glayout[0],), device=pointcloud.device, dtype=torch.int32)
-            gflat = store[gkey]
-            gviews, gfp, gextra = self._group_views(gflat, B0, n0, glayout)
-            if not torch.cuda.is_current_stream_capturing():
-                gflat.record_stream(side)
+        product = hasattr(ext, "set_timing_sink")          # the product binding (writes in place), not a stand-in
+        flat, layout, views = None, None, None
+        if group and GROUP_AHEAD and product:
+            flat, layout = self._ahead_buffer(pointcloud)
+            views = chain_plan.chain_views(flat, layout, pointcloud.shape[0])
         if not torch.cuda.is_current_stream_capturing():
             # The cloud and the persistent index buffers come from the caller's stream's pool but are read / written
             # by the sampling stream: if either dies while a plan is still running (a model dropped right after a
             # prefetch -- seen in the test-suite as FPS indices landing in the next test's fresh tensor), the
             # allocator must not hand the block out before the sampling stream is done with it.
-            pointcloud.record_stream(side)
-            for buf in bufs:
-                buf.record_stream(side)
+            held = [pointcloud] + bufs + ([flat] if flat is not None else [])
             if tail is not None:
-                for t in self._split_buffers(pointcloud).values():
-                    t.record_stream(side)
+                held += list(self._split_buffers(pointcloud).values())
+            for t in held:
+                t.record_stream(side)
         with torch.cuda.stream(side), torch.no_grad():
-            xyz = pointcloud[..., 0:3].contiguous()
-            for li, name in enumerate(("sa1", "sa2", "sa3", "sa4")):
-                npoint = getattr(self, name).npoint
-                if li == 0 and tail is not None:
-                    # the level's rounds [k, npoint) from the tail state; the picks [0, k) move into the plan's buffer
-                    st, k = self._split_buffers(pointcloud), tail["rounds"]
-                    inds = bufs[0]
-                    inds[:, :k].copy_(st["tail_idx"][:, :k])
-                    ext.furthest_point_sampling_resume(xyz, inds, st["tail_temp"], k, npoint - k, small_footprint=small)
-                elif hasattr(ext, "set_timing_sink"):          # the product binding: write in place
-                    inds = ext.furthest_point_sampling(xyz, npoint, out=bufs[li], small_footprint=small)
-                else:
-                    inds = ext.furthest_point_sampling(xyz, npoint)
-                ev = torch.cuda.Event()
-                ev.record(side)
-                plan["inds"].append(inds)
-                plan["events"].append(ev)
-                if group:
-                    src = xyz.contiguous()
-                    xyz = ext.gather_xyz(src, inds, out=gviews[li][0])
-                    gsrc.append(src)
-                elif name != "sa4":
-                    if hasattr(ext, "gather_xyz"):
-                        xyz = ext.gather_xyz(xyz.contiguous(), inds)
-                    else:
-                        xyz = pointnet2_utils.gather_operation(xyz.transpose(1, 2).contiguous(), inds) \
-                            .transpose(1, 2).contiguous()
-                if self.plan_extra and name in self.plan_extra:
-                    extra = self.__dict__.setdefault("_plan_bufs", {}).setdefault(
-                        ("extra", name, pointcloud.shape[0], str(pointcloud.device)),
-                        torch.zeros((pointcloud.shape[0], self.plan_extra[name]), device=pointcloud.device,
-                                    dtype=torch.int32))
-                    if not torch.cuda.is_current_stream_capturing():
-                        extra.record_stream(side)
-                    if hasattr(ext, "set_timing_sink"):
-                        e_inds = ext.furthest_point_sampling(xyz, self.plan_extra[name], out=extra)
-                    else:
-                        e_inds = ext.furthest_point_sampling(xyz, self.plan_extra[name])
-                    e_ev = torch.cuda.Event()
-                    e_ev.record(side)
-                    plan["extra"] = (name, e_inds, e_ev)
-            if group:
+            inds, events, extra, srcs = self._sample_levels(ext, product, pointcloud, bufs, tail, small, views, side)
+            ahead = None
+            if views is not None:
                 # behind every sampling level (their events fire first): ball query and row plan per stage
-                import sa_fused
-                planned = []
-                for li, name in enumerate(("sa1", "sa2", "sa3", "sa4")):
-                    mod = getattr(self, name)
-                    cen, idx, st, csr, ginds = gviews[li]
-                    ginds.copy_(plan["inds"][li])
-                    with sa_fused._tagged("@sa", name):
-                        ext.ball_query(cen, gsrc[li], mod.radius, mod.nsample, out=idx)
-                        rp = sa_fused.make_row_plan(idx, idx.numel(), into=st) if st is not None else None
-                        if csr is not None:
-                            # in the row space the stage will run in: compact under a plan (a planned stage = training)
-                            sa_fused.build_csr_ahead(idx, gsrc[li].shape[1], rp if mod.training else None, csr[0], csr[1])
-                    planned.append(rp is not None and mod.training)
-                for u, k, w, i3, offs, order in gfp:
-                    ext.three_nn_weights(gviews[u][0], gviews[k][0], out=(w, i3))
-                    sa_fused.build_csr_ahead(i3, gviews[k][0].shape[1], None, offs, order)
-                if gextra is not None and plan["extra"] is not None and plan["extra"][0] == gextra[0]:
-                    gextra[1].copy_(plan["extra"][1])
-                g_ev = torch.cuda.Event()
-                g_ev.record(side)
-                plan["group"] = (gflat, g_ev, planned, glayout, sa_fused.PLAN_GROUP)
-        return plan
+                ahead = self._group_levels(ext, flat, layout, views, inds, srcs, extra, side)
+        return ChainPlan(key, pointcloud, trusted, inds, events, extra, ahead)
+
+    def _sample_levels(self, ext, product, pointcloud, bufs, tail, small, views, side):
+        """The four sampling levels (and the extra one) on the current = side stream, an event behind each.  views: of the
+        chain's flat buffer; the levels' centres go there and the coordinates each level sampled from are kept for the
+        grouping.  -> (inds per level, events per level, ExtraLevel | None, source coordinates per level)"""
+        inds_all, events, srcs, extra = [], [], [], None
+        xyz = pointcloud[..., 0:3].contiguous()
+        for li, name in enumerate(_SA_NAMES):
+            npoint = getattr(self, name).npoint
+            if li == 0 and tail is not None:
+                # the level's rounds [k, npoint) from the tail state; the picks [0, k) move into the plan's buffer
+                st, k = self._split_buffers(pointcloud), tail.rounds
+                inds = bufs[0]
+                inds[:, :k].copy_(st["tail_idx"][:, :k])
+                ext.furthest_point_sampling_resume(xyz, inds, st["tail_temp"], k, npoint - k, small_footprint=small)
+            elif product:
+                inds = ext.furthest_point_sampling(xyz, npoint, out=bufs[li], small_footprint=small)
+            else:
+                inds = ext.furthest_point_sampling(xyz, npoint)
+            ev = torch.cuda.Event()
+            ev.record(side)
+            inds_all.append(inds)
+            events.append(ev)
+            if views is not None:
+                src = xyz.contiguous()
+                xyz = ext.gather_xyz(src, inds, out=views.stages[li].centres)
+                srcs.append(src)
+            elif name != "sa4":
+                if hasattr(ext, "gather_xyz"):
+                    xyz = ext.gather_xyz(xyz.contiguous(), inds)
+                else:
+                    xyz = pointnet2_utils.gather_operation(xyz.transpose(1, 2).contiguous(), inds) \
+                        .transpose(1, 2).contiguous()
+            if self.plan_extra and name in self.plan_extra:
+                n_extra = self.plan_extra[name]
+                buf = self.__dict__.setdefault("_plan_bufs", {}).setdefault(
+                    ("extra", name, pointcloud.shape[0], str(pointcloud.device)),
+                    torch.zeros((pointcloud.shape[0], n_extra), device=pointcloud.device, dtype=torch.int32))
+                if not torch.cuda.is_current_stream_capturing():
+                    buf.record_stream(side)
+                e_inds = ext.furthest_point_sampling(xyz, n_extra, out=buf) if product else \
+                    ext.furthest_point_sampling(xyz, n_extra)
+                e_ev = torch.cuda.Event()
+                e_ev.record(side)
+                extra = ExtraLevel(name, e_inds, e_ev)
+        return inds_all, events, extra, srcs
+
+    def _group_levels(self, ext, flat, layout, views, inds, srcs, extra, side):
+        """Behind the sampling levels, on the current = side stream: every stage's ball query, row plan and backward CSR,
+        the FP modules' 3-NN weights and CSR, and the sampled indices themselves, all into the views of `flat` -> Ahead"""
+        import sa_fused
+        planned = []
+        for name, st, src, picked in zip(_SA_NAMES, views.stages, srcs, inds):
+            mod = getattr(self, name)
+            st.inds.copy_(picked)
+            with sa_fused._tagged("@sa", name):
+                ext.ball_query(st.centres, src, mod.radius, mod.nsample, out=st.idx)
+                rp = sa_fused.make_row_plan(st.idx, st.idx.numel(), into=st.plan_state) if st.plan_state is not None else None
+                if st.csr is not None:
+                    # in the row space the stage will run in: compact under a plan (a planned stage = training)
+                    sa_fused.build_csr_ahead(st.idx, src.shape[1], rp if mod.training else None, st.csr.offsets, st.csr.order)
+            planned.append(rp is not None and mod.training)
+        for fp in views.fps:
+            ext.three_nn_weights(fp.unknown, fp.known, out=(fp.weight, fp.idx))
+            sa_fused.build_csr_ahead(fp.idx, fp.known.shape[1], None, fp.csr.offsets, fp.csr.order)
+        if views.extra is not None and extra is not None and extra.name == layout.extra.name:
+            views.extra.copy_(extra.inds)
+        event = torch.cuda.Event()
+        event.record(side)
+        return Ahead(flat, event, layout, tuple(planned))
 
     def prefetch(self, pointcloud, trusted=False, at_next_forward=False, footprint=None, resume=False):
         """Start the sampling plan of a FUTURE batch now (e.g. while the current batch is in backward).
@@ -397,7 +360,7 @@ class Pointnet2Backbone(nn.Module):
         if resume and self._tail is None and self._head is not None:
             self.hand_over_head()
         if at_next_forward:
-            self._pending = (pointcloud, trusted, small, True, resume)
+            self._pending = Pending(pointcloud, trusted, small, True, resume)
         else:
             self._plan = self._launch_plan(pointcloud, trusted, small, True, resume)
 
@@ -422,21 +385,73 @@ class Pointnet2Backbone(nn.Module):
     def take_extra(self, name):
         """Indices of the plan's extra level `name` for the batch just run through forward(), or None."""
         extra, self._extra = self._extra, None
-        if extra is None or extra[0] != name:
+        if extra is None or extra.name != name:
             return None
-        if extra[2] is None:
-            return extra[1]                 # forward() copied it out of the plan's buffer already
-        torch.cuda.current_stream(extra[1].device).wait_event(extra[2])
-        return extra[1].clone()             # the plan's buffer is reused by the next plan
+        if extra.event is None:
+            return extra.inds               # forward() copied it out of the plan's buffer already
+        torch.cuda.current_stream(extra.inds.device).wait_event(extra.event)
+        return extra.inds.clone()           # the plan's buffer is reused by the next plan
 
     def _take_plan(self, pointcloud):
         if not pointcloud.is_cuda or os.environ.get("OMNIPQ_SAMPLING_PLAN", "1") == "0":
             return None
         plan = self._plan
         self._plan = None
-        if plan is None or not (plan["trusted"] or plan["key"] == self._key(pointcloud)):
+        if plan is None or not (plan.trusted or plan.key == self._key(pointcloud)):
             plan = self._launch_plan(pointcloud)
         return plan
+
+    def _take_ahead(self, plan, pointcloud):
+        """What the chain made ahead of the stages (GROUP_AHEAD): one copy of its flat buffer, read with the layout it was
+        filled with.  -> (indices per stage, StageAhead per stage, the plan without what travelled in that copy)"""
+        import sa_fused
+        flat, event, layout, planned = plan.ahead
+        torch.cuda.current_stream(pointcloud.device).wait_event(event)
+        views = chain_plan.chain_views(flat.clone(), layout, pointcloud.shape[0], planned)
+        stages = list(views.stages)
+        if layout.plan_group != sa_fused.PLAN_GROUP:       # plans (and the CSRs in their row space) of another group size: not these
+            stages = [s._replace(plan_state=None, csr=None, planned=False) for s in stages]
+        if views.extra is not None and plan.extra is not None and plan.extra.name == layout.extra.name:
+            self._extra = ExtraLevel(layout.extra.name, views.extra, None)
+            plan = plan._replace(extra=None)
+        # A record rides on one of its own tensors (the FP modules find theirs on the unknown centres, the stages on the
+        # indices): it goes without that field, or tensor and record would keep each other -- and the whole copy -- alive
+        # until a garbage collection.
+        for fp in views.fps:
+            fp.unknown.omnipq_fp_ahead = fp._replace(unknown=None)
+        # the indices travel in the same copy: nothing else of this plan is read
+        return [s.inds for s in stages], [s._replace(inds=None) for s in stages], plan._replace(inds=None)
+
+    def _taken(self, pointcloud):
+        """The sampling plan of this batch, taken in forward()'s order: yields (indices | None, StageAhead | None) per stage.
+        Before the first stage: the chain's flat buffer in one copy (_take_ahead); with a chain pending, everything else the
+        plan still holds is copied and the pending chain launched (it reuses the plan's buffers).  Otherwise the indices of
+        a stage are waited for and copied when that stage is asked for, so a later level keeps sampling under the stages in
+        front of it.  The extra level lands in self._extra (take_extra)."""
+        plan = self._take_plan(pointcloud)
+        self._extra = plan.extra if plan is not None else None
+        inds, aheads = [None] * 4, [None] * 4
+        if plan is not None and plan.ahead is not None:
+            inds, aheads, plan = self._take_ahead(plan, pointcloud)
+        pending, self._pending = self._pending, None
+        if pending is not None:
+            if plan is not None:
+                # the next plan starts below and reuses this plan's buffers: copy everything it holds NOW
+                cur = torch.cuda.current_stream(pointcloud.device)
+                if plan.inds is not None:                  # (else they came with the chain's flat buffer)
+                    for li in range(4):
+                        cur.wait_event(plan.events[li])
+                        inds[li] = plan.inds[li].clone()
+                if plan.extra is not None:
+                    cur.wait_event(plan.extra.event)
+                    self._extra = ExtraLevel(plan.extra.name, plan.extra.inds.clone(), None)
+                plan = None
+            self._plan = self._launch_plan(*pending)
+        for li in range(4):
+            if plan is not None and plan.inds is not None:
+                torch.cuda.current_stream(pointcloud.device).wait_event(plan.events[li])
+                inds[li] = plan.inds[li].clone()           # the plan's buffers are reused by the next plan
+            yield inds[li], aheads[li]
 
     def _break_up_pc(self, pc):
         xyz = pc[..., 0:3].contiguous()
@@ -447,54 +462,9 @@ class Pointnet2Backbone(nn.Module):
         if not end_points:
             end_points = {}
         xyz, features = self._break_up_pc(pointcloud)
-        plan = self._take_plan(pointcloud)
-
-        self._extra = None
-        if plan is not None and plan["extra"] is not None:
-            self._extra = plan["extra"]
-        taken = [None] * 4
-        groups = [None] * 4
-        if plan is not None and plan.get("group") is not None:
-            # made ahead of the stages (GROUP_AHEAD): one copy of the chain's flat buffer, views per stage
-            gflat, g_ev, planned, glayout, gs_then = plan["group"]
-            torch.cuda.current_stream(pointcloud.device).wait_event(g_ev)
-            gv, gfp, gex = self._group_views(gflat.clone(), pointcloud.shape[0], pointcloud.shape[1], glayout)
-            import sa_fused
-            if gs_then != sa_fused.PLAN_GROUP:        # plans (and the CSRs in their row space) of another group size: not these
-                groups = [(g[0], g[1], None, None, False) for g in gv]
-            else:
-                groups = [g[:4] + (pl,) for g, pl in zip(gv, planned)]
-            # the indices travel in the same copy: nothing else of this plan is read below
-            taken = [g[4] for g in gv]
-            if gex is not None and plan["extra"] is not None and plan["extra"][0] == gex[0]:
-                self._extra = (gex[0], gex[1], None)
-                plan = dict(plan, extra=None)
-            plan = dict(plan, inds=None)
-            for u, k, w, i3, offs, order in gfp:                         # the FP modules find theirs on the unknown centres
-                groups[u][0].omnipq_nn = (groups[k][0], w, i3, (offs, order))
-        pending, self._pending = getattr(self, "_pending", None), None
-        if pending is not None:
-            if plan is not None:
-                # the next plan starts below and reuses this plan's buffers: copy everything it holds NOW
-                cur = torch.cuda.current_stream(pointcloud.device)
-                for li in range(4):
-                    if plan["inds"] is None:
-                        break                          # (they came with the group's copy)
-                    cur.wait_event(plan["events"][li])
-                    taken[li] = plan["inds"][li].clone()
-                if plan["extra"] is not None:
-                    name, e_inds, e_ev = plan["extra"]
-                    cur.wait_event(e_ev)
-                    self._extra = (name, e_inds.clone(), None)
-                plan = None
-            self._plan = self._launch_plan(*pending)
-        for li, name in enumerate(("sa1", "sa2", "sa3", "sa4")):
-            inds = taken[li]
-            if plan is not None and plan["inds"] is not None:
-                torch.cuda.current_stream(pointcloud.device).wait_event(plan["events"][li])
-                inds = plan["inds"][li].clone()        # the plan's buffers are reused by the next plan
-            if groups[li] is not None and inds is not None:
-                inds.omnipq_group = groups[li]
+        for name, (inds, ahead) in zip(_SA_NAMES, self._taken(pointcloud)):
+            if ahead is not None and inds is not None:
+                inds.omnipq_stage_ahead = ahead
             xyz, features, inds = getattr(self, name)(xyz, features, inds)
             if name in ("sa1", "sa2"):          # the reference records inds for these two only
                 end_points[name + "_inds"] = inds

@@ -163,16 +163,17 @@ class PointnetSAModuleVotes(nn.Module):
     def forward(self, xyz: torch.Tensor, features: torch.Tensor = None, inds: torch.Tensor = None):
         if inds is not None:
             assert inds.shape[1] == self.npoint
-        # made ahead of the stage by the backbone's sampling chain: (centres, ball-query indices, row-plan state | None)
-        group = getattr(inds, "omnipq_group", None) if inds is not None else None
-        if group is not None and group[0] is not None and not (torch.is_grad_enabled() and xyz.requires_grad):
-            new_xyz = group[0]
+        # made ahead of the stage by the backbone's sampling chain: a chain_plan.StageAhead (the signature is the reference's,
+        # so it rides on the index tensor)
+        group = getattr(inds, "omnipq_stage_ahead", None) if inds is not None else None
+        if group is not None and not (torch.is_grad_enabled() and xyz.requires_grad):
+            new_xyz = group.centres
         else:
             group = None
             new_xyz, inds = _centres(xyz, self.npoint, inds)
         if self._fused(xyz, features):
             import sa_fused
-            return new_xyz, sa_fused.run(self, xyz, new_xyz, features, group=None if group is None else group[1:]), inds
+            return new_xyz, sa_fused.run(self, xyz, new_xyz, features, group=group), inds
         grouped = self.grouper(xyz, new_xyz, features)
         unique_cnt = grouped[2] if self.ret_unique_cnt else None
         grouped_features, grouped_xyz = grouped[0], grouped[1]
@@ -297,16 +298,16 @@ def _fp_forward_rows(self, unknown, known, unknow_feats, known_feats):
             return None
     if known_pm is None or C2 % 8:
         return None
-    pre = getattr(unknown, "omnipq_nn", None)        # made ahead by the backbone's sampling chain: (known, weight, idx, csr)
-    if pre is not None and pre[0] is known and not (unknown.requires_grad or known.requires_grad):
-        weight, idx = pre[1], pre[2]
-        idx.omnipq_csr3 = pre[3]
+    pre = getattr(unknown, "omnipq_fp_ahead", None)  # made ahead by the backbone's sampling chain: a chain_plan.FPAhead
+    csr = None
+    if pre is not None and pre.known is known and not (unknown.requires_grad or known.requires_grad):
+        weight, idx, csr = pre.weight, pre.idx, pre.csr
     elif unknown.dtype == torch.float32 and known.dtype == torch.float32 and not (unknown.requires_grad or known.requires_grad):
         weight, idx = pointnet2_utils._ext.three_nn_weights(unknown.contiguous(), known.contiguous())   # one launch
     else:
         dist, idx = pointnet2_utils.three_nn(unknown, known)
         weight = inverse_distance_weights(dist).contiguous()
-    rows_in = sa_fused.FPGatherRows.apply(known_feats, known_pm, unknow_feats, skip_pm, idx, weight)
+    rows_in = sa_fused.FPGatherRows.apply(known_feats, known_pm, unknow_feats, skip_pm, idx, weight, csr)
     y = _rows_mlp(self.mlp, rows_in)
     if y is None:
         return None

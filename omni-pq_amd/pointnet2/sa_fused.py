@@ -371,15 +371,15 @@ def build_csr_ahead(idx, N, plan, offsets, order):
         _call(_lib.omnipq_sa_build_csr, idx, B, N, M, S, _p(idx), _p(offsets), _p(order), _p(scratch))
 
 
-def _csr_of(idx, B, N, M, S, plan, anchor):
-    """(offsets, order) of the stage's backward: the ones made ahead of the stage (run(group=)) if they were made in the row
-    space this backward runs in -- the SAME plan state (its goff words and group size), or no plan on both sides (ADVICE r5:
-    a flag alone let a CSR of another row space through when a switch changed between prefetch and forward) -- else built
-    now (inside the caller's _row_plan block)."""
-    pre = getattr(idx, "omnipq_csr", None)
-    key = None if plan is None else (plan.goff.data_ptr(), plan.gs)
-    if pre is not None and pre[2] == key and tuple(pre[0].shape) == (B, N + 1) and tuple(pre[1].shape) == (B, M * S):
-        return pre[0], pre[1]
+def _csr_of(pre, idx, B, N, M, S, plan, anchor):
+    """(offsets, order) of the stage's backward: `pre`, the chain_plan.Csr made ahead of the stage (run(group=)), if it was
+    made in the row space this backward runs in -- the SAME plan state (its goff words and group size), or no plan on both
+    sides (a flag alone let a CSR of another row space through when a switch changed between prefetch and
+    forward) -- else built now (inside the caller's _row_plan block)."""
+    space = None if plan is None else (plan.goff.data_ptr(), plan.gs)
+    if pre is not None and pre.space == space and tuple(pre.offsets.shape) == (B, N + 1) and \
+            tuple(pre.order.shape) == (B, M * S):
+        return pre.offsets, pre.order
     dev = idx.device
     offsets = torch.empty((B, N + 1), device=dev, dtype=torch.int32)
     order = torch.empty((B, M * S), device=dev, dtype=torch.int32)
@@ -1336,7 +1336,7 @@ def _last_bwd_no_dy(ctx, g_out, grads, dfr):
           _p(ab[1]), _p(gb3))
     # the data gradient + the BatchNorm-backward sums of the layer below; X2 = relu(bn2(Y2)) as its first phase forms
     # it is kept for the weight gradient (LAST_X2: the TN launch is bound by rebuilding X2 in every fragment)
-    want_w = ctx.needs_input_grad[9 + 3 * (L - 1)]
+    want_w = ctx.needs_input_grad[_PARAMS_AT + 3 * (L - 1)]
     X2 = torch.empty((P, C2), device=dev, dtype=E16.dtype) if (want_w and ctx.route.keep_x2) else None
     pend = zeros_f64(3, below.C, dev)
     dX2 = torch.empty((P, C2), device=dev, dtype=E16.dtype)
@@ -1365,7 +1365,7 @@ def _layer_wgrad(ctx, l, dY, grads, dfr):
     below = ctx.layers[l - 1] if (l > 0 and ctx.route.feed[l - 1] == "yab") else None
     Xin = below.Y if below is not None else (ctx.layers[l - 1].X if l > 0 else ctx.X0)
     wt = ctx.wtargets[l] if (dfr is not None and SA_WGRADS_GROUPED) else None
-    if wt is not None and ctx.needs_input_grad[9 + 3 * l]:
+    if wt is not None and ctx.needs_input_grad[_PARAMS_AT + 3 * l]:
         if l == 0:
             dfr.add_sa(dY, Xin, lay.C, lay.K, g.P, wt, Crop(lay.C, g.cin_raw + 3, rot=3 | (g.cin << 8)), blk=ctx.plan)
         else:
@@ -1404,7 +1404,7 @@ def _tail_grouped(ctx, dY, grads, dfr):
         d_cen = torch.empty((B, M, 3), device=dev)
     # bucket the positions by source point, then every (point, 8-channel piece) sums its
     # own bucket: no atomics, each dX row is read exactly once
-    offsets, order = _csr_of(ctx.idx, B, N, M, S, ctx.plan, dX)
+    offsets, order = _csr_of(ctx.csr_ahead, ctx.idx, B, N, M, S, ctx.plan, dX)
     _call(_lib.omnipq_sa_scatter_csr, dX, B, N, M, S, cin, kpad, inv_r, _p(offsets), _p(order), _p(dX), _p(dfeat_pm), _p(d_xyz),
           _p(d_cen))
     if dfeat_pm is not None:
@@ -1446,11 +1446,11 @@ def _tail_on_source(ctx, dY, grads, dfr):
     C1 = lay.C
     want_xyz = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
     want_feat = ctx.has_features and ctx.needs_input_grad[2]
-    want_w = ctx.needs_input_grad[9]
+    want_w = ctx.needs_input_grad[_PARAMS_AT]
     d_xyz = d_cen = d_feat = None
     if not (want_xyz or want_feat or want_w):
         return d_xyz, d_cen, d_feat
-    offsets, order = _csr_of(ctx.idx, B, N, M, S, plan, dY)
+    offsets, order = _csr_of(ctx.csr_ahead, ctx.idx, B, N, M, S, plan, dY)
     dXr = None
     if want_xyz:
         # gradient of the relative coordinates: dY W_x (the rows cin .. cin + 7 of the transposed prepared weight: W_x^T | 0)
@@ -1482,24 +1482,28 @@ def _tail_on_source(ctx, dY, grads, dfr):
     return d_xyz, d_cen, d_feat
 
 
+_PARAMS_AT = 11         # FusedSAStage.apply: its arguments in front of *params
+
+
 class FusedSAStage(torch.autograd.Function):
-    """forward(xyz, new_xyz, features|None, idx, radius, normalize_xyz, training, bn_cfg, *params)
+    """forward(xyz, new_xyz, features|None, feat_pm|None, idx, radius, normalize_xyz, training, bn_cfg, plan, csr, *params)
 
     params = (W_0, gamma_0, beta_0, W_1, ...); bn_cfg = list of (running_mean, running_var,
-    num_batches_tracked, momentum, eps) per layer.  Returns (B, C_last, M) f32.
+    num_batches_tracked, momentum, eps) per layer; plan, csr: the stage's _Plan and the chain_plan.Csr of its backward where
+    they were made ahead of the stage (run(group=)), else None.  Returns (B, C_last, M) f32.
     """
 
     @staticmethod
-    def forward(ctx, xyz, new_xyz, features, feat_pm, idx, radius, normalize_xyz, training, bn_cfg, *params):
+    def forward(ctx, xyz, new_xyz, features, feat_pm, idx, radius, normalize_xyz, training, bn_cfg, plan, csr, *params):
         ctx.e16 = E16.dtype
-        ctx.n_inputs = 9 + len(params)
+        ctx.n_inputs = _PARAMS_AT + len(params)
         ctx.stage_label = _STAGE_LABEL
         with _tagged("@sa", ctx.stage_label):
             return FusedSAStage._forward(ctx, xyz, new_xyz, features, feat_pm, idx, radius, normalize_xyz, training,
-                                         bn_cfg, *params)
+                                         bn_cfg, plan, csr, *params)
 
     @staticmethod
-    def _forward(ctx, xyz, new_xyz, features, feat_pm, idx, radius, normalize_xyz, training, bn_cfg, *params):
+    def _forward(ctx, xyz, new_xyz, features, feat_pm, idx, radius, normalize_xyz, training, bn_cfg, plan, csr, *params):
         dev = xyz.device
         B, N, _ = xyz.shape
         M, S = idx.shape[1], idx.shape[2]
@@ -1508,7 +1512,6 @@ class FusedSAStage(torch.autograd.Function):
         cin = _round_up(cin_raw, 8)
         g = _Geom(B, N, M, S, B * M * S, cin, cin_raw, _round_up(cin + 3, 32), (1.0 / radius) if normalize_xyz else 1.0,
                   _world() if (training and _SYNC) else 1)
-        plan = getattr(idx, "omnipq_plan", None)           # made ahead of the stage (run(group=)), or below
         route = stage_route(training, B, N, M, S, cin_raw, [params[3 * l].shape[0] for l in range(L)], features is not None,
                             ctx.needs_input_grad[0] or ctx.needs_input_grad[1],
                             features is not None and ctx.needs_input_grad[2], None if plan is None else plan.gs,
@@ -1534,7 +1537,7 @@ class FusedSAStage(torch.autograd.Function):
         ctx.hoist = (feat_pm.reshape(B * N, cin), Xrel) if route.first == "source" else None
         # where a layer's weight gradient may be written behind autograd's back (deferred_wgrads): Parameters only
         ctx.wtargets = [grad_target(params[3 * l]) for l in range(L)] if training else None
-        ctx.idx = idx
+        ctx.idx, ctx.csr_ahead = idx, csr
         ctx.out_pm, ctx.arg, ctx.ysel = out_pm, arg, ysel
         ctx.has_features = features is not None
         ctx.feat_dtype = features.dtype if features is not None else None
@@ -1580,7 +1583,7 @@ class FusedSAStage(torch.autograd.Function):
                 break
             dY, pend = _layer_bwd(ctx, l, dY, grads, dfr)
         ctx.layers = None
-        return (d_xyz, d_cen, d_feat, None, None, None, None, None, None, *grads)
+        return (d_xyz, d_cen, d_feat) + (None,) * (_PARAMS_AT - 3) + tuple(grads)
 
 
 def _bn_of(layer):
@@ -1637,22 +1640,18 @@ def eligible(module, xyz, features):
 
 
 def run(module, xyz, new_xyz, features, group=None):
-    """ball query + fused stage -> (B, C_out, npoint) f32.  group = (idx (B, M, S) int32, plan state | None): the ball query
-    (and row plan) of this stage made ahead of it (they depend on coordinates only: Pointnet2Backbone's sampling chain)."""
+    """ball query + fused stage -> (B, C_out, npoint) f32.  group: a chain_plan.StageAhead -- the ball query (and row plan,
+    and backward CSR with the row space it was built in) of this stage made ahead of it (they depend on coordinates only:
+    Pointnet2Backbone's sampling chain)."""
     global _STAGE_LABEL
     _STAGE_LABEL = getattr(module, "omnipq_stage", None) or f"m{module.npoint}s{module.nsample}"
-    idx = None
-    if group is not None and group[0] is not None and \
-            tuple(group[0].shape) == (xyz.shape[0], new_xyz.shape[1], module.nsample) and group[0].dtype == torch.int32:
-        idx = group[0]
-        if group[1] is not None:
+    idx = plan = csr = None
+    if group is not None and group.idx is not None and \
+            tuple(group.idx.shape) == (xyz.shape[0], new_xyz.shape[1], module.nsample) and group.idx.dtype == torch.int32:
+        idx, csr = group.idx, group.csr
+        if group.plan_state is not None:
             B_, M_, S_ = idx.shape
-            idx.omnipq_plan = plan_from_state(group[1], B_, M_, B_ * M_ * S_)
-        if len(group) > 3 and group[2] is not None:
-            # the row space the CSR was built in: the plan state it travelled with (group[3]: built under that plan), or none
-            built_under = (group[1].data_ptr(), PLAN_GROUP) if (group[3] and group[1] is not None) else None
-            if bool(group[3]) == (built_under is not None):
-                idx.omnipq_csr = (group[2][0], group[2][1], built_under)
+            plan = plan_from_state(group.plan_state, B_, M_, B_ * M_ * S_)
     if idx is None:
         with _tagged("@sa", _STAGE_LABEL):
             idx = pointnet2_utils.ball_query(module.radius, module.nsample, xyz, new_xyz)
@@ -1665,7 +1664,7 @@ def run(module, xyz, new_xyz, features, group=None):
     _SYNC = all(bool(bn_syncs(_bn_of(layer)[1])) for layer in module.mlp_module)
     feat_pm = None if features is None else rows16_of(features, (features.shape[0], features.shape[2], features.shape[1]))
     out, twin = FusedSAStage.apply(xyz, new_xyz, features, feat_pm, idx, float(module.radius),
-                                   bool(module.normalize_xyz), bool(module.training), bn_cfg, *params)
+                                   bool(module.normalize_xyz), bool(module.training), bn_cfg, plan, csr, *params)
     out.omnipq_rows16 = twin        # consumers that work on bf16 rows (next SA stage, FP modules) skip their cast
     return out
 
@@ -1678,7 +1677,8 @@ class FPGatherRows(torch.autograd.Function):
     their bf16 twins.  Gradients come back in the (B, C, .) layout as views of position-major data."""
 
     @staticmethod
-    def forward(ctx, known_feats, known_pm, skip_feats, skip_pm, idx, weight):
+    def forward(ctx, known_feats, known_pm, skip_feats, skip_pm, idx, weight, csr):
+        """csr: the chain_plan.Csr of the backward made ahead of the module (offsets (B, m+1), order (B, 3n)), or None"""
         ctx.e16 = E16.dtype
         B, n = idx.shape[0], idx.shape[1]
         m, C2 = known_pm.shape[1], known_pm.shape[2]
@@ -1688,7 +1688,7 @@ class FPGatherRows(torch.autograd.Function):
         if C1:
             _call(_lib.omnipq_place_rows, rows, B * n, C1, _p(skip_pm), _p(rows), C2 + C1, C2)
         ctx.save_for_backward(idx, weight)
-        ctx.pre_csr = getattr(idx, "omnipq_csr3", None)     # (offsets (B, m+1), order (B, 3n)) made ahead of the module, or None
+        ctx.pre_csr = csr
         ctx.geom = (B, n, m, C2, C1, known_feats.dtype, None if skip_feats is None else skip_feats.dtype)
         return rows
 
@@ -1703,8 +1703,8 @@ class FPGatherRows(torch.autograd.Function):
             # bucket the (unknown point, slot) pairs by the known point they read, then sum bucket-wise: no atomics
             dk = torch.empty((B, m, C2), device=g.device, dtype=torch.float32)
             pre = ctx.pre_csr
-            if pre is not None and tuple(pre[0].shape) == (B, m + 1) and tuple(pre[1].shape) == (B, 3 * n):
-                offsets, order = pre
+            if pre is not None and tuple(pre.offsets.shape) == (B, m + 1) and tuple(pre.order.shape) == (B, 3 * n):
+                offsets, order = pre.offsets, pre.order
             else:
                 offsets = torch.empty((B, m + 1), device=g.device, dtype=torch.int32)
                 order = torch.empty((B, 3 * n), device=g.device, dtype=torch.int32)
@@ -1715,4 +1715,4 @@ class FPGatherRows(torch.autograd.Function):
             d_known = dk.to(kdt).transpose(1, 2)
         if C1 and ctx.needs_input_grad[2]:
             d_skip = g.view(B, n, C2 + C1)[:, :, C2:].to(sdt).transpose(1, 2)
-        return d_known, None, d_skip, None, None, None
+        return d_known, None, d_skip, None, None, None, None

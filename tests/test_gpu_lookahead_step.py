@@ -39,7 +39,7 @@ def test_head_then_resumed_chain_gives_the_plain_forwards_indices(k):
         want = net({"point_clouds": pc})
         before = net.backbone.resumed_levels
         net.prefetch_head({"point_clouds": pc}, k)
-        assert net.backbone._head is not None and net.backbone._head["rounds"] == k
+        assert net.backbone._head is not None and net.backbone._head.rounds == k
         net.prefetch({"point_clouds": pc}, resume=True)
         assert net.backbone.resumed_levels == before + 1          # the chain did continue the head
         assert net.backbone._head is None and net.backbone._tail is None and net.backbone._plan is not None

@@ -553,6 +553,92 @@ def test_grouping_ahead_of_the_stages_is_taken_and_changes_nothing(monkeypatch):
 
 
 @pytest.mark.gpu
+def test_grouping_ahead_at_a_small_batch_where_only_sa1_is_planned(monkeypatch):
+    """Companion of the test above at 2 x 8192 points (sa1 is planned, sa2..sa4 are not: their CSRs are made in the full row
+    space): the same launch counts and bit equality, and what the chain made reaches the stages in typed records -- none of
+    the tuple attributes the hand-off once used hangs on a tensor reachable from end_points, and no record keeps the tensor
+    it rides on alive."""
+    import gc
+    import weakref
+    import bench
+    import backbone_module
+    import pointnet2_utils
+    import sa_fused
+    torch.manual_seed(2)
+    net = bench.build_model(0).to(dev()).train()
+    pc = synth.make_clouds(79, 2, 8192, kind="room").to(dev())
+    keys = ("sa1_inds", "sa2_inds", "sa1_xyz", "sa2_xyz", "sa3_xyz", "sa4_xyz", "sa1_features", "sa2_features", "sa3_features",
+            "sa4_features", "fp2_features")
+    removed = ("omnipq_group", "omnipq_plan", "omnipq_csr", "omnipq_nn", "omnipq_csr3")
+    real = {"bq": pointnet2_utils._ext.ball_query, "plan": sa_fused.make_row_plan, "csr": sa_fused._call}
+    calls = dict.fromkeys(real, 0)
+
+    def counted(what):
+        def spy(*a, **kw):
+            if what != "csr" or a[0].__name__ == "omnipq_sa_build_csr":
+                calls[what] += 1
+            return real[what](*a, **kw)
+        return spy
+
+    def carried(obj, seen):
+        """names of the attributes on every tensor reachable from obj through containers, records and tensor attributes"""
+        if id(obj) in seen:
+            return set()
+        seen.add(id(obj))
+        if isinstance(obj, torch.Tensor):
+            names = set(vars(obj))
+            return names.union(*(carried(v, seen) for v in list(vars(obj).values()) + [obj._base]))
+        if isinstance(obj, dict):
+            obj = list(obj.values())
+        if isinstance(obj, (list, tuple)):
+            return set().union(*(carried(v, seen) for v in obj))
+        return set()
+
+    def run(group):
+        monkeypatch.setattr(backbone_module, "GROUP_AHEAD", group)
+        for p in net.parameters():
+            p.grad = None
+        net.prefetch({"point_clouds": pc})
+        torch.cuda.synchronize()
+        calls.update(dict.fromkeys(calls, 0))
+        monkeypatch.setattr(pointnet2_utils._ext, "ball_query", counted("bq"))
+        monkeypatch.setattr(sa_fused, "make_row_plan", counted("plan"))
+        monkeypatch.setattr(sa_fused, "_call", counted("csr"))
+        try:
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                ep = net.backbone(pc, {})
+            (ep["fp2_features"].float().sum() + ep["sa4_features"].float().sum()).backward()
+        finally:
+            monkeypatch.setattr(pointnet2_utils._ext, "ball_query", real["bq"])
+            monkeypatch.setattr(sa_fused, "make_row_plan", real["plan"])
+            monkeypatch.setattr(sa_fused, "_call", real["csr"])
+        torch.cuda.synchronize()
+        grads = {n: p.grad.clone() for n, p in net.backbone.named_parameters() if p.grad is not None}
+        alive = [weakref.ref(ep[k]) for k in ("sa1_inds", "sa2_xyz", "sa3_xyz", "sa4_xyz")]
+        return {k: ep[k].detach().clone() for k in keys}, grads, dict(calls), carried(ep, set()), alive
+
+    gc.collect()
+    gc.disable()
+    try:
+        want, gwant, c0, names0, _ = run(False)
+        got, ggot, c1, names1, alive = run(True)
+        # a record rides on a tensor it describes: it must not hold that tensor, or the step's copy of the chain's buffer
+        # (10 MB at the benchmark's shape) lives until a garbage collection instead of until its last user
+        assert [r() is None for r in alive] == [True] * 4
+    finally:
+        gc.enable()
+    assert c0["bq"] == 4 and c0["plan"] >= 1 and c0["csr"] >= 5          # in line: every stage makes its own
+    assert c1 == {"bq": 0, "plan": 0, "csr": 0}, c1                        # ahead: nothing left on the path
+    for k in keys:
+        assert torch.equal(got[k], want[k]), k
+    assert sorted(ggot) == sorted(gwant) and len(ggot) >= 30
+    for n in gwant:
+        assert torch.equal(ggot[n], gwant[n]), n
+    assert "omnipq_stage_ahead" in names1 and "omnipq_stage_ahead" not in names0      # the walk does reach the hand-off
+    assert not (names0 | names1) & set(removed), (names0 | names1) & set(removed)
+
+
+@pytest.mark.gpu
 def test_a_csr_made_ahead_in_another_row_space_is_not_reused(monkeypatch):
     """the backward CSR of a stage is made ahead of it in the row space of the plan the chain built.  If what
     decides the row space changes between prefetch and forward (here: ROW_PLAN switched off after the chain ran), the stage

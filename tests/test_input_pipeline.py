@@ -71,7 +71,7 @@ def test_pipeline_delivers_the_batches_and_their_sampling_plans():
     got = []
     for i in range(4):
         pc = pipe.pop()
-        assert backbone._plan is not None and backbone._plan["src"] is pc        # the plan of THIS batch is waiting
+        assert backbone._plan is not None and backbone._plan.src is pc        # the plan of THIS batch is waiting
         with torch.no_grad():
             out = backbone(pc)
         assert backbone._plan is None                                           # ... and forward() consumed it
