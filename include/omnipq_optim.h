@@ -64,6 +64,28 @@
  * touches neither the teacher nor ema_state.  Per element: t = ema * alpha rounded to f32, then ema = fmaf(beta, p_new, t) --
  * the arithmetic of omnipq_ema_update, so the teacher holds the same bits as after that call on the updated parameters.
  *
+ * Dynamic fp16 loss scaling (the two tensors and the recurrence of torch.amp.GradScaler: torch._amp_update_scale_) is one more
+ * scalar recurrence in the finalise launch: omnipq_adamw_scaled_finalize, the superset of the three finalise entry points above.
+ * The squared-norm and update launches are the ones above, unchanged; they see the scale only through result[3].
+ *   scaler_state  one struct omnipq_loss_scaler { scale, growth_tracker } in device memory: GradScaler's `_scale` and
+ *                 `_growth_tracker`; omnipq_loss_scaler_record() reports its layout to a binding.  The caller multiplies its loss by `scale` (a device read: nothing of it is a kernel argument), so the gradients
+ *                 arrive as S * g.  Written by thread 0 of the finalise launch only, with ordinary stores.
+ *   scaler_cfg    double[4] = { growth_factor, backoff_factor, growth_interval, 0 } in device memory: a changed interval, like a
+ *                 loaded scale, takes effect on the next replay of the same captured launch.
+ * With S = scaler_state->scale read at entry and inv = 1 / (double)S:
+ *     total_norm = (float)(sqrt(sum of partials) * inv)            the norm of the UNSCALED gradients (times grad_scale)
+ *     result[3]  = (float)(grad_scale * inv) * clip_coef           the effective factor is grad_scale / S
+ * A micro-batch that is not the applying one touches neither scale nor growth_tracker, so S is constant over an accumulation
+ * window -- which the sum of scaled gradients requires.  An applying call then runs, after everything the other finalise entry
+ * points do:
+ *     norm not finite:  scale = (float)((double)scale * backoff_factor);  growth_tracker = 0
+ *     norm finite:      growth_tracker += 1;  when it equals growth_interval: the candidate (float)((double)scale * growth_factor)
+ *                       replaces scale only if it is finite, and growth_tracker = 0 either way.
+ * The detector is the NORM, as it already is for `skipped`, not torch's per-tensor found_inf: the two differ only when finite
+ * gradients have a norm that overflows f32.  result[3] is ONE f32 for un-scaling and clipping together, where torch multiplies
+ * twice: where grad_scale * clip_coef / S falls below 2^-126 (S beyond 2^120 or so) it is a subnormal f32 and holds fewer than
+ * 24 bits unless it is a power of two.  S = 0 (after ~150 back-offs in a row) makes every later norm non-finite, as in torch.
+ *
  * `.grad` is READ-ONLY here: the clipped (and un-scaled) gradient g' = grad_scale * clip_coef * g exists in registers
  * only and is never written back.  Nothing in the reference reads the gradients after train.py:564; a caller that wants the
  * clipped gradients in memory must keep torch.nn.utils.clip_grad_norm_.
@@ -144,6 +166,28 @@ int omnipq_adamw_ema_update(int nrec, int nchunks, const void *records, const vo
                             int chunk_elems, int n_only, int n_only_chunks, const void *ema_only, const int *only_chunks,
                             const float *exp_avg_base, const float *acc_base, const long long *accum, const float *coef,
                             const float *ema_coef, const float *result, void *stream);
+
+/* The dynamic loss scale in device memory: torch.amp.GradScaler's two tensors (`_scale` f32, `_growth_tracker` int32). */
+struct omnipq_loss_scaler {
+  float scale;          /* S: the loss is multiplied by it, the gradients arrive scaled by it */
+  int growth_tracker;   /* applying calls with a finite norm since the scale last changed (32 bits) */
+};
+
+/* The layout of struct omnipq_loss_scaler as THIS build compiled it, one line in the format of omnipq_abi_records()
+ * (omnipq_pointops.h): "struct omnipq_loss_scaler scale:f growth_tracker:i".  A binding builds the device struct from this
+ * text; the library asserts at compile time that the text states the sizes and offsets the compiler uses. */
+const char *omnipq_loss_scaler_record(void);
+
+/* The superset finalise, one workgroup: omnipq_adamw_finalize (accum == NULL; accum_steps must then be 1) or
+ * omnipq_adamw_accum_finalize (accum != NULL), with the teacher's coefficients of omnipq_adamw_ema_finalize when ema_state and
+ * ema_coef are set (both NULL or both set), the norm and result[3] divided by scaler_state->scale, and on an applying call the
+ * recurrence of torch._amp_update_scale_ on scaler_state with the factors of scaler_cfg (see the head of this file).
+ * OMNIPQ_EINVAL, before anything is launched: a null scaler_cfg or scaler_state, only one of ema_state / ema_coef, accum ==
+ * NULL with accum_steps != 1, and everything the other finalise entry points refuse. */
+int omnipq_adamw_scaled_finalize(int nchunks, const double *partials, const double *hyper, int ngroups, int accum_steps,
+                                 long long *counters, long long *accum, long long *ema_state, float *ema_coef,
+                                 const double *scaler_cfg, struct omnipq_loss_scaler *scaler_state, float *result,
+                                 float *coef, void *stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,12 @@
 // forms alpha = min(1 - 1/(global_step + 1), decay) from a device word and advances it, the update launch holds the new p in
 // registers and reads and writes the teacher's copy next to it (8 more bytes per parameter instead of a launch of 12), and a
 // few more workgroups average the parameters that have no gradient.
+//
+// Dynamic loss scaling (torch.amp.GradScaler's two tensors and torch._amp_update_scale_) is one more scalar recurrence in the
+// finalise launch (kScaled): thread 0 divides the norm and the update's coefficient by the scale it reads from device memory
+// and, on an applying call, backs the scale off or grows it.  The two streaming launches do not know it exists.
 #include <math.h>
+#include <stddef.h>
 
 #include "common.h"
 #include "omnipq_optim.h"
@@ -175,12 +180,17 @@ __global__ __launch_bounds__(kAdamThreads) void adamw_grad_sqnorm_kernel(const A
 }
 
 // ema_state (kEma): int64[1] = the global_step the NEXT averaging uses; ema_coef: float[2] = { alpha, beta } for the update
-template <bool kAccum, bool kEma>
+// scaler (kScaled): the dynamic loss scale S and its growth tracker; scaler_cfg: double[4] = { growth_factor, backoff_factor,
+// growth_interval, 0 }.  The gradients arrive as S * g: the norm and the update's coefficient are divided by the S read at
+// entry, and an applying call ends with the recurrence of torch._amp_update_scale_.
+template <bool kAccum, bool kEma, bool kScaled>
 __global__ __launch_bounds__(kAdamThreads) void adamw_finalize_kernel(int nchunks, const double *__restrict__ partials,
                                                                      const double *__restrict__ hyper, int ngroups,
                                                                      int accum_steps, long long *__restrict__ counters,
                                                                      long long *__restrict__ accum,
                                                                      long long *__restrict__ ema_state,
+                                                                     const double *__restrict__ scaler_cfg,
+                                                                     omnipq_loss_scaler *__restrict__ scaler,
                                                                      float *__restrict__ result, float *__restrict__ coef,
                                                                      float *__restrict__ ema_coef) {
   double acc = 0.0;
@@ -189,8 +199,15 @@ __global__ __launch_bounds__(kAdamThreads) void adamw_finalize_kernel(int nchunk
   if (threadIdx.x != 0) return;
   const double *last = hyper + 8 * (size_t)ngroups;
   const float max_norm = (float)last[0];
-  const float gs = (float)last[1];
-  const float total_norm = (float)sqrt(sum);
+  float gs = (float)last[1];
+  float total_norm = (float)sqrt(sum);
+  float scale = 1.f;
+  if (kScaled) {
+    scale = scaler->scale;
+    const double inv = 1.0 / (double)scale;
+    total_norm = (float)(sqrt(sum) * inv);           // the norm of the unscaled gradients
+    gs = (float)(last[1] * inv);
+  }
   const bool finite = isfinite(total_norm);
   if (kAccum) {
     // a micro-batch that is not the k-th only counts: the norm of the running sum is reported, nothing else is touched
@@ -212,6 +229,22 @@ __global__ __launch_bounds__(kAdamThreads) void adamw_finalize_kernel(int nchunk
     ema_coef[0] = (float)a;
     ema_coef[1] = (float)(1.0 - a);
     ema_state[0] = step + 1;
+  }
+  if (kScaled) {
+    // torch._amp_update_scale_ (ATen/native/cuda/AmpKernels.cu): float * double in f64, one rounding to f32
+    if (!finite) {
+      scaler->scale = (float)((double)scale * scaler_cfg[1]);
+      scaler->growth_tracker = 0;
+    } else {
+      const int successful = scaler->growth_tracker + 1;
+      if (successful == (int)scaler_cfg[2]) {
+        const float grown = (float)((double)scale * scaler_cfg[0]);
+        if (isfinite(grown)) scaler->scale = grown;
+        scaler->growth_tracker = 0;
+      } else {
+        scaler->growth_tracker = successful;
+      }
+    }
   }
   // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1, in the norm's f32
   float clip = 1.f;
@@ -499,8 +532,8 @@ extern "C" int omnipq_adamw_finalize(int nchunks, const double *partials, const 
                                      long long *counters, float *result, float *coef, void *stream) {
   if (nchunks < 0 || ngroups < 1) return OMNIPQ_EINVAL;
   if (!hyper || !counters || !result || !coef || (nchunks > 0 && !partials)) return OMNIPQ_EINVAL;
-  adamw_finalize_kernel<false, false><<<1, kAdamThreads, 0, (hipStream_t)stream>>>(
-      nchunks, partials, hyper, ngroups, 1, counters, nullptr, nullptr, result, coef, nullptr);
+  adamw_finalize_kernel<false, false, false><<<1, kAdamThreads, 0, (hipStream_t)stream>>>(
+      nchunks, partials, hyper, ngroups, 1, counters, nullptr, nullptr, nullptr, nullptr, result, coef, nullptr);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }
@@ -538,8 +571,8 @@ extern "C" int omnipq_adamw_accum_finalize(int nchunks, const double *partials, 
                                            void *stream) {
   if (nchunks < 0 || ngroups < 1 || accum_steps < 1) return OMNIPQ_EINVAL;
   if (!hyper || !counters || !accum || !result || !coef || (nchunks > 0 && !partials)) return OMNIPQ_EINVAL;
-  adamw_finalize_kernel<true, false><<<1, kAdamThreads, 0, (hipStream_t)stream>>>(
-      nchunks, partials, hyper, ngroups, accum_steps, counters, accum, nullptr, result, coef, nullptr);
+  adamw_finalize_kernel<true, false, false><<<1, kAdamThreads, 0, (hipStream_t)stream>>>(
+      nchunks, partials, hyper, ngroups, accum_steps, counters, accum, nullptr, nullptr, nullptr, result, coef, nullptr);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }
@@ -590,11 +623,11 @@ extern "C" int omnipq_adamw_ema_finalize(int nchunks, const double *partials, co
   if (!hyper || !counters || !ema_state || !result || !coef || !ema_coef || (nchunks > 0 && !partials)) return OMNIPQ_EINVAL;
   if (!accum && accum_steps != 1) return OMNIPQ_EINVAL;
   if (accum)
-    adamw_finalize_kernel<true, true><<<1, kAdamThreads, 0, (hipStream_t)stream>>>(
-        nchunks, partials, hyper, ngroups, accum_steps, counters, accum, ema_state, result, coef, ema_coef);
+    adamw_finalize_kernel<true, true, false><<<1, kAdamThreads, 0, (hipStream_t)stream>>>(
+        nchunks, partials, hyper, ngroups, accum_steps, counters, accum, ema_state, nullptr, nullptr, result, coef, ema_coef);
   else
-    adamw_finalize_kernel<false, true><<<1, kAdamThreads, 0, (hipStream_t)stream>>>(
-        nchunks, partials, hyper, ngroups, 1, counters, nullptr, ema_state, result, coef, ema_coef);
+    adamw_finalize_kernel<false, true, false><<<1, kAdamThreads, 0, (hipStream_t)stream>>>(
+        nchunks, partials, hyper, ngroups, 1, counters, nullptr, ema_state, nullptr, nullptr, result, coef, ema_coef);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }
@@ -620,6 +653,52 @@ extern "C" int omnipq_adamw_ema_update(int nrec, int nchunks, const void *record
     adamw_update_kernel<false, true><<<grid, kAdamThreads, 0, (hipStream_t)stream>>>(
         (const AdamRec *)records, (float *const *)ema_ptrs, nchunks, chunks, chunk_elems, (const EmaOnlyRec *)ema_only,
         only_chunks, nullptr, nullptr, nullptr, coef, ema_coef, result);
+  OMNIPQ_LAUNCH_CHECK();
+  return OMNIPQ_OK;
+}
+
+// ---- dynamic loss scaling: the superset finalise ----------------------------------------------------------------------------
+
+// the layout a binding builds the device struct from (the line format of omnipq_abi_records), held to the compiler's
+extern "C" const char *omnipq_loss_scaler_record(void) {
+  static_assert(sizeof(omnipq_loss_scaler) == 8 && sizeof(float) == 4 && sizeof(int) == 4, "omnipq_loss_scaler: size");
+  static_assert(offsetof(omnipq_loss_scaler, scale) == 0, "omnipq_loss_scaler.scale: offset");
+  static_assert(offsetof(omnipq_loss_scaler, growth_tracker) == 4, "omnipq_loss_scaler.growth_tracker: offset");
+  return "struct omnipq_loss_scaler scale:f growth_tracker:i";
+}
+
+template <bool kAccum, bool kEma>
+static void launch_scaled_finalize(int nchunks, const double *partials, const double *hyper, int ngroups, int accum_steps,
+                                   long long *counters, long long *accum, long long *ema_state, float *ema_coef,
+                                   const double *scaler_cfg, omnipq_loss_scaler *scaler_state, float *result, float *coef,
+                                   hipStream_t stream) {
+  adamw_finalize_kernel<kAccum, kEma, true><<<1, kAdamThreads, 0, stream>>>(
+      nchunks, partials, hyper, ngroups, accum_steps, counters, accum, ema_state, scaler_cfg, scaler_state, result, coef,
+      ema_coef);
+}
+
+extern "C" int omnipq_adamw_scaled_finalize(int nchunks, const double *partials, const double *hyper, int ngroups,
+                                            int accum_steps, long long *counters, long long *accum, long long *ema_state,
+                                            float *ema_coef, const double *scaler_cfg, omnipq_loss_scaler *scaler_state,
+                                            float *result, float *coef, void *stream) {
+  if (nchunks < 0 || ngroups < 1 || accum_steps < 1) return OMNIPQ_EINVAL;
+  if (!hyper || !counters || !result || !coef || (nchunks > 0 && !partials)) return OMNIPQ_EINVAL;
+  if (!scaler_cfg || !scaler_state) return OMNIPQ_EINVAL;
+  if ((ema_state == nullptr) != (ema_coef == nullptr)) return OMNIPQ_EINVAL;
+  if (!accum && accum_steps != 1) return OMNIPQ_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (accum && ema_state)
+    launch_scaled_finalize<true, true>(nchunks, partials, hyper, ngroups, accum_steps, counters, accum, ema_state, ema_coef,
+                                       scaler_cfg, scaler_state, result, coef, st);
+  else if (accum)
+    launch_scaled_finalize<true, false>(nchunks, partials, hyper, ngroups, accum_steps, counters, accum, nullptr, nullptr,
+                                        scaler_cfg, scaler_state, result, coef, st);
+  else if (ema_state)
+    launch_scaled_finalize<false, true>(nchunks, partials, hyper, ngroups, 1, counters, nullptr, ema_state, ema_coef,
+                                        scaler_cfg, scaler_state, result, coef, st);
+  else
+    launch_scaled_finalize<false, false>(nchunks, partials, hyper, ngroups, 1, counters, nullptr, nullptr, nullptr,
+                                         scaler_cfg, scaler_state, result, coef, st);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }

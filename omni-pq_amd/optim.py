@@ -3,11 +3,11 @@
     grad_total_norm = clip_grad_norm_(model.parameters(), config.clip_norm)
     optimizer.step()                      # AdamW over two parameter groups (train.py:364-374)
 
-`FusedAdamW` takes torch.optim.AdamW's arguments plus `max_norm` (the clip, fused in) and `grad_scale` (the inverse of a
-static fp16 loss scale).  One step is three launches over a device table of all parameter tensors (include/omnipq_optim.h:
-squared-norm partials, finalise, update) instead of several dozen multi-tensor launches driven from the host.  Learning
-rates, betas, eps, weight decay, max_norm, grad_scale, the step count and the bias corrections all live in device memory:
-no launch takes one as an argument, so the launches can be captured into `train_step.CapturedStep`'s graph and a replay
+`FusedAdamW` takes torch.optim.AdamW's arguments plus `max_norm` (the clip, fused in), `grad_scale` (the inverse of a
+static fp16 loss scale) and `loss_scaler` (a dynamic one, below).  One step is three launches over a device table of all
+parameter tensors (include/omnipq_optim.h: squared-norm partials, finalise, update) instead of several dozen multi-tensor
+launches driven from the host.  Learning rates, betas, eps, weight decay, max_norm, grad_scale, the step count and the bias
+corrections all live in device memory: no launch takes one as an argument, so the launches can be captured into `train_step.CapturedStep`'s graph and a replay
 follows whatever an LR scheduler wrote into `param_groups` (`sync_hyperparameters()` stages the rows).
 
 What differs from torch.optim.AdamW, all of it stated rather than hidden:
@@ -30,8 +30,19 @@ ema_model, decay)` makes every applying step average the teacher inside the fina
 launches, 8 more bytes per parameter instead of a fourth launch of 12.  alpha = min(1 - 1/(global_step + 1), decay) is formed
 on the device from a step count that lives there, so a captured launch averages with the alpha of its own step; the teacher
 holds the bits `ema.update_ema_variables` would have left after the step.
+
+Dynamic fp16 loss scaling (torch.amp.GradScaler's other half -- the skip on a non-finite norm is the first):
+`FusedAdamW(..., loss_scaler=LossScaler(init_scale, growth_factor, backoff_factor, growth_interval))`.  The scale S and its
+growth tracker are GradScaler's two tensors, in device memory; `opt.loss_scale` IS S (a 0-dim f32 view), the caller writes
+`(loss * opt.loss_scale).backward(); opt.step()`.  The finalise launch (omnipq_adamw_scaled_finalize, the superset of the other
+three) divides the norm and the update's coefficient by the S it reads -- the effective factor is grad_scale / S, the
+squared-norm and update launches are unchanged -- and every applying call ends with the recurrence of
+torch._amp_update_scale_: a non-finite norm backs S off, `growth_interval` finite ones in a row grow it.  S is constant
+over an accumulation window.  A host-side GradScaler cannot do this inside a captured step: its step()/update() read
+found_inf on the host.  `scaler_state_dict()` / `load_scaler_state_dict()` speak GradScaler.state_dict()'s keys and types.
 """
 import ctypes
+import math
 import os
 import sys
 
@@ -60,6 +71,46 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
 
 
+def _is_int(x):
+    return not isinstance(x, bool) and isinstance(x, (int, np.integer))
+
+
+def _is_real(x):
+    return not isinstance(x, bool) and isinstance(x, (int, float, np.integer, np.floating))
+
+
+class LossScaler:
+    """The configuration of a dynamic loss scale: torch.amp.GradScaler's arguments with torch's defaults.  `init_scale` is where
+    FusedAdamW starts; the three others may be changed on the optimiser's copy (`opt.loss_scaler`) at any time and are staged
+    by sync_hyperparameters() like a learning rate."""
+    __slots__ = ("init_scale", "growth_factor", "backoff_factor", "growth_interval")
+
+    def __init__(self, init_scale=2.0 ** 16, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
+        self.init_scale, self.growth_factor, self.backoff_factor = init_scale, growth_factor, backoff_factor
+        self.growth_interval = growth_interval
+        self.validate()
+        self.init_scale, self.growth_factor = float(init_scale), float(growth_factor)
+        self.backoff_factor, self.growth_interval = float(backoff_factor), int(growth_interval)
+
+    def validate(self):
+        if not _is_real(self.init_scale) or not math.isfinite(self.init_scale) or not self.init_scale > 0:
+            raise ValueError(f"LossScaler: init_scale must be a finite number > 0, not {self.init_scale!r}")
+        with np.errstate(over="ignore", under="ignore"):
+            as_f32 = float(np.float32(self.init_scale))
+        if as_f32 == 0.0 or not math.isfinite(as_f32):
+            raise ValueError(f"LossScaler: init_scale={self.init_scale!r} is zero or infinite in float32, the scale's type")
+        if not _is_real(self.growth_factor) or not math.isfinite(self.growth_factor) or not self.growth_factor > 1:
+            raise ValueError(f"LossScaler: growth_factor must be a finite number > 1, not {self.growth_factor!r}")
+        if not _is_real(self.backoff_factor) or not 0 < self.backoff_factor < 1:
+            raise ValueError(f"LossScaler: backoff_factor must be in (0, 1), not {self.backoff_factor!r}")
+        if not _is_int(self.growth_interval) or self.growth_interval < 1 or self.growth_interval > 2 ** 31 - 1:
+            raise ValueError(f"LossScaler: growth_interval must be an integer in [1, 2^31), not {self.growth_interval!r}")
+
+    def __repr__(self):
+        return (f"LossScaler(init_scale={self.init_scale!r}, growth_factor={self.growth_factor!r}, "
+                f"backoff_factor={self.backoff_factor!r}, growth_interval={self.growth_interval!r})")
+
+
 class _Table:
     """The device tables of one (parameter, gradient) address set."""
     __slots__ = ("key", "shape_key", "records", "chunks", "partials", "nrec", "nchunks",
@@ -68,7 +119,7 @@ class _Table:
 
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
-                 max_norm=0.0, grad_scale=1.0, chunk_elems=CHUNK, accum_steps=1):
+                 max_norm=0.0, grad_scale=1.0, chunk_elems=CHUNK, accum_steps=1, loss_scaler=None):
         if amsgrad:
             raise NotImplementedError("FusedAdamW: amsgrad is not implemented (the reference does not use it)")
         if maximize:
@@ -77,6 +128,14 @@ class FusedAdamW(torch.optim.Optimizer):
             raise ValueError("FusedAdamW: chunk_elems must be a positive multiple of 1024")
         if isinstance(accum_steps, bool) or not isinstance(accum_steps, (int, np.integer)) or accum_steps < 1:
             raise ValueError("FusedAdamW: accum_steps must be an integer >= 1 (the number of micro-batches summed per step)")
+        if loss_scaler is not None:
+            if not isinstance(loss_scaler, LossScaler):
+                raise ValueError("FusedAdamW: loss_scaler is an optim.LossScaler or None (a torch.amp.GradScaler reads found_inf "
+                                 "on the host and cannot run inside a captured step)")
+            loss_scaler.validate()
+            # the optimiser's own copy: growth_factor, backoff_factor and growth_interval may be changed on it
+            loss_scaler = LossScaler(loss_scaler.init_scale, loss_scaler.growth_factor, loss_scaler.backoff_factor,
+                                     loss_scaler.growth_interval)
         # torch.optim.AdamW validates the values and knows which keys a param_group of THIS torch carries: its defaults are
         # taken over as they are, so that a state_dict of either optimiser has the other's param_groups keys
         probe = torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
@@ -114,13 +173,28 @@ class FusedAdamW(torch.optim.Optimizer):
         self._teacher = None
         self.ema_decay = 0.0
         self.ema_state = self.ema_coef = None
+        # dynamic loss scaling: one omnipq_loss_scaler { scale, growth_tracker } in device memory, laid out as the loaded
+        # library reports it; its three factors travel in one more row of the staged hyper-parameters (_rows)
+        self.loss_scaler = loss_scaler
+        self.scaler_state = self.loss_scale = self._tracker = None
+        if loss_scaler is not None:
+            rec = _ext().loss_scaler_struct()
+            if (rec.scale.size, rec.growth_tracker.size) != (4, 4) or rec.scale.offset % 4 or rec.growth_tracker.offset % 4:
+                raise RuntimeError("FusedAdamW: the loaded library's struct omnipq_loss_scaler is not { float, int32 }")
+            self.scaler_state = torch.zeros(ctypes.sizeof(rec), dtype=torch.uint8, device=dev)
+            o = rec.scale.offset
+            self.loss_scale = self.scaler_state[o:o + 4].view(torch.float32).reshape(())      # a view: S itself
+            o = rec.growth_tracker.offset
+            self._tracker = self.scaler_state[o:o + 4].view(torch.int32).reshape(())
+            self.loss_scale.fill_(loss_scaler.init_scale)
         ngroups = len(self.param_groups)
+        nrows = ngroups + 1 + (loss_scaler is not None)
         self.counters = torch.zeros(2, dtype=torch.int64, device=dev)             # t, skipped
         self.result = torch.zeros(4, dtype=torch.float32, device=dev)             # total_norm, clip_coef, found_nonfinite, g coefficient
         self.grad_total_norm = self.result[0]                                      # what step() returns: rewritten by every step
         self._coef = torch.zeros(ngroups * ROW, dtype=torch.float32, device=dev)
-        self._hyper = torch.zeros((ngroups + 1, ROW), dtype=torch.float64, device=dev)
-        self._stages = [torch.zeros((ngroups + 1, ROW), dtype=torch.float64, pin_memory=dev.type == "cuda")
+        self._hyper = torch.zeros((nrows, ROW), dtype=torch.float64, device=dev)
+        self._stages = [torch.zeros((nrows, ROW), dtype=torch.float64, pin_memory=dev.type == "cuda")
                         for _ in range(_STAGES if dev.type == "cuda" else 1)]
         self._stage_events = [None] * len(self._stages)
         self._stage_next = 0
@@ -169,6 +243,47 @@ class FusedAdamW(torch.optim.Optimizer):
     def is_update_step(self):
         """was the last step() / launch() (or replay of a captured launch()) the applying one?  Host-side, no device read."""
         return self._applied
+
+    # ---- the dynamic loss scale ---------------------------------------------------------------------------------------------
+    def _need_scaler(self, what):
+        if self.loss_scaler is None:
+            raise RuntimeError(f"FusedAdamW.{what}: this optimiser was built without loss_scaler=")
+
+    @property
+    def scale_value(self):
+        """the loss scale the NEXT step's loss is multiplied by (reads the device); None without a loss scaler"""
+        return None if self.loss_scaler is None else float(self.loss_scale)
+
+    @property
+    def growth_tracker(self):
+        """applying steps with a finite norm since the scale last changed (reads the device); None without a loss scaler"""
+        return None if self.loss_scaler is None else int(self._tracker)
+
+    def scaler_state_dict(self):
+        """torch.amp.GradScaler.state_dict(): the same keys and value types, so either loads what the other wrote.  Not part
+        of state_dict(), which stays torch.optim.AdamW's: save the two next to each other."""
+        self._need_scaler("scaler_state_dict")
+        return {"scale": self.scale_value, "growth_factor": float(self.loss_scaler.growth_factor),
+                "backoff_factor": float(self.loss_scaler.backoff_factor),
+                "growth_interval": int(self.loss_scaler.growth_interval), "_growth_tracker": self.growth_tracker}
+
+    def load_scaler_state_dict(self, state_dict):
+        """What GradScaler.load_state_dict() accepts.  The scale and the tracker are written to the device on the current
+        stream, the factors are staged like hyper-parameters: a captured launch sees all of them on its next replay."""
+        self._need_scaler("load_scaler_state_dict")
+        if len(state_dict) == 0:
+            raise RuntimeError("FusedAdamW.load_scaler_state_dict: the state dict is empty (written by a disabled GradScaler?)")
+        tracker = state_dict["_growth_tracker"]
+        if not _is_int(tracker) or not 0 <= tracker <= 2 ** 31 - 1:
+            raise ValueError(f"FusedAdamW.load_scaler_state_dict: _growth_tracker must be an integer >= 0, not {tracker!r}")
+        loaded = LossScaler(state_dict["scale"], state_dict["growth_factor"], state_dict["backoff_factor"],
+                            state_dict["growth_interval"])
+        self.loss_scaler.growth_factor, self.loss_scaler.backoff_factor = loaded.growth_factor, loaded.backoff_factor
+        self.loss_scaler.growth_interval = loaded.growth_interval
+        with torch.no_grad():
+            self.loss_scale.fill_(loaded.init_scale)
+            self._tracker.fill_(int(tracker))
+        self.sync_hyperparameters()
 
     def reset_accumulation(self):
         """Discard a partial sum (where the reference's zero_grad does: the start of an epoch).  The device word is set to 0
@@ -281,15 +396,21 @@ class FusedAdamW(torch.optim.Optimizer):
 
     # ---- hyper-parameters ----------------------------------------------------------------------------------------------------
     def _rows(self):
-        rows = np.zeros((len(self.param_groups) + 1, ROW), dtype=np.float64)
+        ng = len(self.param_groups)
+        rows = np.zeros((ng + 1 + (self.loss_scaler is not None), ROW), dtype=np.float64)
         for i, g in enumerate(self.param_groups):
             rows[i, :5] = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
-        rows[-1, :3] = (self.max_norm, self.grad_scale, float(self.ema_decay))
+        rows[ng, :3] = (self.max_norm, self.grad_scale, float(self.ema_decay))
+        if self.loss_scaler is not None:
+            # scaler_cfg of omnipq_adamw_scaled_finalize: one row behind the ones the other launches index by ngroups
+            self.loss_scaler.validate()
+            rows[ng + 1, :3] = (float(self.loss_scaler.growth_factor), float(self.loss_scaler.backoff_factor),
+                                float(self.loss_scaler.growth_interval))
         return rows
 
     def sync_hyperparameters(self):
-        """Stage the rows {lr, beta1, beta2, eps, weight_decay} of every param_group and {max_norm, grad_scale, ema_decay} to the device
-        when a host value has changed since the last call: pinned staging tensor, non-blocking copy on the current stream, no
+        """Stage the rows {lr, beta1, beta2, eps, weight_decay} of every param_group, {max_norm, grad_scale, ema_decay} and -- with
+        a loss scaler -- {growth_factor, backoff_factor, growth_interval} to the device when a host value has changed since the last call: pinned staging tensor, non-blocking copy on the current stream, no
         host read of the device.  An LR scheduler keeps working on `param_groups`; step() calls this, and so does
         CapturedStep.step() in front of its replay.  -> True when rows were sent."""
         rows = self._rows()
@@ -412,7 +533,9 @@ class FusedAdamW(torch.optim.Optimizer):
     def launch(self):
         """The three launches on the current stream, hyper-parameters as they are on the device (no staging, no host read):
         what CapturedStep records into its graph.  -> the device tensor grad_total_norm.  accum_steps = k > 1: one call per
-        micro-batch, the same three launches every time; the k-th call applies the sum, the others only add and count."""
+        micro-batch, the same three launches every time; the k-th call applies the sum, the others only add and count.
+        With a loss scaler the gradients are expected scaled by `loss_scale` as it stood when they were computed; the norm
+        returned is that of the unscaled gradients, and an applying call leaves the next step's scale in `loss_scale`."""
         if self.device.type != "cuda":
             raise RuntimeError("CPU not supported")      # like the native ops: no CPU path in the product
         ext = _ext()
@@ -420,51 +543,55 @@ class FusedAdamW(torch.optim.Optimizer):
         if tab.nrec == 0:
             return self.grad_total_norm
         lib, ng = ext._lib0, len(self.param_groups)
-        if self._teacher is not None:
-            # the same three launches with the teacher's averaging inside the last two (accum is None: the plain family)
-            if self.accum_steps > 1:
-                ext._run(lib.omnipq_adamw_accum_sqnorm, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.chunks),
-                         self.chunk_elems, _ptr(self._hyper), ng, _ptr(self.exp_avg), _ptr(self.acc), _ptr(self.accum),
-                         _ptr(tab.partials))
-            else:
-                ext._run(lib.omnipq_adamw_grad_sqnorm, self.result, tab.nrec, tab.nchunks, _ptr(tab.records),
-                         _ptr(tab.chunks), self.chunk_elems, _ptr(self._hyper), ng, _ptr(tab.partials))
+        accum, teacher = self.accum_steps > 1, self._teacher is not None
+        # 1. squared-norm partials (accumulating: of the running sum, which it also stores)
+        if accum:
+            ext._run(lib.omnipq_adamw_accum_sqnorm, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.chunks),
+                     self.chunk_elems, _ptr(self._hyper), ng, _ptr(self.exp_avg), _ptr(self.acc), _ptr(self.accum),
+                     _ptr(tab.partials))
+        else:
+            ext._run(lib.omnipq_adamw_grad_sqnorm, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.chunks),
+                     self.chunk_elems, _ptr(self._hyper), ng, _ptr(tab.partials))
+        # 2. finalise: with a loss scaler the superset entry point serves every family (accum / ema_state are None where the
+        # family has none); without one, the entry point of the family, as before
+        if self.loss_scaler is not None:
+            ext._run(lib.omnipq_adamw_scaled_finalize, self.result, tab.nchunks, _ptr(tab.partials), _ptr(self._hyper), ng,
+                     self.accum_steps, _ptr(self.counters), _ptr(self.accum), _ptr(self.ema_state), _ptr(self.ema_coef),
+                     _ptr(self._hyper[ng + 1]), _ptr(self.scaler_state), _ptr(self.result), _ptr(self._coef))
+        elif teacher:
             ext._run(lib.omnipq_adamw_ema_finalize, self.result, tab.nchunks, _ptr(tab.partials), _ptr(self._hyper), ng,
                      self.accum_steps, _ptr(self.counters), _ptr(self.accum), _ptr(self.ema_state), _ptr(self.result),
                      _ptr(self._coef), _ptr(self.ema_coef))
+        elif accum:
+            ext._run(lib.omnipq_adamw_accum_finalize, self.result, tab.nchunks, _ptr(tab.partials), _ptr(self._hyper), ng,
+                     self.accum_steps, _ptr(self.counters), _ptr(self.accum), _ptr(self.result), _ptr(self._coef))
+        else:
+            ext._run(lib.omnipq_adamw_finalize, self.result, tab.nchunks, _ptr(tab.partials), _ptr(self._hyper), ng,
+                     _ptr(self.counters), _ptr(self.result), _ptr(self._coef))
+        # 3. update (with a teacher: and its averaging; accum is None in the plain family)
+        if teacher:
             ext._run(lib.omnipq_adamw_ema_update, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.ema_ptrs),
                      _ptr(tab.chunks), self.chunk_elems, tab.n_only, tab.n_only_chunks, _ptr(tab.ema_only),
                      _ptr(tab.only_chunks), _ptr(self.exp_avg), _ptr(self.acc), _ptr(self.accum), _ptr(self._coef),
                      _ptr(self.ema_coef), _ptr(self.result))
-            if self.accum_steps > 1:
-                self.replayed()
-            else:
-                self._applied = True
-            return self.grad_total_norm
-        if self.accum_steps > 1:
-            ext._run(lib.omnipq_adamw_accum_sqnorm, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.chunks),
-                     self.chunk_elems, _ptr(self._hyper), ng, _ptr(self.exp_avg), _ptr(self.acc), _ptr(self.accum),
-                     _ptr(tab.partials))
-            ext._run(lib.omnipq_adamw_accum_finalize, self.result, tab.nchunks, _ptr(tab.partials), _ptr(self._hyper), ng,
-                     self.accum_steps, _ptr(self.counters), _ptr(self.accum), _ptr(self.result), _ptr(self._coef))
+        elif accum:
             ext._run(lib.omnipq_adamw_accum_update, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.chunks),
                      self.chunk_elems, _ptr(self.exp_avg), _ptr(self.acc), _ptr(self.accum), _ptr(self._coef),
                      _ptr(self.result))
+        else:
+            ext._run(lib.omnipq_adamw_update, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.chunks),
+                     self.chunk_elems, _ptr(self._coef), _ptr(self.result))
+        if accum:
             self.replayed()
-            return self.grad_total_norm
-        ext._run(lib.omnipq_adamw_grad_sqnorm, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.chunks),
-                 self.chunk_elems, _ptr(self._hyper), ng, _ptr(tab.partials))
-        ext._run(lib.omnipq_adamw_finalize, self.result, tab.nchunks, _ptr(tab.partials), _ptr(self._hyper), ng,
-                 _ptr(self.counters), _ptr(self.result), _ptr(self._coef))
-        ext._run(lib.omnipq_adamw_update, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.chunks),
-                 self.chunk_elems, _ptr(self._coef), _ptr(self.result))
-        self._applied = True
+        else:
+            self._applied = True
         return self.grad_total_norm
 
     @torch.no_grad()
     def step(self, closure=None):
         """clip_grad_norm_(max_norm) + AdamW.step() in three launches.  -> grad_total_norm, a 0-dim DEVICE tensor (the norm of
-        grad_scale * gradients before clipping; rewritten by the next step).  Parameters whose .grad is None are left out.
+        grad_scale * gradients before clipping -- with a loss scaler divided by the scale the gradients carry, i.e. of the
+        unscaled gradients; rewritten by the next step).  Parameters whose .grad is None are left out.
         accum_steps = k > 1: call once per micro-batch.  Every call adds the gradients into the accumulator and returns the
         norm of grad_scale * the running SUM; every k-th call clips and applies that sum (`is_update_step`), the others leave
         parameters, moments and the step count alone.  The gradients are summed as in the reference, whose loss is not
@@ -480,12 +607,14 @@ class FusedAdamW(torch.optim.Optimizer):
     # ---- save / restore (CapturedStep's warm-up and capture runs must leave no trace) ---------------------------------------
     def _saved_tensors(self):
         return (self.exp_avg, self.exp_avg_sq, self.counters, self.result) + \
+            ((self.scaler_state,) if self.loss_scaler is not None else ()) + \
             ((self.acc, self.accum) if self.accum_steps > 1 else ()) + \
             ((self.ema_state, self.ema_coef) + tuple(e for e, _ in self._teacher) if self._teacher is not None else ())
 
     def snapshot(self):
         """moments, counters and -- the warm-up and capture runs advance them too -- the accumulator, the device micro-batch
-        counter and its host mirror; with a teacher attached its global_step, coefficients and weights as well"""
+        counter and its host mirror; with a teacher attached its global_step, coefficients and weights as well; with a loss
+        scaler its scale and growth tracker"""
         return [t.detach().clone() for t in self._saved_tensors()] + [(self._micro, self._applied)]
 
     def restore(self, saved):

@@ -96,12 +96,26 @@ def struct(name):
     every pointer, arrays for arrays.  One class per name; resolve it once at import, not per call.  omni-pq_amd/build.py:
     record_struct() is the same mapping on the build's side, where the compiler checks its sizes and offsets against the C
     definitions (csrc/capi.hip)."""
+    return _structure(name, _record("struct", name))
+
+
+def _structure(name, record_fields):
     fields = []
-    for field in _record("struct", name):
+    for field in record_fields:
         fname, _, kind = field.partition(":")
         letter, _, count = kind.partition("*")
         fields.append((fname, _CTYPE[letter] * int(count) if count else _CTYPE[letter]))
     return type(name, (ctypes.Structure,), {"_fields_": fields})
+
+
+@functools.lru_cache(maxsize=None)
+def loss_scaler_struct():
+    """The `ctypes.Structure` of `struct omnipq_loss_scaler` (include/omnipq_optim.h), from the one record line the loaded
+    library reports for it (omnipq_loss_scaler_record: the format of omnipq_abi_records' struct lines)."""
+    kind, name, *fields = _lib0.omnipq_loss_scaler_record().decode().split()
+    if (kind, name) != ("struct", "omnipq_loss_scaler"):
+        raise KeyError(f"pointnet2._ext: the loaded library ({_LIB_PATH}) reports `{kind} {name}` as its loss scaler record")
+    return _structure(name, fields)
 
 
 class _Elem16(threading.local):

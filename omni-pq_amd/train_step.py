@@ -53,7 +53,19 @@ class CapturedStep:
     example_inputs   {'point_clouds': (B, N, 3 + C) f32 on the GPU} (or the tensor): fixes the batch shape; its contents
                      are only used for the warm-up steps.
     amp_dtype        torch.bfloat16 / torch.float16 / None (strict f32); loss_scale: static scale applied to the loss before
-                     backward (fp16: 2^14, what torch.amp.GradScaler would settle on; gradients come back scaled).
+                     backward (fp16: 2^14, what torch.amp.GradScaler would settle on; gradients come back scaled), or
+                     "dynamic": torch.amp.GradScaler's behaviour inside the step.  Accepted with
+                     optimizer=optim.FusedAdamW(..., loss_scaler=optim.LossScaler(...)) and with nothing else (such an
+                     optimizer in turn takes no numeric loss_scale other than 1).  The loss is multiplied by
+                     optimizer.loss_scale, a device word (one multiply, as with a static scale: the step's launch count does
+                     not change); the optimizer's finalise launch un-scales, skips a step whose norm is not finite, backs the
+                     scale off then and grows it after growth_interval good steps, so a replay follows the scale the one
+                     before it left.  Composes with step_freq=k (the scale is constant over an accumulation window),
+                     teacher= / ema_in_step=True and buckets=.  Under data parallelism the gradients are all-reduced before
+                     the optimizer's launches, so every rank forms the same norm from the same bits and takes the same
+                     decision: the scales stay equal without a collective of their own (they start equal: same init_scale
+                     or the same loaded scaler_state_dict()).  optimizer.scale_value / .growth_tracker read it back;
+                     building the stepper leaves both where they were.
     graph            True: capture + replay; False: the same step launched eagerly (debugging, A/B).
     prefetch         "forward": the next batch's sampling chain starts inside forward() (default), "backward": between
                      forward and backward, None: no prefetch (every forward samples its own batch: +5 ms at 40 000 points).
@@ -129,6 +141,18 @@ class CapturedStep:
                              "optimizer accumulates `.grad` itself after each step(), with step_freq=1)")
         self.step_freq = step_freq
         self.is_update_step = False
+        scaler = optimizer.loss_scaler if optimizer is not None else None
+        self.dynamic_scale = isinstance(loss_scale, str)
+        if (self.dynamic_scale and (loss_scale != "dynamic" or scaler is None)) or \
+                (not self.dynamic_scale and scaler is not None and float(loss_scale) != 1.0):
+            raise ValueError(f"CapturedStep: loss_scale={loss_scale!r} with " +
+                             ("an optimizer built with " + ("a loss_scaler" if scaler is not None else "no loss_scaler")
+                              if optimizer is not None else "no in-graph optimizer") +
+                             " -- a scale that backs off and grows lives in the optimizer's device memory, so "
+                             'loss_scale="dynamic" needs optimizer=optim.FusedAdamW(loss_scaler=optim.LossScaler(...)), and '
+                             "such an optimizer takes no second, static scale (a number other than 1) on top of its own")
+        if self.dynamic_scale:
+            loss_scale = 1.0             # the loss is multiplied by optimizer.loss_scale, a device tensor (_backward)
         if optimizer is not None:
             if float(loss_scale) != 1.0:
                 optimizer.grad_scale = 1.0 / float(loss_scale)
@@ -194,7 +218,9 @@ class CapturedStep:
         import sa_fused
         if self.buckets is not None:
             self.buckets.collectives = 0
-        if self.scale != 1.0:
+        if self.dynamic_scale:
+            loss = loss * self.optimizer.loss_scale      # the device word the optimizer's finalise launch maintains
+        elif self.scale != 1.0:
             loss = loss * self.scale
         if self.defer:
             with sa_fused.deferred_wgrads(on_early_flush=self.buckets.on_early_flush if self.buckets is not None else None):
