@@ -426,6 +426,46 @@ int omnipq_sa_last_wgrad_combine(int C3, int C2, const float *R, const float *cs
                                  const float *alpha, const float *beta, const void *Wp, int ldw, float *out, int out_ld,
                                  int accumulate, void *stream);
 
+/* ---- the inference stage in ONE launch (csrc/sa_infer.hip) ---------------------------------------------------
+ * Replaces, for `model.eval()` under `torch.no_grad()`, the grouping, the shared MLP and the max-pool of a set-abstraction
+ * stage (reference pointnet2_modules.py:243-262: QueryAndGroup, SharedMLP, max_pool2d; pytorch_utils.py:11-64: Conv2d 1x1 +
+ * BatchNorm2d + ReLU per layer) -- what omnipq_sa_gather, one omnipq_gemm_nt_e16 + omnipq_bnrelu per layer and omnipq_sa_pool
+ * compute as separate launches with every activation stored.  In eval mode BatchNorm is an affine known before the launch, so
+ * a tile of balls goes from point indices to pooled features inside one workgroup.
+ *
+ * `layers` is a HOST array of nlayers records (read during the call only):
+ *   W              e16 [C][ldw], what omnipq_prep_weight leaves: layer 0 with rot = 3 over kpad columns ([features | xyz | 0]),
+ *                  layer l > 0 over K = C of layer l - 1 columns; ldw >= K, ldw % 8 == 0
+ *   gamma, beta, running_mean, running_var   float[C];  eps: the BatchNorm's
+ * omnipq_sa_infer_layer_record() reports the record's layout as THIS build compiled it, one line in the format of
+ * omnipq_abi_records() (omnipq_pointops.h); a binding builds its structure from that text.
+ *
+ * Per ball (b, j), with p = (b m + j) s + t and column c:
+ *   rows       x0[p] = [feat_pm[b][idx[p]][0..cin) | (xyz[b][idx[p]] - new_xyz[b][j]) * inv_radius | 0 .. kpad): subtracted, then
+ *              multiplied, in f32 and rounded to e16 -- bit for bit the row omnipq_sa_gather writes.  feat_pm NULL iff cin == 0.
+ *   layer l    x_{l+1} = relu(a_l .* (W_l x_l) + b_l), a_l = gamma / sqrt(running_var + eps), b_l = beta - running_mean a_l formed
+ *              in f32 by the kernel; f32 MFMA accumulation, affine and ReLU on the f32 accumulator; below the last layer the
+ *              result is rounded to e16 ONCE.
+ *   last       out_f32[(b, j)][c] = max_t relu(a acc + b) in f32 (no 16-bit rounding), out_pm = e16(out_f32); both
+ *              position-major [b m][C], the layout of omnipq_sa_pool.  No arg, Y or X is written.
+ * Nothing of shape [b m s][.] touches global memory.  No atomics (bit-reproducible), no host read, no allocation; one launch
+ * with a static grid: graph-capturable.
+ * Shapes: s in {16, 32, 64, 128}; 1 <= nlayers <= 3; every C % 32 == 0, 32 <= C <= 640; kpad % 32 == 0, kpad >= cin + 3;
+ * cin % 8 == 0; and an LDS footprint the CU has.  omnipq_sa_infer_lds_bytes (host only) = the dynamic LDS bytes the launch
+ * asks for (at most 160 KiB), or -1 for a shape the kernel does not take; omnipq_sa_infer returns OMNIPQ_EINVAL in exactly
+ * those cases (and for a NULL required pointer), before anything is launched. */
+struct omnipq_sa_infer_layer {
+  const void *W;
+  int ldw, C;
+  const float *gamma, *beta, *running_mean, *running_var;
+  float eps;
+};
+const char *omnipq_sa_infer_layer_record(void);
+long long omnipq_sa_infer_lds_bytes(int s, int kpad, int nlayers, const int *widths);
+int omnipq_sa_infer(int b, int n, int m, int s, int cin, int kpad, float inv_radius, const float *xyz, const float *new_xyz,
+                    const int *idx, const void *feat_pm, int nlayers, const void *layers, float *out_f32, void *out_pm,
+                    void *stream);
+
 /* ---- one-shot peer-to-peer all-reduce of a small f64 vector between the ranks of one node (round 6; csrc/ipc_exchange.hip) ----
  * The SyncBatchNorm statistics exchange (reference models/pq_transformer.py:194) without RCCL: every rank owns a mailbox
  * (omnipq_ipc_mailbox_create: device memory + a 64-byte hipIpc handle for the peers; omnipq_ipc_mailbox_open maps a peer's),

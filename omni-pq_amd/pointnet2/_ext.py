@@ -118,6 +118,16 @@ def loss_scaler_struct():
     return _structure(name, fields)
 
 
+@functools.lru_cache(maxsize=None)
+def sa_infer_layer_struct():
+    """The `ctypes.Structure` of `struct omnipq_sa_infer_layer` (include/omnipq_sa.h: the host record of one layer of
+    omnipq_sa_infer), from the record line the loaded library reports for it (omnipq_sa_infer_layer_record)."""
+    kind, name, *fields = _lib0.omnipq_sa_infer_layer_record().decode().split()
+    if (kind, name) != ("struct", "omnipq_sa_infer_layer"):
+        raise KeyError(f"pointnet2._ext: the loaded library ({_LIB_PATH}) reports `{kind} {name}` as its inference layer record")
+    return _structure(name, fields)
+
+
 class _Elem16(threading.local):
     """The element type the hand-written 16-bit kernels are running in: `E16.dtype`.  It follows torch.autocast:
     every entry into the hand-written path asks `E16.autocast()` -- True when CUDA autocast is on with a dtype a library

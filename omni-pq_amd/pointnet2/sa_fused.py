@@ -91,6 +91,8 @@ class _tagged:
 
 _STAGE_LABEL = None  # set by run(): the stage's name for the timing sink ("sa1" .. "vote", or m<npoint>s<nsample>)
 _SYNC = True       # set by run() per stage: do this stage's BatchNorm layers synchronise across ranks (SyncBatchNorm)?
+_NO_GRAD = False   # set by run() for the duration of the stage: was it called with autograd off (`not torch.is_grad_enabled()`)?
+                   # Asked there, not in FusedSAStage.forward: inside a Function's forward grad mode is always off
 
 
 def _world():
@@ -513,6 +515,28 @@ def last_no_dy_ok(plan, L, P, c2, c3, S, below_keeps_y_only):
     return LAST_NO_DY and c3 <= LAST_NO_DY_MAX_C3 and plan is not None and getattr(plan, "unit_src", None) is not None and L >= 2 and \
         _partial_sum_rows(P) and below_keeps_y_only and c2 % 128 == 0 and c3 % 128 == 0 and c2 + 32 <= 1024 and S >= 8 and \
         (S & (S - 1)) == 0 and AFFINE_OPERANDS and POOL_EPILOGUE
+
+
+# The INFERENCE stage in one launch (csrc/sa_infer.hip, include/omnipq_sa.h: omnipq_sa_infer).  In eval mode
+# BatchNorm is the affine a = gamma / sqrt(running_var + eps), b = beta - running_mean a, known before the launch, so no
+# grid-wide statistics sit between a layer's GEMM and its consumer: a tile of balls goes from point indices to pooled features
+# inside one workgroup -- gather, up to three conv + folded BatchNorm + ReLU layers and the max-pool -- and nothing of shape
+# [P][.] is written.  Taken when nothing can ask for a backward: eval mode, run() called under torch.no_grad().
+# EVAL_CHAIN = False restores the stored dataflow (gather, one GEMM + normalise/ReLU pass per layer, pool).
+EVAL_CHAIN = True
+eval_chain_uses = 0
+_InferLayer = _ext.sa_infer_layer_struct()
+
+
+@functools.lru_cache(maxsize=None)
+def _infer_lds_bytes(S, kpad, widths):
+    return int(_lib.omnipq_sa_infer_lds_bytes(S, kpad, len(widths), (ctypes.c_int * len(widths))(*widths)))
+
+
+def eval_chain_ok(S, kpad, widths):
+    """the shapes omnipq_sa_infer takes (nsample 16 / 32 / 64 / 128, one to three layers of 32 k <= 640 channels, kpad % 32 == 0
+    and an LDS footprint the CU has): asked of the library, which refuses exactly the others"""
+    return _infer_lds_bytes(int(S), int(kpad), tuple(int(w) for w in widths)) > 0
 
 
 def last_wgrad_dz(Y2, below, hot, plan, S, C3, C2, P, alpha, beta, Wp, out=None):
@@ -1056,12 +1080,15 @@ class StageRoute(typing.NamedTuple):
     condition in stage_route(), and a step function for the dispatchers (_forward_layers, FusedSAStage._backward) to call."""
     training: bool
     first: str        # layer 0: "grouped" (on the gathered rows [features | xyz]) | "xyz" (generated from the grouped coordinates,
-                      # never stored: XYZGEN) | "source" (on the source points, gathered afterwards: HOIST_L1)
+                      # never stored: XYZGEN) | "source" (on the source points, gathered afterwards: HOIST_L1) | "chain" (the
+                      # whole stage, gather to pool, is ONE forward-only launch: EVAL_CHAIN)
     plan_gs: int      # rows per group of the stage's row plan (ROW_PLAN); 0: every row is computed
     plan_arrives: bool    # the plan that came with idx is the stage's (else forward makes one)
     feed: tuple       # per layer below the last, what its consumers read: "stored" relu(bn(Y)) | "yab" (Y, a, b) (AFFINE_OPERANDS)
+                      # | "lds" (the activation never leaves the workgroup: "chain")
     finalize: tuple   # per layer, where its BatchNorm is finalised: "launch" (its own) | "relu" (with the ReLU pass) | "consumer"
                       # (the prologue of the GEMM it feeds) | "pool" (the pool-select launch) | "running" (eval: nothing to do)
+                      # | "folded" (eval, "chain": the kernel forms a / b from the running estimates itself)
     extrema: str      # ball extrema recorded by the last GEMM (POOL_EPILOGUE): "" (the pool scans Y) | "both" | "one" (the side
                       # gamma's sign selects: ONE_SIDED_EXTREMA)
     last: str         # the last layer's backward: "y" (statistics from the stored Y) | "ysel" (from the pooled rows' values) |
@@ -1069,12 +1096,16 @@ class StageRoute(typing.NamedTuple):
     keep_x2: bool     # "no_dy": the data-gradient launch leaves X2 for the weight gradient (LAST_X2)
 
 
-def stage_route(training, B, N, M, S, cin_raw, widths, has_features, xyz_grad, feat_grad, plan_gs=None, plan_unit_map=False):
+def stage_route(training, B, N, M, S, cin_raw, widths, has_features, xyz_grad, feat_grad, plan_gs=None, plan_unit_map=False,
+                no_grad=False):
     """The route of a stage from shapes alone (no tensor, no launch; the module switches are read now).  widths: the layers'
     output channels; xyz_grad / feat_grad: a gradient flows into the coordinates / the features; plan_gs, plan_unit_map: group
-    size of the plan that came with idx (None: none did) and whether it carries a unit map."""
+    size of the plan that came with idx (None: none did) and whether it carries a unit map; no_grad: nothing will ask this
+    pass for a backward (eval under torch.no_grad(): the forward may keep nothing)."""
     L, P = len(widths), B * M * S
     if not training:
+        if no_grad and EVAL_CHAIN and eval_chain_ok(S, _round_up(_round_up(cin_raw, 8) + 3, 32), widths):
+            return StageRoute(False, "chain", 0, False, ("lds",) * (L - 1), ("folded",) * L, "", "y", False)
         return StageRoute(False, "grouped", 0, False, ("stored",) * (L - 1), ("running",) * L, "", "y", False)
     xgen = not has_features and xyzgen_ok(P, L, widths[0], xyz_grad) and affine_pays(P, widths[1])
     plan, arrives = None, False
@@ -1095,7 +1126,8 @@ def stage_route(training, B, N, M, S, cin_raw, widths, has_features, xyz_grad, f
 
 def _count_uses(route):
     """the counters the tests read to see which route ran"""
-    global xyzgen_uses, row_plan_uses, hoist_uses, last_no_dy_uses
+    global xyzgen_uses, row_plan_uses, hoist_uses, last_no_dy_uses, eval_chain_uses
+    eval_chain_uses += route.first == "chain"
     xyzgen_uses += route.first == "xyz"
     hoist_uses += route.first == "source"
     row_plan_uses += route.plan_gs > 0
@@ -1215,10 +1247,34 @@ def _eval_layer(g, lay, X, gamma, beta, bn, last):
     return lay.X
 
 
+def _eval_chain(g, xyz_c, cen_c, idx, feat_pm, params, bn_cfg, dev):
+    """route "chain" (see EVAL_CHAIN): the whole stage as ONE launch.  -> (layers, (out f32 [B][M][C], its 16-bit twin))"""
+    L = len(bn_cfg)
+    layers = [_new_layer(l, params[3 * l], g, False) for l in range(L)]
+    recs = (_InferLayer * L)()
+    keep = []                                   # the f32 vectors the records point to (copies, where a buffer is not f32)
+    for l, (lay, rec) in enumerate(zip(layers, recs)):
+        rm, rv, _, _, eps = bn_cfg[l]
+        vecs = [v.detach().float().contiguous() for v in (params[3 * l + 1], params[3 * l + 2], rm, rv)]
+        keep.append(vecs)
+        rec.W, rec.ldw, rec.C = lay.Wp.data_ptr(), lay.Wp.stride(0), lay.C
+        rec.gamma, rec.beta, rec.running_mean, rec.running_var = (v.data_ptr() for v in vecs)
+        rec.eps = eps
+    C = layers[-1].C
+    out_f32 = torch.empty((g.B, g.M, C), device=dev, dtype=torch.float32)
+    out_pm = torch.empty((g.B * g.M, C), device=dev, dtype=E16.dtype)
+    _call(_lib.omnipq_sa_infer, xyz_c, g.B, g.N, g.M, g.S, g.cin, g.kpad, g.inv_r, _p(xyz_c), _p(cen_c), _p(idx), _p(feat_pm), L,
+          ctypes.byref(recs), _p(out_f32), _p(out_pm))
+    return layers, (out_f32, out_pm)
+
+
 def _forward_layers(route, g, plan, xyz_c, cen_c, idx, feat_pm, params, bn_cfg, dev):
-    """-> (layers, X0, the relative coordinates of a "source" first layer, pool of the last GEMM)"""
+    """-> (layers, X0, the relative coordinates of a "source" first layer, pool of the last GEMM | the outputs of "chain")"""
     L = len(bn_cfg)
     layers, X0, Xrel, pool = [], None, None, None
+    if route.first == "chain":
+        layers, pool = _eval_chain(g, xyz_c, cen_c, idx, feat_pm, params, bn_cfg, dev)
+        return layers, None, None, pool
     if route.first != "source":
         X0 = _gather_rows(g, xyz_c, cen_c, idx, feat_pm, 8 if route.first == "xyz" else g.kpad, dev)
     X = X0
@@ -1250,6 +1306,8 @@ def _forward_layers(route, g, plan, xyz_c, cen_c, idx, feat_pm, params, bn_cfg, 
 def _pool_forward(route, g, last, pool, dev):
     """max-pool over every ball -> (out f32 [B][M][C], its 16-bit twin, the arg-max rows, the selected pre-BN values | None)"""
     B, M, S = g.B, g.M, g.S
+    if route.first == "chain":                  # pooled inside the stage's one launch; no arg-max: there is no backward
+        return pool[0], pool[1], None, None
     out_f32 = torch.empty((B, M, last.C), device=dev, dtype=torch.float32)
     out_pm = torch.empty((B * M, last.C), device=dev, dtype=E16.dtype)
     arg = torch.empty((B * M, last.C), device=dev, dtype=torch.uint8)
@@ -1515,7 +1573,8 @@ class FusedSAStage(torch.autograd.Function):
         route = stage_route(training, B, N, M, S, cin_raw, [params[3 * l].shape[0] for l in range(L)], features is not None,
                             ctx.needs_input_grad[0] or ctx.needs_input_grad[1],
                             features is not None and ctx.needs_input_grad[2], None if plan is None else plan.gs,
-                            plan is not None and plan.unit_src is not None)
+                            plan is not None and plan.unit_src is not None,
+                            no_grad=_NO_GRAD)
         _count_uses(route)
         if features is None:
             feat_pm = None
@@ -1663,8 +1722,13 @@ def run(module, xyz, new_xyz, features, group=None):
     global _SYNC
     _SYNC = all(bool(bn_syncs(_bn_of(layer)[1])) for layer in module.mlp_module)
     feat_pm = None if features is None else rows16_of(features, (features.shape[0], features.shape[2], features.shape[1]))
-    out, twin = FusedSAStage.apply(xyz, new_xyz, features, feat_pm, idx, float(module.radius),
-                                   bool(module.normalize_xyz), bool(module.training), bn_cfg, plan, csr, *params)
+    global _NO_GRAD
+    _NO_GRAD = not torch.is_grad_enabled()
+    try:
+        out, twin = FusedSAStage.apply(xyz, new_xyz, features, feat_pm, idx, float(module.radius),
+                                       bool(module.normalize_xyz), bool(module.training), bn_cfg, plan, csr, *params)
+    finally:
+        _NO_GRAD = False
     out.omnipq_rows16 = twin        # consumers that work on bf16 rows (next SA stage, FP modules) skip their cast
     return out
 
