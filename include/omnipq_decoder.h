@@ -59,6 +59,45 @@ int omnipq_add_to_e16(long long n, const void *a, int a_is_f32, const void *b, v
  * GEMMs' operand width: torch's .to(e16) + F.pad is three launches) */
 int omnipq_pad_rows_e16(long long n, int cin, int k, long long ldx, const void *x, int x_is_f32, void *out16, void *stream);
 
+/* ---- an inference per-point stack in ONE launch (csrc/rows_infer.hip) ----------------------------------------
+ * Replaces, for `model.eval()` under `torch.no_grad()`, what a stack of 1x1 convolutions with BatchNorm and ReLU on rows costs
+ * layer by layer (omnipq_pad_rows_e16, one NT GEMM, the launches that rebuild the BatchNorm's scale and shift from the running
+ * estimates, omnipq_bnrelu): 1 <= nlayers <= 3 linear layers from the input rows to the last layer's output, forward only.
+ * x: f32 or e16 [n][cin] with row pitch ldx (the arguments of omnipq_pad_rows_e16); the kernel widens a row to
+ * kpad = round_up(cin, 32) itself: ONE rounding to e16, zero columns, bit for bit what omnipq_pad_rows_e16 stores.
+ * `layers` is a HOST array of nlayers records (read during the call):
+ *   W              e16 [C][ldw], what omnipq_prep_weight leaves (zero rows up to C, the padded width; layer 0 over kpad
+ *                  columns, layer l > 0 over K = C of layer l - 1); ldw >= K, ldw % 8 == 0
+ *   bias           float[C] or NULL
+ *   gamma, beta, running_mean, running_var   float[C], all four (a BatchNorm layer, a ReLU follows) or all NULL;  eps: its
+ *   relu           without BatchNorm: a ReLU follows (the `act` kind at p = 0)
+ * omnipq_rows_infer_layer_record() reports the record's layout as THIS build compiled it, one line in the format of
+ * omnipq_abi_records() (omnipq_pointops.h).
+ * Per layer, z = W x accumulated in f32:
+ *   BatchNorm:   a = gamma / sqrt(running_var + eps),  b = beta - (running_mean - bias) a  (a bias that feeds a BatchNorm only
+ *                moves the mean),  y = relu(a z + b)
+ *   otherwise:   y = z + bias, relu(.) when `relu` is set
+ * a, b and the affine in f32.  A hidden y is rounded to e16 ONCE and stays in LDS; the last layer's y is rounded to e16 once
+ * and stored as out16 [n][C_last] (16-byte aligned).  Columns whose weight rows and bias are zero are exact zeros.  Rows past n
+ * are neither read nor written.  No atomics (bit-reproducible), no host read, no allocation; one launch with a static grid of
+ * persistent workgroups: graph-capturable.
+ * Shapes: every C % 32 == 0, 32 <= C <= 640; kpad <= 1024; and an LDS footprint the CU has.  A workgroup's tile is 64 rows where
+ * that fits the 160 KiB and 32 rows where it does not (1024 -> 512 -> 512): the one rule, a function of (kpad, widths) alone.
+ * omnipq_rows_infer_lds_bytes (host only) = the dynamic LDS bytes of the tile the launch will use, or -1 for a shape the kernel
+ * does not take; omnipq_rows_infer returns OMNIPQ_EINVAL in exactly those cases (and for a NULL required pointer or an
+ * incomplete BatchNorm quadruple), before anything is launched. */
+struct omnipq_rows_infer_layer {
+  const void *W;
+  int ldw, C;
+  const float *bias, *gamma, *beta, *running_mean, *running_var;
+  float eps;
+  int relu;
+};
+const char *omnipq_rows_infer_layer_record(void);
+long long omnipq_rows_infer_lds_bytes(int kpad, int nlayers, const int *widths);
+int omnipq_rows_infer(long long n, int cin, long long ldx, const void *x, int x_is_f32, int nlayers, const void *layers,
+                      void *out16, void *stream);
+
 /* Object prediction head after its output GEMM (models/pq_transformer.py:35-59 `decode_scores`, :86-89): row
  * r = (batch, proposal), y[r] = [objectness 2 | centre 3 | heading scores nh | heading residuals nh | size scores ns |
  * size residuals 3 ns | semantic scores ncls] in e16 (pitch ldy).  One launch writes the ten `end_points` tensors:

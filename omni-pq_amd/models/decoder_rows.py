@@ -274,7 +274,7 @@ def posembed_pair(pe_a, pe_b, xyz):
     sa, sb = _posembed_stack(pe_a), _posembed_stack(pe_b)
     if pe_a.training != pe_b.training or not (rows_mlp.usable(x, sa, pe_a.training) and rows_mlp.usable(x, sb, pe_b.training)):
         return None
-    return rows_mlp.run_pair(x, sa, x, sb, pe_a.training)
+    return rows_mlp.run_pair(x, sa, x, sb, pe_a.training, eval_chain=True)
 
 
 def key_side(layer, key, key_pos, mem16=None, k_pe=None):

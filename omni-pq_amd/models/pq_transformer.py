@@ -81,6 +81,11 @@ def conv1x1(x, conv):
 
 
 _JOINT_HEADS = True
+# The prediction heads' stacks on the inference chain (rows_mlp.EVAL_CHAIN).  Measured faster (profiles/
+# rows_infer_ab.txt: head pair) and shipped OFF: tests/test_gpu_decoder.py pins that the eval forward sends the heads' GEMMs out as
+# pair launches and that paired and single heads give the same bits, and the chain rounds a hidden activation once where the
+# stored route rounds it twice.  On: both head_stack and head_stack_pair opt in.
+_HEAD_EVAL_CHAIN = False
 
 
 def _rows_of(heads):
@@ -102,7 +107,7 @@ def head_stack(self, net, heads, net_rows=None, raw=False):
     if rows_mlp.usable(x, stack, self.training):
         # hand-written MFMA / BN kernels; with `raw` the consumer takes the kernels' zero-padded rows as they are
         _head_bias(self, stack, heads, w, raw, net.is_cuda)
-        y = rows_mlp.run(x, stack, self.training, padded=raw)
+        y = rows_mlp.run(x, stack, self.training, padded=raw, eval_chain=_HEAD_EVAL_CHAIN)
     else:
         x = rows_f32.bn_act(lin(x, self.conv1), self.bn1)
         x = rows_f32.bn_act(lin(x, self.conv2), self.bn2)
@@ -151,7 +156,7 @@ def head_stack_pair(head, quad_head, net, net_q, rows_a=None, rows_b=None):
             rows_mlp.usable(pa[0], pa[1], head.training) and rows_mlp.usable(pb[0], pb[1], quad_head.training):
         _head_bias(head, pa[1], head.heads(), pa[2], True, net.is_cuda)
         _head_bias(quad_head, pb[1], quad_head.heads(), pb[2], True, net_q.is_cuda)
-        return rows_mlp.run_pair(pa[0], pa[1], pb[0], pb[1], head.training, padded=True)
+        return rows_mlp.run_pair(pa[0], pa[1], pb[0], pb[1], head.training, padded=True, eval_chain=_HEAD_EVAL_CHAIN)
     return (head_stack(head, net, head.heads(), rows_a, raw=True),
             head_stack(quad_head, net_q, quad_head.heads(), rows_b, raw=True))
 
@@ -445,7 +450,7 @@ class PositionEmbeddingLearned(nn.Module):
                 xyz.omnipq_rows2d = x
         stack = [rows_mlp.Layer(head[0].weight, head[0].bias, head[1]), rows_mlp.Layer(head[3].weight, head[3].bias)]
         if rows_mlp.usable(x, stack, self.training):
-            x = rows_mlp.run(x, stack, self.training)
+            x = rows_mlp.run(x, stack, self.training, eval_chain=True)
         else:
             x = lin(rows_f32.bn_act(lin(x, head[0]), head[1]), head[3])
         return x.view(B, P, -1).transpose(1, 2)

@@ -135,12 +135,12 @@ class VotingModule(nn.Module):
                  rows_mlp.Layer(self.conv3.weight, self.conv3.bias)]
         if _FUSED_TAIL and normalized and vf == 1 and C <= 320 and rows_mlp.usable(x, stack, self.training) and \
                 seed_xyz.dtype == torch.float32 and seed_features.dtype in (torch.float32, E16.dtype):
-            net = rows_mlp.run(x, stack, self.training, padded=True)
+            net = rows_mlp.run(x, stack, self.training, padded=True, eval_chain=True)
             vote_xyz, vote_features, twin = VoteDecode.apply(net, seed_xyz, seed_features)
             vote_features.omnipq_rows16 = twin          # the vote aggregation reads bf16 rows: no cast there
             return vote_xyz, vote_features
         if rows_mlp.usable(x, stack, self.training):
-            net = rows_mlp.run(x, stack, self.training)
+            net = rows_mlp.run(x, stack, self.training, eval_chain=True)
         else:
             net = rows_f32.bn_act(_lin(x, self.conv1), self.bn1)
             net = rows_f32.bn_act(_lin(net, self.conv2), self.bn2)

@@ -128,6 +128,16 @@ def sa_infer_layer_struct():
     return _structure(name, fields)
 
 
+@functools.lru_cache(maxsize=None)
+def rows_infer_layer_struct():
+    """The `ctypes.Structure` of `struct omnipq_rows_infer_layer` (include/omnipq_decoder.h: the host record of one layer of
+    omnipq_rows_infer), from the record line the loaded library reports for it (omnipq_rows_infer_layer_record)."""
+    kind, name, *fields = _lib0.omnipq_rows_infer_layer_record().decode().split()
+    if (kind, name) != ("struct", "omnipq_rows_infer_layer"):
+        raise KeyError(f"pointnet2._ext: the loaded library ({_LIB_PATH}) reports `{kind} {name}` as its rows inference layer record")
+    return _structure(name, fields)
+
+
 class _Elem16(threading.local):
     """The element type the hand-written 16-bit kernels are running in: `E16.dtype`.  It follows torch.autocast:
     every entry into the hand-written path asks `E16.autocast()` -- True when CUDA autocast is on with a dtype a library

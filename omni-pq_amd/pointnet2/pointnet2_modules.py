@@ -229,7 +229,7 @@ def _rows_mlp(shared_mlp, x_rows):
     import rows_mlp
     stack = [rows_mlp.Layer(conv.weight, None, bn) for conv, bn in plan]
     if rows_mlp.usable(x_rows, stack, shared_mlp.training):
-        return rows_mlp.run(x_rows, stack, shared_mlp.training)        # hand-written MFMA / BN kernels
+        return rows_mlp.run(x_rows, stack, shared_mlp.training, eval_chain=True)        # hand-written MFMA / BN kernels
     import rows_f32
     for conv, bn in plan:
         # f32 mode: on a GPU the hand-written split-f32 GEMM and row BatchNorm (rows_f32), otherwise F.linear + torch's BN

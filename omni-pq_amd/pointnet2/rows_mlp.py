@@ -17,6 +17,8 @@ mean accounts for it (and its gradient is exactly zero).
 Used under `torch.autocast("cuda", dtype=torch.bfloat16)` (or float16: sa_fused.E16); otherwise callers keep PyTorch's f32 layers.
 """
 import collections
+import ctypes
+import functools
 import os
 import typing
 
@@ -68,10 +70,16 @@ def usable(x, layers, training):
     return True
 
 
-def run(x_rows, layers, training, padded=False):
+def run(x_rows, layers, training, padded=False, eval_chain=False):
     """x_rows (N, C_in) -> (N, C_out of the last layer), bf16.  padded: return the kernels' own (N, C_out rounded
     up to 32) buffer instead of the slice -- the extra columns are exact zeros (zero weight rows and bias), and a
-    consumer that hands back a gradient of that shape saves the stack a zero-fill and a copy."""
+    consumer that hands back a gradient of that shape saves the stack a zero-fill and a copy.  eval_chain: the caller opts
+    into the one-launch inference route (see EVAL_CHAIN) for the calls stack_route sends there; every other call is run as
+    without the keyword."""
+    if eval_chain:
+        route = _chain_route(x_rows, layers, training)
+        if route is not None:
+            return _infer(x_rows, layers, route, padded)
     spec, params = _spec_of(x_rows, layers, training, padded)
     return RowsMLP.apply(x_rows, spec, bool(training), *params)
 
@@ -92,11 +100,14 @@ def _kind(spec):
 class LayerRoute(typing.NamedTuple):
     kind: str         # "bn" | "act" | "plain"
     feed: str         # the GEMM's operand: "input" (layer 0: the prepared input rows) | "stored" (the layer below's output) | "yab"
-                      # (rebuilt from the layer below's pre-BN output and its scale / shift while the GEMM stages it)
+                      # (rebuilt from the layer below's pre-BN output and its scale / shift while the GEMM stages it) | "lds" (chain:
+                      # the layer below's output, which never leaves the workgroup)
     gemm: str         # "stats" (with the batch statistics of its output) | "relu_dropout" (ReLU + dropout in its epilogue) | "plain";
-                      # on a "yab" feed the affine entry point of the same kind
+                      # on a "yab" feed the affine entry point of the same kind | "chain" (every layer of the stack: ONE forward-only
+                      # launch, omnipq_rows_infer; the backward fields are "")
     finalize: str     # bn: where the layer's constants are derived: "consumer" (the prologue of the GEMM it feeds, nothing stored) |
-                      # "launch" (omnipq_bn_finalize_relu) | "running" (eval: from the running estimates, + omnipq_bnrelu); else ""
+                      # "launch" (omnipq_bn_finalize_relu) | "running" (eval: from the running estimates, + omnipq_bnrelu) | "folded"
+                      # (chain: from the running estimates inside the launch); else ""
     act: str          # act: ReLU + dropout in the GEMM's "epilogue" | the in-place "pass" (omnipq_relu_dropout); else ""
     dgrad: str        # the data gradient: "input" (layer 0: only if the input needs one) | "bnbwd" (with the BatchNorm-backward totals
                       # of the layer below) | "mask" (with the layer below's ReLU + dropout mask in its epilogue) | "plain"
@@ -113,9 +124,40 @@ class StackRoute(typing.NamedTuple):
     layers: tuple     # one LayerRoute per layer
 
 
-def stack_route(training, N, cin, layers):
+# The INFERENCE stack in one launch (csrc/rows_infer.hip, include/omnipq_decoder.h: omnipq_rows_infer).  In eval
+# mode BatchNorm is the affine a = gamma / sqrt(running_var + eps), b = beta - (running_mean - bias) a, known before the launch:
+# a tile of rows goes from the input to the last layer's output inside one workgroup, every hidden activation rounded once and
+# never stored.  Taken when nothing can ask for a backward -- eval mode, the call made under torch.no_grad() -- and only where
+# the caller opted in (run / run_pair: eval_chain=True).  EVAL_CHAIN = False restores the stored dataflow (one GEMM, the
+# rebuilt constants and omnipq_bnrelu per layer) everywhere.
+EVAL_CHAIN = True
+eval_chain_uses = 0
+_InferLayer = sa_fused._ext.rows_infer_layer_struct()
+
+
+@functools.lru_cache(maxsize=None)
+def _infer_lds_bytes(kpad, widths):
+    return int(_lib.omnipq_rows_infer_lds_bytes(kpad, len(widths), (ctypes.c_int * max(len(widths), 1))(*widths)))
+
+
+def eval_chain_ok(cin, widths):
+    """the shapes omnipq_rows_infer takes (one to three layers of 32 k <= 640 channels, an input of at most 1024 channels and an
+    LDS footprint the CU has): asked of the library, which refuses exactly the others.  widths: as the kernels hold them
+    (rounded up to 32, what omnipq_prep_weight leaves)."""
+    return cin > 0 and _infer_lds_bytes(_round_up(int(cin), 32), tuple(int(w) for w in widths)) > 0
+
+
+def stack_route(training, N, cin, layers, no_grad=False):
     """The route of a stack from shapes alone (no tensor, no launch; the switches are read now).  N rows of cin channels;
-    layers: per layer (output channels, kind)."""
+    layers: per layer (output channels, kind).  no_grad: the call is made under torch.no_grad() (read by the caller, outside
+    any autograd Function: inside Function.forward grad mode is always off) -- an eval stack with a hidden layer whose shape
+    the library takes is then ONE launch: gemm "chain", operands from the "input" / from "lds", BatchNorm "folded"."""
+    if no_grad and not training and EVAL_CHAIN and len(layers) >= 2 and \
+            all(cout % 32 == 0 for cout, kind in layers if kind == "bn") and \
+            eval_chain_ok(cin, tuple(_round_up(cout, 32) for cout, _ in layers)):
+        return StackRoute(False, tuple(LayerRoute(kind, "lds" if l else "input", "chain", "folded" if kind == "bn" else "",
+                                                  "epilogue" if kind == "act" else "", "", "", "")
+                                       for l, (_, kind) in enumerate(layers)))
     L, K, out = len(layers), _round_up(cin, 32), []
     for l, (cout, kind) in enumerate(layers):
         Cp = _round_up(cout, 32)
@@ -348,6 +390,58 @@ def _forward_program(ctx, lead, x, spec, training, params):
     return X if (spec.padded or last.Cp == last.C) else X[:, :last.C]
 
 
+# ---- the inference chain (route "chain": see EVAL_CHAIN) ----
+
+def _layer_kind(lay):
+    return "bn" if lay.bn is not None else "act" if lay.relu_dropout is not None else "plain"
+
+
+def _chain_route(x, layers, training):
+    """the stack's route if stack_route sends this call to the chain, else None.  Grad mode is read HERE."""
+    if training or torch.is_grad_enabled() or x.dim() != 2:
+        return None
+    route = stack_route(False, x.shape[0], x.shape[1], tuple((lay.weight.shape[0], _layer_kind(lay)) for lay in layers), no_grad=True)
+    return route if route.layers[0].gemm == "chain" else None
+
+
+def _infer(x, layers, route, padded):
+    """the whole stack as ONE launch (omnipq_rows_infer) -> (N, C_out) E16, or the kernel's own (N, C_out rounded up to 32)
+    buffer with padded"""
+    global eval_chain_uses
+    N, cin = x.shape
+    x = x.detach()
+    if x.dtype not in (torch.float32, E16.dtype) or x.stride(1) != 1:
+        x = x.to(E16.dtype).contiguous()
+    L = len(layers)
+    recs = (_InferLayer * L)()
+    keep = []                                   # what the records point to
+    K = _round_up(cin, 32)
+    for lay, r, rec in zip(layers, route.layers, recs):
+        nl = _new_layer(lay.weight, lay.bias, K, None, False)
+        if r.kind == "bn":
+            bn = lay.bn
+            vecs = [v.detach().float().contiguous() for v in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+            rec.gamma, rec.beta, rec.running_mean, rec.running_var = (v.data_ptr() for v in vecs)
+            rec.eps = float(bn.eps)
+            bias = None if lay.bias is None else lay.bias.detach().float().contiguous()
+        else:
+            vecs = []
+            # (no copy where the bias arrives f32 and padded, as the heads' joint bias does; a narrower one is padded per call,
+            # as on the stored route: a copy kept across calls would miss an optimizer that writes the parameter by pointer)
+            bias = None if lay.bias is None else _padded_bias(lay.bias, nl.Cp).contiguous()
+        rec.W, rec.ldw, rec.C = nl.Wp.data_ptr(), nl.Wp.stride(0), nl.Cp
+        rec.bias = 0 if bias is None else bias.data_ptr()
+        rec.relu = int(r.kind != "plain")
+        keep.append((nl.Wp, bias, vecs))
+        K = nl.Cp
+    Y = torch.empty((N, K), device=x.device, dtype=E16.dtype)
+    _call(_lib.omnipq_rows_infer, Y, N, cin, x.stride(0) if N > 1 else cin, _p(x), int(x.dtype == torch.float32), L,
+          ctypes.c_void_p(ctypes.addressof(recs)), _p(Y))
+    eval_chain_uses += 1
+    C = layers[-1].weight.shape[0]
+    return Y if (padded or K == C) else Y[:, :C]
+
+
 # ---- backward steps ----
 
 def _output_grad(g, last, N, padded):
@@ -526,9 +620,14 @@ def _spec_of(x_rows, layers, training, padded):
     return StackSpec(tuple(spec), bool(padded), sync), params
 
 
-def run_pair(xa, layers_a, xb, layers_b, training, padded=False):
+def run_pair(xa, layers_a, xb, layers_b, training, padded=False, eval_chain=False):
     """`run` on two independent stacks (e.g. the object and the quad head of a decoder stage: same shapes, different
-    weights) whose GEMMs go out pairwise in one launch each.  -> (ya, yb)"""
+    weights) whose GEMMs go out pairwise in one launch each.  -> (ya, yb).  eval_chain: see run(); a pair whose two stacks
+    both go to the chain is two chain launches."""
+    if eval_chain:
+        ra, rb = _chain_route(xa, layers_a, training), _chain_route(xb, layers_b, training)
+        if ra is not None and rb is not None:
+            return _infer(xa, layers_a, ra, padded), _infer(xb, layers_b, rb, padded)
     spec_a, params_a = _spec_of(xa, layers_a, training, padded)
     spec_b, params_b = _spec_of(xb, layers_b, training, padded)
     return RowsMLPPair.apply(xa, spec_a, xb, spec_b, bool(training), len(params_a), *params_a, *params_b)
