@@ -47,6 +47,31 @@ int omnipq_add_dropout_layernorm_bwd_partials(long long R, int C, const float *x
 int omnipq_layernorm_param_reduce(int n, const float *const *partials, const int *blocks, const int *channels,
                                   float *const *out, void *stream);
 
+/* The decoder layer's LAST LayerNorm next to the two prediction heads.  Rows are ordered (scene, token), p tokens per scene, the
+ * first p0 of them the object queries, R % p == 0, C % 8 == 0 (else OMNIPQ_EINVAL).  Arguments before `p` as in the functions
+ * above, which these are (the same kernels) with the head's place of a row worked out per row.
+ * Forward: the packed e16 values of out16 (out16 itself may be NULL) are also stored as the two heads' contiguous row blocks
+ *   obj16 (R / p * p0, C), quad16 (R / p * (p - p0), C) -- bit for bit omnipq_split_rows(out16); obj16 is required when p0 > 0,
+ *   quad16 when p0 < p.
+ * Backward: g_obj16 / g_quad16 (e16, each may be NULL = zero) are the gradients of those blocks.  Per element
+ *   m = the row's block gradient (+0 if absent); with g16: m = e16(float(m) + float(g16)), one add and one rounding;
+ *   t = g32; t += float(m); t += g16_pe -- what omnipq_merge_rows followed by the plain backward computes, dx, dy and the
+ *   parameter sums bit for bit. */
+int omnipq_add_dropout_layernorm_split(long long R, int C, const float *x, const void *y, const float *gamma,
+                                       const float *beta, float eps, float dropout_p, const unsigned long long *seed_ptr,
+                                       unsigned salt, float *out32, void *out16, const void *pe, void *out16_pe, float *mean,
+                                       float *rstd, int p, int p0, void *obj16, void *quad16, void *stream);
+int omnipq_add_dropout_layernorm_bwd_split(long long R, int C, const float *x, const void *y, const float *gamma,
+                                           float dropout_p, const unsigned long long *seed_ptr, unsigned salt,
+                                           const float *mean, const float *rstd, const float *g32, const void *g16,
+                                           const void *g16_pe, float *dx, void *dy, float *dgamma_dbeta, int p, int p0,
+                                           const void *g_obj16, const void *g_quad16, void *stream);
+int omnipq_add_dropout_layernorm_bwd_partials_split(long long R, int C, const float *x, const void *y, const float *gamma,
+                                                    float dropout_p, const unsigned long long *seed_ptr, unsigned salt,
+                                                    const float *mean, const float *rstd, const float *g32, const void *g16,
+                                                    const void *g16_pe, float *dx, void *dy, float *partials, int p, int p0,
+                                                    const void *g_obj16, const void *g_quad16, void *stream);
+
 /* h = dropout(relu(h)) in place on e16 [n]; backward: out = (h > 0) ? d / (1-p) : 0 (out may be d; h = the
  * forward's OUTPUT: positive exactly where the unit was active and kept). */
 int omnipq_relu_dropout(long long n, void *h, float dropout_p, const unsigned long long *seed_ptr, unsigned salt,
@@ -132,6 +157,13 @@ int omnipq_quad_decode_bwd(int R, int K, const void *y, int ldy, const float *no
 int omnipq_decode_pair(int Rh, int Kh, int nh, int ns, int ncls, const void *yh, int ldyh, const float *baseh,
                        const float *means, float hr_scale, void *const *outs_h, int Rq, int Kq, const void *yq, int ldyq,
                        const float *baseq, void *const *outs_q, float *norm, float *pos, void *stream);
+/* omnipq_decode_pair that also leaves pos as the operand the next layer's query position embedding starts from: pos16 e16
+ * [B][Kh + Kq][kpad] = [e16(x) e16(y) e16(z) | 0 ...], the f32 value just stored to pos rounded once, exact zeros behind it:
+ * bit for bit omnipq_pad_rows_e16(B * (Kh + Kq), 3, kpad, 3, pos, 1, ...).  pos and pos16 are both required, kpad >= 3. */
+int omnipq_decode_pair_pos16(int Rh, int Kh, int nh, int ns, int ncls, const void *yh, int ldyh, const float *baseh,
+                             const float *means, float hr_scale, void *const *outs_h, int Rq, int Kq, const void *yq,
+                             int ldyq, const float *baseq, void *const *outs_q, float *norm, float *pos, void *pos16,
+                             int kpad, void *stream);
 int omnipq_decode_pair_bwd(int Rh, int Kh, int nh, int ns, int ncls, const void *yh, int ldyh, const float *means,
                            float hr_scale, const void *const *gptr_h, const int *gstrides_h, const int *gn2_h,
                            const int *gbf_h, void *dyh, int lddyh, float *dbaseh, int Rq, int Kq, const void *yq, int ldyq,
@@ -174,6 +206,15 @@ int omnipq_add_n(int count, const void *const *src, long long n, int is_e16, voi
 int omnipq_split_rows(int b, int p, int p0, int c, const void *x16, void *obj16, void *quad16, void *stream);
 int omnipq_merge_rows(int b, int p, int p0, int c, const void *g_obj16, const void *g_quad16, const void *g_joint16,
                       void *out16, void *stream);
+
+/* The decoder's entry, the inverse of omnipq_split_rows: the heads' row blocks obj16 (b * p0, c), quad16 (b * (p - p0), c) ->
+ * the joint rows (b, p, c) as f32 (out32: exact widening) and as their e16 twin (out16: a copy), one launch.  And its gradient:
+ * e16(g32 + float(g16)) of the two outputs' gradients (one f32 add, one rounding; either may be NULL: the other alone, g16 then
+ * passing as it is) written as the two blocks' gradients d_obj16 / d_quad16.  c % 8 == 0, 16-byte aligned. */
+int omnipq_merge_rows_f32(int b, int p, int p0, int c, const void *obj16, const void *quad16, float *out32, void *out16,
+                          void *stream);
+int omnipq_split_rows_sum(int b, int p, int p0, int c, const float *g32, const void *g16, void *d_obj16, void *d_quad16,
+                          void *stream);
 
 #ifdef __cplusplus
 }

@@ -41,7 +41,17 @@ struct LnArgs {
   float eps, keep_inv;
   unsigned thresh, salt;
   const unsigned long long *seed_ptr;
+  int p, p0;                          // > 0: rows are (scene, token) with p tokens per scene, the first p0 the object queries
 };
+
+// the row's place in its head's contiguous row block (obj: tokens [0, p0), quad: the rest), or null if that block is absent
+template <typename T>
+__device__ __forceinline__ T *split_row(const LnArgs &g, long long row, T *obj, T *quad) {
+  const long long b = row / g.p;
+  const int t = (int)(row - b * g.p);
+  if (t < g.p0) return obj ? obj + (b * g.p0 + t) * g.C : nullptr;
+  return quad ? quad + (b * (g.p - g.p0) + (t - g.p0)) * g.C : nullptr;
+}
 
 // r = x + dropout(y) for this lane's chunks of one row
 __device__ __forceinline__ void load_residual(const LnArgs &g, long long row, int lane, unsigned seed,
@@ -75,7 +85,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(LnArgs g, const float *__re
                                                     const float *__restrict__ beta, float *__restrict__ out32,
                                                     e16_t *__restrict__ out16, const e16_t *__restrict__ pe,
                                                     e16_t *__restrict__ out16_pe, float *__restrict__ mean,
-                                                    float *__restrict__ rstd) {
+                                                    float *__restrict__ rstd, e16_t *__restrict__ obj16,
+                                                    e16_t *__restrict__ quad16) {
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
   const int nch = g.C >> 2;
   const unsigned seed = g.thresh ? dec_seed(g.seed_ptr, g.salt) : 0u;
@@ -102,6 +113,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(LnArgs g, const float *__re
       mean[row] = mu;
       rstd[row] = rs;
     }
+    e16_t *const head16 = g.p ? split_row(g, row, obj16, quad16) : nullptr;     // what split_rows_kernel would copy out of out16
 #pragma unroll
     for (int i = 0; i < LN_MAXCH; ++i) {
       const int c = lane + 64 * i;
@@ -114,7 +126,9 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(LnArgs g, const float *__re
         o[2] = (r[i][2] - mu) * rs * gv.z + bv.z;
         o[3] = (r[i][3] - mu) * rs * gv.w + bv.w;
         if (out32) *reinterpret_cast<float4 *>(out32 + row * g.C + c * 4) = make_float4(o[0], o[1], o[2], o[3]);
-        if (out16) *reinterpret_cast<uint2 *>(out16 + row * g.C + c * 4) = pack4(o);
+        const uint2 o16 = pack4(o);
+        if (out16) *reinterpret_cast<uint2 *>(out16 + row * g.C + c * 4) = o16;
+        if (head16) *reinterpret_cast<uint2 *>(head16 + c * 4) = o16;
         if (out16_pe) {
           float p[4];
           unpack4(*reinterpret_cast<const uint2 *>(pe + row * g.C + c * 4), p);
@@ -133,7 +147,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnArgs g, const float *__re
                                                     const float *__restrict__ g32, const e16_t *__restrict__ g16,
                                                     const e16_t *__restrict__ g16_pe, float *__restrict__ dx,
                                                     e16_t *__restrict__ dy, float *__restrict__ dgb,
-                                                    float *__restrict__ part) {
+                                                    float *__restrict__ part, const e16_t *__restrict__ g_obj16,
+                                                    const e16_t *__restrict__ g_quad16) {
   extern __shared__ float dyn[];                            // [4 waves][dgamma | dbeta][C]
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
   const int nch = g.C >> 2;
@@ -156,6 +171,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnArgs g, const float *__re
     float r[LN_MAXCH][4], go[LN_MAXCH][4];
     load_residual(g, row, lane, seed, x, y, r);
     const float mu = mean[row], rs = rstd[row];
+    const e16_t *const gh16 = g.p ? split_row(g, row, g_obj16, g_quad16) : nullptr;
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < LN_MAXCH; ++i) {
@@ -166,7 +182,21 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnArgs g, const float *__re
           const float4 v = *reinterpret_cast<const float4 *>(g32 + row * g.C + c * 4);
           t[0] = v.x, t[1] = v.y, t[2] = v.z, t[3] = v.w;
         }
-        if (g16) {
+        if (g.p) {
+          // the heads' gradient of this row (+0 where its block is absent) and the joint one meet as merge_rows_kernel adds
+          // them -- one f32 add, ONE rounding to e16 -- and the rounded sum enters t where g16 does: bit for bit the two launches
+          uint2 m = make_uint2(0u, 0u);
+          if (gh16) m = *reinterpret_cast<const uint2 *>(gh16 + c * 4);
+          if (g16) {
+            const uint2 w = *reinterpret_cast<const uint2 *>(g16 + row * g.C + c * 4);
+            m.x = pack_e16x2(e16_lo(m.x) + e16_lo(w.x), e16_hi(m.x) + e16_hi(w.x));
+            m.y = pack_e16x2(e16_lo(m.y) + e16_lo(w.y), e16_hi(m.y) + e16_hi(w.y));
+          }
+          float u[4];
+          unpack4(m, u);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) t[e] += u[e];
+        } else if (g16) {
           float u[4];
           unpack4(*reinterpret_cast<const uint2 *>(g16 + row * g.C + c * 4), u);
 #pragma unroll
@@ -343,24 +373,52 @@ static int flat_grid(long long n4) {
 
 }  // namespace omnipq
 
+namespace omnipq {
+// the split variants' geometry: p tokens per scene, the first p0 of them object queries; whole scenes; rows the heads' row
+// GEMMs take (C % 8, the rule of omnipq_split_rows)
+static bool split_geom_ok(long long R, int C, int p, int p0) {
+  return p > 0 && p0 >= 0 && p0 <= p && (R % p) == 0 && (C % 8) == 0;
+}
+}  // namespace omnipq
+
+// p == 0: no split (obj16 / quad16 unused)
+static int ln_fwd_impl(long long R, int C, const float *x, const void *y, const float *gamma, const float *beta, float eps,
+                       float dropout_p, const unsigned long long *seed_ptr, unsigned salt, float *out32, void *out16,
+                       const void *pe, void *out16_pe, float *mean, float *rstd, int p, int p0, void *obj16, void *quad16,
+                       void *stream) {
+  using namespace omnipq;
+  if (R < 0 || C <= 0 || (C % 4) || C > 64 * 4 * LN_MAXCH) return OMNIPQ_EINVAL;
+  if (R == 0) return OMNIPQ_OK;
+  if (!x || !gamma || !beta || !mean || !rstd || (!pe != !out16_pe)) return OMNIPQ_EINVAL;
+  if (p && ((p0 > 0 && !obj16) || (p0 < p && !quad16))) return OMNIPQ_EINVAL;
+  if (R * C >= (1ll << 32)) return OMNIPQ_ETOOLARGE;
+  LnArgs g{R, C, eps, 1.f, 0u, salt, seed_ptr, p, p0};
+  const int rc = drop_params(y ? dropout_p : 0.f, seed_ptr, &g.thresh, &g.keep_inv);
+  if (rc) return rc;
+  ln_fwd_kernel<<<rows_grid(R), 256, 0, (hipStream_t)stream>>>(g, x, (const e16_t *)y, gamma, beta, out32,
+                                                              (e16_t *)out16, (const e16_t *)pe, (e16_t *)out16_pe,
+                                                              mean, rstd, (e16_t *)obj16, (e16_t *)quad16);
+  OMNIPQ_LAUNCH_CHECK();
+  return OMNIPQ_OK;
+}
+
 extern "C" int omnipq_add_dropout_layernorm(long long R, int C, const float *x, const void *y, const float *gamma,
                                             const float *beta, float eps, float dropout_p,
                                             const unsigned long long *seed_ptr, unsigned salt, float *out32,
                                             void *out16, const void *pe, void *out16_pe, float *mean, float *rstd,
                                             void *stream) {
-  using namespace omnipq;
-  if (R < 0 || C <= 0 || (C % 4) || C > 64 * 4 * LN_MAXCH) return OMNIPQ_EINVAL;
-  if (R == 0) return OMNIPQ_OK;
-  if (!x || !gamma || !beta || !mean || !rstd || (!pe != !out16_pe)) return OMNIPQ_EINVAL;
-  if (R * C >= (1ll << 32)) return OMNIPQ_ETOOLARGE;
-  LnArgs g{R, C, eps, 1.f, 0u, salt, seed_ptr};
-  const int rc = drop_params(y ? dropout_p : 0.f, seed_ptr, &g.thresh, &g.keep_inv);
-  if (rc) return rc;
-  ln_fwd_kernel<<<rows_grid(R), 256, 0, (hipStream_t)stream>>>(g, x, (const e16_t *)y, gamma, beta, out32,
-                                                              (e16_t *)out16, (const e16_t *)pe, (e16_t *)out16_pe,
-                                                              mean, rstd);
-  OMNIPQ_LAUNCH_CHECK();
-  return OMNIPQ_OK;
+  return ln_fwd_impl(R, C, x, y, gamma, beta, eps, dropout_p, seed_ptr, salt, out32, out16, pe, out16_pe, mean, rstd, 0, 0,
+                     nullptr, nullptr, stream);
+}
+
+extern "C" int omnipq_add_dropout_layernorm_split(long long R, int C, const float *x, const void *y, const float *gamma,
+                                                  const float *beta, float eps, float dropout_p,
+                                                  const unsigned long long *seed_ptr, unsigned salt, float *out32,
+                                                  void *out16, const void *pe, void *out16_pe, float *mean, float *rstd,
+                                                  int p, int p0, void *obj16, void *quad16, void *stream) {
+  if (!omnipq::split_geom_ok(R, C, p, p0)) return OMNIPQ_EINVAL;
+  return ln_fwd_impl(R, C, x, y, gamma, beta, eps, dropout_p, seed_ptr, salt, out32, out16, pe, out16_pe, mean, rstd, p, p0,
+                     obj16, quad16, stream);
 }
 
 namespace omnipq {
@@ -378,19 +436,20 @@ extern "C" long long omnipq_add_dropout_layernorm_bwd_blocks(long long R) {
 static int ln_bwd_impl(long long R, int C, const float *x, const void *y, const float *gamma, float dropout_p,
                        const unsigned long long *seed_ptr, unsigned salt, const float *mean, const float *rstd,
                        const float *g32, const void *g16, const void *g16_pe, float *dx, void *dy,
-                       float *dgamma_dbeta, float *partials, void *stream) {
+                       float *dgamma_dbeta, float *partials, int p, int p0, const void *g_obj16, const void *g_quad16,
+                       void *stream) {
   using namespace omnipq;
   if (R < 0 || C <= 0 || (C % 4) || C > 64 * 4 * LN_MAXCH) return OMNIPQ_EINVAL;
   if (R == 0) return OMNIPQ_OK;
   if (!x || !gamma || !mean || !rstd || !dx || (!dgamma_dbeta == !partials) || (!y != !dy)) return OMNIPQ_EINVAL;
   if (R * C >= (1ll << 32)) return OMNIPQ_ETOOLARGE;
-  LnArgs g{R, C, 0.f, 1.f, 0u, salt, seed_ptr};
+  LnArgs g{R, C, 0.f, 1.f, 0u, salt, seed_ptr, p, p0};
   const int rc = drop_params(y ? dropout_p : 0.f, seed_ptr, &g.thresh, &g.keep_inv);
   if (rc) return rc;
   const long long blocks = ln_bwd_blocks(R);
   ln_bwd_kernel<<<(int)blocks, 256, sizeof(float) * 8 * C, (hipStream_t)stream>>>(
       g, x, (const e16_t *)y, gamma, mean, rstd, g32, (const e16_t *)g16, (const e16_t *)g16_pe, dx, (e16_t *)dy,
-      dgamma_dbeta, partials);
+      dgamma_dbeta, partials, (const e16_t *)g_obj16, (const e16_t *)g_quad16);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }
@@ -401,7 +460,18 @@ extern "C" int omnipq_add_dropout_layernorm_bwd(long long R, int C, const float 
                                                 const void *g16, const void *g16_pe, float *dx, void *dy,
                                                 float *dgamma_dbeta, void *stream) {
   return ln_bwd_impl(R, C, x, y, gamma, dropout_p, seed_ptr, salt, mean, rstd, g32, g16, g16_pe, dx, dy, dgamma_dbeta,
-                     nullptr, stream);
+                     nullptr, 0, 0, nullptr, nullptr, stream);
+}
+
+extern "C" int omnipq_add_dropout_layernorm_bwd_split(long long R, int C, const float *x, const void *y, const float *gamma,
+                                                      float dropout_p, const unsigned long long *seed_ptr, unsigned salt,
+                                                      const float *mean, const float *rstd, const float *g32,
+                                                      const void *g16, const void *g16_pe, float *dx, void *dy,
+                                                      float *dgamma_dbeta, int p, int p0, const void *g_obj16,
+                                                      const void *g_quad16, void *stream) {
+  if (!omnipq::split_geom_ok(R, C, p, p0)) return OMNIPQ_EINVAL;
+  return ln_bwd_impl(R, C, x, y, gamma, dropout_p, seed_ptr, salt, mean, rstd, g32, g16, g16_pe, dx, dy, dgamma_dbeta,
+                     nullptr, p, p0, g_obj16, g_quad16, stream);
 }
 
 extern "C" int omnipq_add_dropout_layernorm_bwd_partials(long long R, int C, const float *x, const void *y,
@@ -411,7 +481,19 @@ extern "C" int omnipq_add_dropout_layernorm_bwd_partials(long long R, int C, con
                                                          const void *g16, const void *g16_pe, float *dx, void *dy,
                                                          float *partials, void *stream) {
   return ln_bwd_impl(R, C, x, y, gamma, dropout_p, seed_ptr, salt, mean, rstd, g32, g16, g16_pe, dx, dy, nullptr,
-                     partials, stream);
+                     partials, 0, 0, nullptr, nullptr, stream);
+}
+
+extern "C" int omnipq_add_dropout_layernorm_bwd_partials_split(long long R, int C, const float *x, const void *y,
+                                                               const float *gamma, float dropout_p,
+                                                               const unsigned long long *seed_ptr, unsigned salt,
+                                                               const float *mean, const float *rstd, const float *g32,
+                                                               const void *g16, const void *g16_pe, float *dx, void *dy,
+                                                               float *partials, int p, int p0, const void *g_obj16,
+                                                               const void *g_quad16, void *stream) {
+  if (!omnipq::split_geom_ok(R, C, p, p0)) return OMNIPQ_EINVAL;
+  return ln_bwd_impl(R, C, x, y, gamma, dropout_p, seed_ptr, salt, mean, rstd, g32, g16, g16_pe, dx, dy, nullptr,
+                     partials, p, p0, g_obj16, g_quad16, stream);
 }
 
 extern "C" int omnipq_layernorm_param_reduce(int n, const float *const *partials, const int *blocks, const int *channels,
@@ -621,7 +703,75 @@ __global__ __launch_bounds__(256) void merge_rows_kernel(long long chunks, int p
   }
   out[q] = v;
 }
+
+// The decoder's entry, the inverse of the split: the two heads' row blocks -> the joint rows, as the f32 residual stream (exact
+// widening) and its e16 twin (a copy) in one launch; and the way back: e16(g32 + float(g16)) -- one f32 add, one rounding --
+// of the joint rows' two gradients, written as the two blocks' gradients.
+__global__ __launch_bounds__(256) void join_rows_kernel(long long chunks, int p, int p0, int c8, const uint4 *__restrict__ obj,
+                                                       const uint4 *__restrict__ quad, float4 *__restrict__ out32,
+                                                       uint4 *__restrict__ out16) {
+  const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (q >= chunks) return;
+  const long long row = q / c8;
+  const int piece = (int)(q - row * c8);
+  const long long b = row / p;
+  const int t = (int)(row - b * p);
+  const uint4 v = t < p0 ? obj[(b * p0 + t) * c8 + piece] : quad[(b * (p - p0) + (t - p0)) * c8 + piece];
+  out32[2 * q] = make_float4(e16_lo(v.x), e16_hi(v.x), e16_lo(v.y), e16_hi(v.y));
+  out32[2 * q + 1] = make_float4(e16_lo(v.z), e16_hi(v.z), e16_lo(v.w), e16_hi(v.w));
+  out16[q] = v;
+}
+
+__global__ __launch_bounds__(256) void split_rows_sum_kernel(long long chunks, int p, int p0, int c8,
+                                                            const float4 *__restrict__ g32, const uint4 *__restrict__ g16,
+                                                            uint4 *__restrict__ d_obj, uint4 *__restrict__ d_quad) {
+  const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (q >= chunks) return;
+  const long long row = q / c8;
+  const int piece = (int)(q - row * c8);
+  const long long b = row / p;
+  const int t = (int)(row - b * p);
+  float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+  if (g32) lo = g32[2 * q], hi = g32[2 * q + 1];
+  if (g16) {
+    const uint4 w = g16[q];
+    lo.x += e16_lo(w.x), lo.y += e16_hi(w.x), lo.z += e16_lo(w.y), lo.w += e16_hi(w.y);
+    hi.x += e16_lo(w.z), hi.y += e16_hi(w.z), hi.z += e16_lo(w.w), hi.w += e16_hi(w.w);
+  }
+  uint4 v = make_uint4(pack_e16x2(lo.x, lo.y), pack_e16x2(lo.z, lo.w), pack_e16x2(hi.x, hi.y), pack_e16x2(hi.z, hi.w));
+  if (g16 && !g32) v = g16[q];                       // the twin's gradient alone passes as it is (no +0 added to a -0)
+  if (t < p0)
+    d_obj[(b * p0 + t) * c8 + piece] = v;
+  else
+    d_quad[(b * (p - p0) + (t - p0)) * c8 + piece] = v;
+}
 }  // namespace omnipq
+
+extern "C" int omnipq_merge_rows_f32(int b, int p, int p0, int c, const void *obj16, const void *quad16, float *out32,
+                                     void *out16, void *stream) {
+  using namespace omnipq;
+  if (b < 0 || p <= 0 || p0 < 0 || p0 > p || c <= 0 || (c % 8)) return OMNIPQ_EINVAL;
+  const long long chunks = (long long)b * p * (c / 8);
+  if (chunks == 0) return OMNIPQ_OK;
+  if (!out32 || !out16 || (p0 > 0 && !obj16) || (p0 < p && !quad16)) return OMNIPQ_EINVAL;
+  join_rows_kernel<<<(unsigned)((chunks + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+      chunks, p, p0, c / 8, (const uint4 *)obj16, (const uint4 *)quad16, (float4 *)out32, (uint4 *)out16);
+  OMNIPQ_LAUNCH_CHECK();
+  return OMNIPQ_OK;
+}
+
+extern "C" int omnipq_split_rows_sum(int b, int p, int p0, int c, const float *g32, const void *g16, void *d_obj16,
+                                     void *d_quad16, void *stream) {
+  using namespace omnipq;
+  if (b < 0 || p <= 0 || p0 < 0 || p0 > p || c <= 0 || (c % 8)) return OMNIPQ_EINVAL;
+  const long long chunks = (long long)b * p * (c / 8);
+  if (chunks == 0) return OMNIPQ_OK;
+  if ((p0 > 0 && !d_obj16) || (p0 < p && !d_quad16)) return OMNIPQ_EINVAL;
+  split_rows_sum_kernel<<<(unsigned)((chunks + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+      chunks, p, p0, c / 8, (const float4 *)g32, (const uint4 *)g16, (uint4 *)d_obj16, (uint4 *)d_quad16);
+  OMNIPQ_LAUNCH_CHECK();
+  return OMNIPQ_OK;
+}
 
 extern "C" int omnipq_split_rows(int b, int p, int p0, int c, const void *x16, void *obj16, void *quad16, void *stream) {
   using namespace omnipq;

@@ -40,14 +40,25 @@ __device__ __forceinline__ int head_argmax(const e16_t *scores, int ns) {
 
 // optional second copy of a head's centres inside the joint query positions of the next decoder layer:
 // pos[b][off + k][0..2], b = r / K, k = r % K, P positions per scene (reference models/pq_transformer.py:245 concatenates)
+// pos16 (optional, with pos): the same rows as the operand the next layer's position embedding starts from, e16 [.][kpad] =
+// [x y z | 0 ...]: the f32 value just stored rounded once, exact zeros behind it -- what pad_rows_bf16_kernel<true> makes of pos.
+// The thread that stores coordinate c also zeroes the pad columns 3 + c, 6 + c, ...
 struct PosOut {
   float *pos;
   int K, P, off;
+  e16_t *pos16;
+  int kpad;
 };
 __device__ __forceinline__ void pos_store(const PosOut &po, int r, int c, float v) {
   if (!po.pos) return;
   const int b = r / po.K, k = r - b * po.K;
-  po.pos[((size_t)b * po.P + po.off + k) * 3 + c] = v;
+  const size_t row = (size_t)b * po.P + po.off + k;
+  po.pos[row * 3 + c] = v;
+  if (po.pos16) {
+    e16_t *o = po.pos16 + row * po.kpad;
+    o[c] = (e16_t)v;
+    for (int z = 3 + c; z < po.kpad; z += 3) o[z] = (e16_t)0.f;
+  }
 }
 
 // one row per 128 threads: r = the row (clamped by the caller; `live` false for a half-block past the end), t = 0..127,
@@ -427,10 +438,10 @@ extern "C" int omnipq_head_decode_bwd(int R, int K, int nh, int ns, int ncls, co
 // omnipq_head_decode + omnipq_quad_decode in one launch (arguments as there; head: Rh rows, quad: Rq rows).
 // pos (optional): f32 [B][Kh + Kq][3], receives the two heads' centres side by side per scene (the next decoder layer's
 // query positions, reference models/pq_transformer.py:245); Kh / Kq = proposals per scene, Rh / Kh == Rq / Kq scenes.
-extern "C" int omnipq_decode_pair(int Rh, int Kh, int nh, int ns, int ncls, const void *yh, int ldyh, const float *baseh,
-                                  const float *means, float hr_scale, void *const *outs_h, int Rq, int Kq, const void *yq,
-                                  int ldyq, const float *baseq, void *const *outs_q, float *norm, float *pos,
-                                  void *stream) {
+static int decode_pair_impl(int Rh, int Kh, int nh, int ns, int ncls, const void *yh, int ldyh, const float *baseh,
+                            const float *means, float hr_scale, void *const *outs_h, int Rq, int Kq, const void *yq,
+                            int ldyq, const float *baseq, void *const *outs_q, float *norm, float *pos, void *pos16,
+                            int kpad, void *stream) {
   using namespace omnipq;
   if (Rh <= 0 || Rq <= 0 || nh < 1 || ns < 1 || ncls < 1 || Kh < 1 || Kq < 1 || (Rh % Kh) || (Rq % Kq)) return OMNIPQ_EINVAL;
   if (pos && Rh / Kh != Rq / Kq) return OMNIPQ_EINVAL;
@@ -444,12 +455,32 @@ extern "C" int omnipq_decode_pair(int Rh, int Kh, int nh, int ns, int ncls, cons
              (e16_t *)outs_h[5], (e16_t *)outs_h[6], (float *)outs_h[7], (float *)outs_h[8], (e16_t *)outs_h[9]};
   QuadOut qo{(e16_t *)outs_q[0], (float *)outs_q[1], (e16_t *)outs_q[2], (e16_t *)outs_q[3]};
   PairHead h{Rh, Kh, nh, ns, ncls, ldyh, 0, (const e16_t *)yh, baseh, means, hr_scale, nullptr, nullptr, 0,
-             PosOut{pos, Kh, Kh + Kq, 0}};
-  PairQuad q{Rq, Kq, ldyq, 0, (const e16_t *)yq, baseq, norm, nullptr, nullptr, 0, PosOut{pos, Kq, Kh + Kq, Kh}};
+             PosOut{pos, Kh, Kh + Kq, 0, (e16_t *)pos16, kpad}};
+  PairQuad q{Rq, Kq, ldyq, 0, (const e16_t *)yq, baseq, norm, nullptr, nullptr, 0,
+             PosOut{pos, Kq, Kh + Kq, Kh, (e16_t *)pos16, kpad}};
   const int blocks = (Rh + 1) / 2 + (Rq + kQuadRows - 1) / kQuadRows;
   decode_pair_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(h, ho, q, qo);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
+}
+
+extern "C" int omnipq_decode_pair(int Rh, int Kh, int nh, int ns, int ncls, const void *yh, int ldyh, const float *baseh,
+                                  const float *means, float hr_scale, void *const *outs_h, int Rq, int Kq, const void *yq,
+                                  int ldyq, const float *baseq, void *const *outs_q, float *norm, float *pos,
+                                  void *stream) {
+  return decode_pair_impl(Rh, Kh, nh, ns, ncls, yh, ldyh, baseh, means, hr_scale, outs_h, Rq, Kq, yq, ldyq, baseq, outs_q,
+                          norm, pos, nullptr, 0, stream);
+}
+
+// ... and with pos16: e16 [B][Kh + Kq][kpad], the rows of pos as the next layer's position embedding takes them (bit for bit
+// omnipq_pad_rows_e16(n, 3, kpad, 3, pos, 1, ...)); pos and pos16 both required, kpad >= 3.
+extern "C" int omnipq_decode_pair_pos16(int Rh, int Kh, int nh, int ns, int ncls, const void *yh, int ldyh,
+                                        const float *baseh, const float *means, float hr_scale, void *const *outs_h, int Rq,
+                                        int Kq, const void *yq, int ldyq, const float *baseq, void *const *outs_q,
+                                        float *norm, float *pos, void *pos16, int kpad, void *stream) {
+  if (!pos || !pos16 || kpad < 3) return OMNIPQ_EINVAL;
+  return decode_pair_impl(Rh, Kh, nh, ns, ncls, yh, ldyh, baseh, means, hr_scale, outs_h, Rq, Kq, yq, ldyq, baseq, outs_q,
+                          norm, pos, pos16, kpad, stream);
 }
 
 // omnipq_head_decode_bwd + omnipq_quad_decode_bwd in one launch (arguments as there).  accumulate: bit 0 -> dbaseh +=,

@@ -160,17 +160,81 @@ class SplitRows(torch.autograd.Function):
         return out, None
 
 
+class JoinRows(torch.autograd.Function):
+    """The inverse of SplitRows at the decoder's entry: object rows (B*P0, C) and quad rows (B*(P-P0), C), 16-bit -> the joint
+    rows (B*P, C) as the f32 residual stream (exact widening) and as its 16-bit twin, in one launch (a concatenation of two
+    channel-major views, a transposing copy and a cast before); backward: bf16(g32 + float(g16)) of the two outputs'
+    gradients -- one f32 add, one rounding, the arithmetic of the cast, the f32 accumulation and the cast it replaces --
+    written as the two blocks' gradients in one launch."""
+
+    @staticmethod
+    def forward(ctx, obj, quad, B):
+        ctx.e16 = E16.dtype
+        C = obj.shape[1]
+        p0, pq = obj.shape[0] // B, quad.shape[0] // B
+        out32 = torch.empty((B * (p0 + pq), C), device=obj.device, dtype=torch.float32)
+        out16 = torch.empty((B * (p0 + pq), C), device=obj.device, dtype=E16.dtype)
+        _call(_lib.omnipq_merge_rows_f32, obj, B, p0 + pq, p0, C, _p(obj), _p(quad), _p(out32), _p(out16))
+        ctx.geom = (B, p0 + pq, p0, C)
+        ctx.set_materialize_grads(False)
+        return out32, out16
+
+    @staticmethod
+    def backward(ctx, g32, g16):
+        E16.select(ctx.e16)
+        if g32 is None and g16 is None:
+            return None, None, None
+        B, P, p0, C = ctx.geom
+        g32 = None if g32 is None else g32.float().contiguous()
+        g16 = None if g16 is None else g16.to(E16.dtype).contiguous()
+        dev = (g32 if g32 is not None else g16).device
+        d_obj = torch.empty((B * p0, C), device=dev, dtype=E16.dtype)
+        d_quad = torch.empty((B * (P - p0), C), device=dev, dtype=E16.dtype)
+        _call(_lib.omnipq_split_rows_sum, d_obj, B, P, p0, C, _p(g32), _p(g16), _p(d_obj), _p(d_quad))
+        return d_obj, d_quad, None
+
+
+def join_queries(qa, qb, layers):
+    """The two query projections, (B, C, P0) and (B, C, Pq) 16-bit views of position-major rows, as the decoder's joint query
+    (B, C, P0 + Pq): an f32 view of joint rows with their 16-bit twin attached (`omnipq_rows16`), so that the first layer
+    starts like every other one (run: a free `_rows(query).float()`, the 16-bit position-embedding add).  None where that does
+    not apply (the caller concatenates)."""
+    if not (qa.is_cuda and qa.dim() == 3 and qb.dim() == 3 and qa.shape[:2] == qb.shape[:2] and qa.shape[2] and qb.shape[2]):
+        return None
+    B, C = qa.shape[0], qa.shape[1]
+    ra, rb = qa.transpose(1, 2), qb.transpose(1, 2)
+    if not (qa.dtype == qb.dtype == E16.dtype and ra.is_contiguous() and rb.is_contiguous() and C % 8 == 0 and
+            ra.data_ptr() % 16 == 0 and rb.data_ptr() % 16 == 0 and all(usable(layer, qa, qa) for layer in layers)):
+        return None
+    x32, x16 = JoinRows.apply(ra.reshape(-1, C), rb.reshape(-1, C), B)
+    P = qa.shape[2] + qb.shape[2]
+    out = x32.view(B, P, C).transpose(1, 2)
+    out.omnipq_rows16 = x16.view(B, P, C)
+    return out
+
+
 def split_usable(x16):
     return x16 is not None and x16.is_cuda and x16.dtype == E16.dtype and x16.is_contiguous() and \
         x16.dim() == 3 and x16.shape[2] % 8 == 0 and x16.data_ptr() % 16 == 0
 
 
+# The layer's third LayerNorm writes the two prediction heads' row blocks itself and its backward reads their gradients
+# (omnipq_add_dropout_layernorm_split / _bwd_split): no omnipq_split_rows / omnipq_merge_rows launch between a decoder layer and
+# its heads.  False: SplitRows after the layer, as before -- the same bits either way.
+LN_SPLIT = True
+
+
+def ln_split_usable(R, C, p, p0):
+    return LN_SPLIT and p > 0 and 0 <= p0 <= p and R % p == 0 and C % 8 == 0
+
+
 class AddDropoutLayerNorm(torch.autograd.Function):
-    """(x f32, y bf16 | None, gamma, beta, eps, p, pe bf16 | None, want32, want16)
-    -> (LayerNorm(x + dropout(y)) as f32 | None, as bf16 | None, bf16(that + pe) | None)"""
+    """(x f32, y bf16 | None, gamma, beta, eps, p, pe bf16 | None, want32, want16[, split = (tokens per scene, object tokens)])
+    -> (LayerNorm(x + dropout(y)) as f32 | None, as bf16 | None, bf16(that + pe) | None); with `split` two more: the bf16
+    rows of the object tokens (B * p0, C) and of the quad tokens (B * (p - p0), C), what SplitRows makes of the second"""
 
     @staticmethod
-    def forward(ctx, x, y, gamma, beta, eps, p, pe, want32, want16):
+    def forward(ctx, x, y, gamma, beta, eps, p, pe, want32, want16, split=None):
         ctx.e16 = E16.dtype
         R, C = x.shape
         dev = x.device
@@ -183,18 +247,29 @@ class AddDropoutLayerNorm(torch.autograd.Function):
         seed = dropout_state.seed(dev) if drop else None
         salt = dropout_state.next_salt() if drop else 0
         g32, b32 = gamma.detach().float(), beta.detach().float()
-        _call(_lib.omnipq_add_dropout_layernorm, x, R, C, _p(x), _p(y), _p(g32), _p(b32),
-              eps, p if drop else 0.0, _p(seed), salt, _p(out32), _p(out16), _p(pe),
-              _p(out_pe), _p(mean), _p(rstd))
+        ctx.split = split
+        if split is not None:
+            tokens, n_obj = split
+            obj = torch.empty((R // tokens * n_obj, C), device=dev, dtype=E16.dtype)
+            quad = torch.empty((R // tokens * (tokens - n_obj), C), device=dev, dtype=E16.dtype)
+            _call(_lib.omnipq_add_dropout_layernorm_split, x, R, C, _p(x), _p(y), _p(g32), _p(b32),
+                  eps, p if drop else 0.0, _p(seed), salt, _p(out32), _p(out16), _p(pe),
+                  _p(out_pe), _p(mean), _p(rstd), tokens, n_obj, _p(obj), _p(quad))
+        else:
+            _call(_lib.omnipq_add_dropout_layernorm, x, R, C, _p(x), _p(y), _p(g32), _p(b32),
+                  eps, p if drop else 0.0, _p(seed), salt, _p(out32), _p(out16), _p(pe),
+                  _p(out_pe), _p(mean), _p(rstd))
         ctx.save_for_backward(x, y, g32, mean, rstd)
         ctx.set_materialize_grads(False)        # unused outputs (f32 / bf16 / bf16 + pe) arrive as None, not as zero tensors
         ctx.cfg = (p if drop else 0.0, seed, salt, pe is not None)
         both = isinstance(gamma, torch.nn.Parameter) and isinstance(beta, torch.nn.Parameter)
         ctx.params = (gamma, beta) if both and gamma.requires_grad and beta.requires_grad else None
+        if split is not None:
+            return out32, out16, out_pe, obj, quad
         return out32, out16, out_pe
 
     @staticmethod
-    def backward(ctx, g32, g16, gpe):
+    def backward(ctx, g32, g16, gpe, g_obj=None, g_quad=None):
         E16.select(ctx.e16)
         x, y, gamma, mean, rstd = ctx.saved_tensors
         p, seed, salt, has_pe = ctx.cfg
@@ -204,20 +279,29 @@ class AddDropoutLayerNorm(torch.autograd.Function):
         gpe = gpe.contiguous() if gpe is not None else None
         dx = torch.empty_like(x)
         dy = torch.empty_like(y) if y is not None else None
+        if ctx.split is not None:
+            # the heads' gradients meet the joint rows' inside the kernel, rounded as omnipq_merge_rows rounds their sum
+            g_obj, g_quad = (None if g is None else g.to(E16.dtype).contiguous() for g in (g_obj, g_quad))
+            g16 = g16.to(E16.dtype) if g16 is not None else None
+            tail = (*ctx.split, _p(g_obj), _p(g_quad))
+            bwd, bwd_partials = _lib.omnipq_add_dropout_layernorm_bwd_split, _lib.omnipq_add_dropout_layernorm_bwd_partials_split
+        else:
+            tail = ()
+            bwd, bwd_partials = _lib.omnipq_add_dropout_layernorm_bwd, _lib.omnipq_add_dropout_layernorm_bwd_partials
         dfr = sa_fused.deferred_wgrads.active
         if dfr is not None and ctx.params is not None:
             # nothing reads dgamma / dbeta before the optimizer: leave per-workgroup partial sums and let the block sum
             # those of all LayerNorms in one launch (the atomics of the immediate path were most of this kernel's time)
             blocks = int(_lib.omnipq_add_dropout_layernorm_bwd_blocks(R))
             part = torch.empty((blocks, 2 * C), device=x.device, dtype=torch.float32)
-            _call(_lib.omnipq_add_dropout_layernorm_bwd_partials, x, R, C, _p(x), _p(y), _p(gamma),
-                  p, _p(seed), salt, _p(mean), _p(rstd), _p(g32), _p(g16), _p(gpe), _p(dx), _p(dy), _p(part))
+            _call(bwd_partials, x, R, C, _p(x), _p(y), _p(gamma),
+                  p, _p(seed), salt, _p(mean), _p(rstd), _p(g32), _p(g16), _p(gpe), _p(dx), _p(dy), _p(part), *tail)
             dfr.add_layernorm(part, blocks, C, *ctx.params)
-            return dx, dy, None, None, None, None, (gpe if has_pe else None), None, None
+            return (dx, dy, None, None, None, None, (gpe if has_pe else None)) + (None, None, None)
         dgb = zeros_f32(2 * C, x.device)
-        _call(_lib.omnipq_add_dropout_layernorm_bwd, x, R, C, _p(x), _p(y), _p(gamma),
-              p, _p(seed), salt, _p(mean), _p(rstd), _p(g32), _p(g16), _p(gpe), _p(dx), _p(dy), _p(dgb))
-        return dx, dy, dgb[:C], dgb[C:], None, None, (gpe if has_pe else None), None, None
+        _call(bwd, x, R, C, _p(x), _p(y), _p(gamma),
+              p, _p(seed), salt, _p(mean), _p(rstd), _p(g32), _p(g16), _p(gpe), _p(dx), _p(dy), _p(dgb), *tail)
+        return (dx, dy, dgb[:C], dgb[C:], None, None, (gpe if has_pe else None)) + (None, None, None)
 
 
 def usable(layer, query, key):
@@ -341,9 +425,11 @@ def join_key_sides(device, done=None):
         torch.cuda.current_stream(device).wait_stream(_side_stream(device))
 
 
-def run(layer, query, key, query_pos, key_pos, kv=None):
+def run(layer, query, key, query_pos, key_pos, kv=None, split_at=None):
     """query (B,C,Pq), key (B,C,Pk), query_pos (B,Pq,3), key_pos (B,Pk,3) -> (B,C,Pq) f32 (a view of rows).
-    kv: the layer's precomputed key side (`precompute_key_sides`), or None to compute it in line."""
+    kv: the layer's precomputed key side (`precompute_key_sides`), or None to compute it in line.
+    split_at: the number of object queries among the Pq -- the last LayerNorm then also writes the two prediction heads' row
+    blocks, attached to the result as `omnipq_rows_split` = (object rows (B, split_at, C), quad rows (B, Pq - split_at, C))."""
     B, C, Pq = query.shape
     Pk = key.shape[2]
     training = layer.training
@@ -392,8 +478,17 @@ def run(layer, query, key, query_pos, key_pos, kv=None):
     # feed-forward (:216-219)
     y = rows_mlp.run(x16, [rows_mlp.Layer(layer.linear1.weight, layer.linear1.bias, relu_dropout=pdrop(layer.dropout)),
                            rows_mlp.Layer(layer.linear2.weight, layer.linear2.bias)], training)
-    x32, x16, _ = AddDropoutLayerNorm.apply(x32, y, layer.norm3.weight, layer.norm3.bias, float(layer.norm3.eps),
-                                            pdrop(layer.dropout3), None, True, True)
+    blocks = None
+    if split_at is not None and ln_split_usable(B * Pq, C, Pq, split_at):
+        x32, x16, _, obj, quad = AddDropoutLayerNorm.apply(x32, y, layer.norm3.weight, layer.norm3.bias,
+                                                           float(layer.norm3.eps), pdrop(layer.dropout3), None, True, True,
+                                                           (Pq, split_at))
+        blocks = (obj.view(B, split_at, C), quad.view(B, Pq - split_at, C))
+    else:
+        x32, x16, _ = AddDropoutLayerNorm.apply(x32, y, layer.norm3.weight, layer.norm3.bias, float(layer.norm3.eps),
+                                                pdrop(layer.dropout3), None, True, True)
     out = x32.view(B, Pq, C).transpose(1, 2)
     out.omnipq_rows16 = x16.view(B, Pq, C)      # the same values in bf16, for consumers that run on bf16 rows
+    if blocks is not None:
+        out.omnipq_rows_split = blocks
     return out

@@ -328,7 +328,7 @@ class DecodePair(torch.autograd.Function):
     sink (XyzGradSink | None): the gradient of `base_h` is added into the sink instead of being returned."""
 
     @staticmethod
-    def forward(ctx, yh, base_h, means, nh, ns, ncls, yq, base_q, sink=None, want_pos=False):
+    def forward(ctx, yh, base_h, means, nh, ns, ncls, yq, base_q, sink=None, want_pos=False, pos_kpad=0):
         ctx.e16 = E16.dtype
         import ctypes
         B, K, _ = base_h.shape
@@ -349,12 +349,17 @@ class DecodePair(torch.autograd.Function):
                   torch.empty((Bq, Kq, 2), **bf)]
         norm = torch.empty(1, **f32)
         pos = torch.empty((B, K + Kq, 3), **f32) if (want_pos and B == Bq) else None
+        # pos_kpad: the positions also as the 16-bit rows, padded to pos_kpad columns, that the next layer's position
+        # embedding starts from (a sixteenth output, without gradient)
+        pos16 = torch.empty((B * (K + Kq), pos_kpad), **bf) if (pos is not None and pos_kpad >= 3) else None
         scale = float(np.float32(np.pi / nh))
-        sa_fused._call(sa_fused._lib.omnipq_decode_pair, yh, B * K, K, nh, ns, ncls, sa_fused._p(yh), yh.stride(0),
-                       sa_fused._p(bh), sa_fused._p(means), scale,
-                       (ctypes.c_void_p * 10)(*[o.data_ptr() for o in outs_h]), Bq * Kq, Kq, sa_fused._p(yq), yq.stride(0),
-                       sa_fused._p(bq), (ctypes.c_void_p * 4)(*[o.data_ptr() for o in outs_q]), sa_fused._p(norm),
-                       sa_fused._p(pos))
+        args = (B * K, K, nh, ns, ncls, sa_fused._p(yh), yh.stride(0), sa_fused._p(bh), sa_fused._p(means), scale,
+                (ctypes.c_void_p * 10)(*[o.data_ptr() for o in outs_h]), Bq * Kq, Kq, sa_fused._p(yq), yq.stride(0),
+                sa_fused._p(bq), (ctypes.c_void_p * 4)(*[o.data_ptr() for o in outs_q]), sa_fused._p(norm), sa_fused._p(pos))
+        if pos16 is None:
+            sa_fused._call(sa_fused._lib.omnipq_decode_pair, yh, *args)
+        else:
+            sa_fused._call(sa_fused._lib.omnipq_decode_pair_pos16, yh, *args, sa_fused._p(pos16), pos_kpad)
         ctx.save_for_backward(yh, means, yq, norm)
         ctx.geom = (B, K, nh, ns, ncls, scale, Bq, Kq)
         ctx.sink = sink
@@ -363,6 +368,9 @@ class DecodePair(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         if pos is None:
             return tuple(outs_h) + tuple(outs_q)
+        if pos16 is not None:
+            ctx.mark_non_differentiable(pos, pos16)
+            return tuple(outs_h) + tuple(outs_q) + (pos, pos16)
         ctx.mark_non_differentiable(pos)
         return tuple(outs_h) + tuple(outs_q) + (pos,)
 
@@ -395,7 +403,7 @@ class DecodePair(torch.autograd.Function):
                        sa_fused._p(dbh), Bq * Kq, Kq, sa_fused._p(yq), yq.stride(0), sa_fused._p(norm),
                        (ctypes.c_void_p * 4)(*pq), (ctypes.c_int * 16)(*sq), (ctypes.c_int * 4)(*fq), sa_fused._p(dyq),
                        dyq.stride(0), sa_fused._p(dbq), acc)
-        return dyh, (None if sink is not None else dbh), None, None, None, None, dyq, dbq, None, None
+        return dyh, (None if sink is not None else dbh), None, None, None, None, dyq, dbq, None, None, None
 
 
 _HEAD_KEYS = ("objectness_scores", "center", "heading_scores", "heading_residuals_normalized", "heading_residuals",
@@ -404,6 +412,15 @@ _QUAD_KEYS = ("quad_scores", "quad_center", "normal_vector", "quad_size")
 _PAIR_DECODE = True        # module switches, toggled by tests/test_gpu_decoder.py to compare with the separate launches
 _XYZ_SINK = True
 _PAIR_STACKS = True
+# The pair decode also writes the next layer's query positions as the padded 16-bit rows its position embedding starts from
+# (omnipq_decode_pair_pos16), attached to the positions the way rows_mlp._input_rows looks for a prepared operand: no
+# omnipq_pad_rows_e16 launch on the query side.  False: rows_mlp converts them, as before -- the same bits.
+_POS_ROWS16 = True
+# The decoder's entry: the two query projections become the first layer's joint f32 rows and their 16-bit twin in one launch
+# (decoder_rows.JoinRows; backward one launch too) instead of torch.cat of two channel-major views, a transposing copy and a
+# cast, and the casts and the f32 add of their way back.  False: the concatenation, as before -- the same bits.
+_JOIN_ROWS = True
+_POS_KPAD = 32            # three coordinates at the row GEMMs' operand width (rows_mlp: cin rounded up to 32)
 
 
 def predict_pair(head, quad_head, net, net_q, base_xyz, base_xyz_q, end_points, prefix, rows=None, rows_q=None,
@@ -423,10 +440,16 @@ def predict_pair(head, quad_head, net, net_q, base_xyz, base_xyz_q, end_points, 
         center_q, _, end_points = quad_head.finish(yq, net_q, base_xyz_q, end_points, prefix)
         return center, center_q, end_points, None
     outs = DecodePair.apply(yh, base_xyz, head._mean_sizes(net.device), head.num_heading_bin, head.num_size_cluster,
-                            head.num_class, yq, base_xyz_q, sink, want_pos)
+                            head.num_class, yq, base_xyz_q, sink, want_pos, _POS_KPAD if (want_pos and _POS_ROWS16) else 0)
     for key, val in zip(_HEAD_KEYS + _QUAD_KEYS, outs):
         end_points[f'{prefix}{key}'] = val
-    return outs[1], outs[11], end_points, (outs[14] if len(outs) > 14 else None)
+    pos = outs[14] if len(outs) > 14 else None
+    if len(outs) > 15:
+        # (here, not inside DecodePair.forward: attributes set there need not survive `apply`)
+        rows2d = pos.view(-1, 3)
+        rows2d.omnipq_rows_in = (rows2d._version, outs[15])
+        pos.omnipq_rows2d = rows2d
+    return outs[1], outs[11], end_points, pos
 
 
 class PositionEmbeddingLearned(nn.Module):
@@ -721,8 +744,14 @@ class PQ_Transformer(nn.Module):
         base_xyz = center.detach()
         base_xyz_q = center_q.detach()
 
-        query_joint = torch.cat(conv1x1_pair(cluster_feature, self.decoder_query_proj,
-                                             quad_feature, self.quad_decoder_query_proj), -1)
+        query_obj, query_quad = conv1x1_pair(cluster_feature, self.decoder_query_proj,
+                                             quad_feature, self.quad_decoder_query_proj)
+        query_joint = None
+        if _JOIN_ROWS and transformer_mod._USE_ROWS:
+            # the two projections' rows -> the first layer's f32 residual rows and their 16-bit twin, one launch each way
+            query_joint = decoder_rows.join_queries(query_obj, query_quad, self.decoder)
+        if query_joint is None:
+            query_joint = torch.cat((query_obj, query_quad), -1)
         if key is None:
             key = conv1x1(sf_key, self.decoder_key_proj)
 
@@ -738,12 +767,17 @@ class PQ_Transformer(nn.Module):
             # (the pair decode of the stage before leaves both centres side by side already)
             query_pos_joint = pos_joint if pos_joint is not None else torch.cat([base_xyz, base_xyz_q], 1)
             pos_joint = None
-            query_joint = self.decoder[i](query_joint, key, query_pos_joint, key_pos, key_sides[i])
+            query_joint = self.decoder[i](query_joint, key, query_pos_joint, key_pos, key_sides[i], self.num_proposal)
             n_obj, n_quad = self.num_proposal, query_joint.shape[2] - self.num_proposal
             query, query_q = torch.split(query_joint, [n_obj, n_quad], dim=2)     # one cat in backward
             rows16 = getattr(query_joint, 'omnipq_rows16', None)          # (B, P, C) bf16 twin from the row-major decoder
             rows_obj = rows_quad = None
-            if decoder_rows.split_usable(rows16):
+            blocks = getattr(query_joint, 'omnipq_rows_split', None)
+            if blocks is not None:
+                # the layer's last LayerNorm wrote the two heads' row blocks itself, and its backward takes their gradients
+                # next to the joint rows' (decoder_rows.LN_SPLIT)
+                rows_obj, rows_quad = blocks
+            elif decoder_rows.split_usable(rows16):
                 # the two heads' inputs as contiguous row blocks, and the joint rows' three gradients (two heads, next
                 # layer) merged by one launch in backward
                 rows_obj, rows_quad, alias = decoder_rows.SplitRows.apply(rows16, n_obj)
