@@ -169,6 +169,20 @@ int omnipq_decode_pair_bwd(int Rh, int Kh, int nh, int ns, int ncls, const void 
                            const int *gbf_h, void *dyh, int lddyh, float *dbaseh, int Rq, int Kq, const void *yq, int ldyq,
                            const float *norm, const void *const *gptr_q, const int *gstrides_q, const int *gbf_q, void *dyq,
                            int lddyq, float *dbaseq, int accumulate, void *stream);
+/* omnipq_decode_pair_bwd of nstage stages of the same shapes, four stages per launch (no stage's decode feeds another stage
+ * with gradient, so all their output gradients exist together).  yh, means, dyh, dbaseh, yq, norm, dyq, dbaseq: arrays of
+ * nstage pointers, in the order the single calls would be issued; gptr_h / gbf_h: nstage x 10, gstrides_h: nstage x 40,
+ * gptr_q / gbf_q: nstage x 4, gstrides_q: nstage x 16, gn2_h: 10 (common).  dbaseh / dbaseq (the arrays or single entries
+ * may be NULL) receive each stage's own base-position gradients.  sink (may be NULL; with it every dbaseh entry must be NULL):
+ * f32 [Rh][3], receives the SUM of the stages' object base-position gradients, formed by one thread per element in stage
+ * order -- bit for bit what the single calls leave when they add into one buffer; accumulate != 0: added to its contents. */
+int omnipq_decode_pair_group_bwd(int nstage, int Rh, int Kh, int nh, int ns, int ncls, const void *const *yh, int ldyh,
+                                 const float *const *means, float hr_scale, const void *const *gptr_h,
+                                 const int *gstrides_h, const int *gn2_h, const int *gbf_h, void *const *dyh, int lddyh,
+                                 float *const *dbaseh, int Rq, int Kq, const void *const *yq, int ldyq,
+                                 const float *const *norm, const void *const *gptr_q, const int *gstrides_q,
+                                 const int *gbf_q, void *const *dyq, int lddyq, float *const *dbaseq, float *sink,
+                                 int accumulate, void *stream);
 
 /* The tail of the voting module and the normalisation that follows it (models/voting_module.py:55-63,
  * models/pq_transformer.py:216-217; vote_factor 1) in one launch, their gradient in another.

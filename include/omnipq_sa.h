@@ -60,9 +60,17 @@ int omnipq_sa_scatter_csr(int b, int n, int m, int s, int cin, int kpad, float i
  * number of pair launches made so far).  The two problems must be independent and nothing else may be enqueued on the
  * stream between hold and flush.  Used for the object / quad head stacks of a decoder stage (reference
  * models/pq_transformer.py:62-121: same shapes, different weights), each of whose GEMMs alone covers less than one
- * workgroup per CU. */
+ * workgroup per CU.
+ * Groups.  omnipq_pair_group(n), 1 <= n <= 14, opens a group on the calling thread (whatever was held goes out first): while
+ * it is open omnipq_pair_hold() arms again after every launch held, up to n - 1 launches of one kind are held, and the n-th
+ * sends all n out as ONE grid (the plain and the BatchNorm-backward data-gradient GEMMs on the K-resident small-tile path, and
+ * omnipq_bn_bwd_apply_fused; the other variants go out singly, in order).  A launch of the kind that was not armed closes the
+ * group with what is held; a launch of another kind or on another stream, or omnipq_pair_flush(), sends everything held
+ * out singly in issue order and closes the group.  Without an open group everything above is unchanged.  Used for the backward
+ * of the prediction heads of all decoder stages at once. */
 void omnipq_pair_hold(void);
-int omnipq_pair_held(void);       /* 1 while a launch is being held back */
+int omnipq_pair_group(int n);
+int omnipq_pair_held(void);       /* the number of launches being held back */
 long long omnipq_pair_flush(void);
 
 /* C[M][N] (e16) = A[M][K] * B[N][K]^T on MFMA (K % 32 == 0, N % 8 == 0). */

@@ -204,45 +204,63 @@ struct PlanScope {
   RowPlan saved_;
 };
 
-// Pair launches (include/omnipq_sa.h: omnipq_pair_hold): one launch of the calling thread held back for a partner of the
-// same kind.  `blob` holds the kernel-specific problem record, `single` sends it out on its own.
+// Pair and group launches (include/omnipq_sa.h: omnipq_pair_hold, omnipq_pair_group): launches of the calling thread held
+// back for partners of the same kind.  `blob[i]` holds the kernel-specific problem record of the i-th launch held, `single`
+// sends one of them out on its own.  Without an open group the protocol is "hold one, pair with the next"; a group of n
+// holds up to n - 1 and sends all n as one grid.
+constexpr int kHeldMax = 14;                    // launches per group (the heads of seven stages: 14 stacks)
+constexpr int kHeldBlob = 320;
 struct HeldLaunch {
-  bool armed = false, full = false;
-  int key = 0;                                  // kind of launch: only equal keys pair
+  bool armed = false;                           // the next launch is to be held
+  int group = 0;                                // launches the open group waits for (0: no group open, a pair)
+  int held = 0;                                 // launches held back
+  int key = 0;                                  // kind of the held launches: only equal keys go out together
   hipStream_t stream = nullptr;
-  void (*single)(const HeldLaunch &) = nullptr;
-  alignas(16) unsigned char blob[768];
+  void (*single)(const void *blob, hipStream_t stream) = nullptr;
+  alignas(16) unsigned char blob[kHeldMax][kHeldBlob];
 };
 HeldLaunch &held_launch();                      // gemm_bf16.hip; thread-local
-void count_pair_launch();
+void count_pair_launch();                       // one per grid that carried more than one launch
 constexpr int kHeldApplyKey = 1000;             // bn_bwd_apply_fused (the GEMM variants use small keys)
 
-// The protocol every pairable launcher follows.  Returns true when the launch was consumed (held, or sent out as a pair by
-// `pair(first, second)`); false: the caller launches `prob` on its own (after a held stranger was sent out).
-template <typename P, typename PairFn>
-static inline bool hold_or_pair(const P &prob, int key, hipStream_t stream, void (*single)(const HeldLaunch &), PairFn pair) {
-  static_assert(sizeof(P) <= sizeof(HeldLaunch::blob), "problem record too large");
+// Sends everything held out singly, in issue order; disarms and closes the group.
+static inline void release_held(HeldLaunch &h) {
+  const int n = h.held;
+  h.held = h.group = 0;
+  h.armed = false;
+  for (int i = 0; i < n; ++i) h.single(h.blob[i], h.stream);
+}
+
+// The protocol every pairable launcher follows.  Returns true when the launch was consumed (held, or sent out with the held
+// ones by `send(records, n)`, n >= 2, which returns the number of shared grids it took: one, or zero where the kind has no
+// n-way kernel and the launches went out singly); false: the caller launches `prob` on its own (after held strangers
+// were sent out).  A launch joins the held ones of its kind; they go out together when the group is complete or when the
+// joining launch was not armed (the last of its round).
+template <typename P, typename SendFn>
+static inline bool hold_or_pair(const P &prob, int key, hipStream_t stream, void (*single)(const void *, hipStream_t),
+                                SendFn send) {
+  static_assert(sizeof(P) <= kHeldBlob && alignof(P) <= 16, "problem record too large");
   HeldLaunch &h = held_launch();
-  if (h.armed && !h.full) {
-    h.full = true;
-    h.key = key;
-    h.stream = stream;
-    h.single = single;
-    __builtin_memcpy(h.blob, &prob, sizeof(P));
-    return true;
+  if (h.held && (h.key != key || h.stream != stream)) {
+    release_held(h);
+    return false;
   }
-  if (h.full) {
-    h.full = h.armed = false;
-    if (h.key == key && h.stream == stream) {
-      P first;
-      __builtin_memcpy(&first, h.blob, sizeof(P));
-      pair(first, prob);
-      count_pair_launch();
-      return true;
-    }
-    h.single(h);
-  }
-  return false;
+  if (!h.held && !h.armed) return false;
+  const bool armed = h.armed;
+  h.armed = false;
+  h.key = key;
+  h.stream = stream;
+  h.single = single;
+  __builtin_memcpy(h.blob[h.held++], &prob, sizeof(P));
+  const int want = h.group ? h.group : 2;
+  if (h.held < want && armed) return true;
+  const int n = h.held;
+  h.held = h.group = 0;
+  if (n == 1) return false;                     // a group of one: nothing to share a grid with
+  P recs[kHeldMax];
+  for (int i = 0; i < n; ++i) __builtin_memcpy(&recs[i], h.blob[i], sizeof(P));
+  for (int grids = send(recs, n); grids > 0; --grids) count_pair_launch();
+  return true;
 }
 
 }  // namespace omnipq

@@ -1000,6 +1000,40 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_pair_kernel(SmallProblem p0, S
                                                  XyzGen(), id - n0);
 }
 
+// Up to kHeldMax independent small problems of the same variant in one grid (omnipq_pair_group: the backward of the
+// prediction heads of all decoder stages, whose output gradients exist together).  Every workgroup finds its problem by
+// binary search over the first-workgroup offsets (multiples of 8, as gemm_nt_grid rounds every problem: the workgroup-to-tile
+// mapping of the body stays what it is in a launch of its own) and runs the same program as the single and the pair launch.
+// The records travel by value in the kernel arguments and carry no AffineIn, which would not fit fourteen times.
+struct NtGroupItem {
+  GemmArgs g;
+  const e16_t *A, *B;
+  void *C;
+  const float *bias;
+  void *stats;
+  BnBwdEpilogue bn;
+  int wg_begin;
+};
+struct NtGroupArgs {
+  int n;
+  NtGroupItem item[kHeldMax];
+};
+static_assert(sizeof(NtGroupArgs) <= 4096, "kernel arguments are limited to 4 KB");
+
+template <int STATS, bool AFF>
+__global__ __launch_bounds__(256, 2) void gemm_nt_group_kernel(NtGroupArgs a) {
+  static_assert(!AFF, "the group record carries no AffineIn");
+  const int id = (int)blockIdx.x;
+  int lo = 0, hi = a.n - 1;          // last item with wg_begin <= id
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (a.item[mid].wg_begin <= id) lo = mid; else hi = mid - 1;
+  }
+  const NtGroupItem &it = a.item[lo];
+  gemm_nt_body<false, STATS, AFF, 64, 0, true>(it.g, it.A, it.B, it.C, it.bias, it.stats, it.bn, AffineIn(), PoolOut(),
+                                               XyzGen(), id - it.wg_begin);
+}
+
 #ifdef OMNIPQ_NT_TRACE
 }  // namespace omnipq
 extern "C" int omnipq_debug_read_nt_trace(long long *host_out) {
@@ -1186,7 +1220,7 @@ static bool gemm_nt_kres(int K) { return K <= omnipq::kResMaxSteps * omnipq::GBK
 // omnipq_pair_hold(): the NEXT small-tile GEMM this thread issues is held back instead of launched; the one after it, if it
 // is the same variant on the same stream, goes out with it as one grid (gemm_nt_pair_kernel); anything else (another
 // variant, omnipq_pair_flush()) sends the held one out on its own first.  The caller guarantees the two are independent
-// and issues nothing else in between.
+// and issues nothing else in between.  omnipq_pair_group(n): the same for n launches, up to n - 1 held (common.h: hold_or_pair).
 static thread_local omnipq::HeldLaunch t_held;
 static std::atomic<long long> t_pairs_launched{0};      // written by the forward thread and the autograd thread
 namespace omnipq {
@@ -1198,13 +1232,9 @@ struct HeldSmallBlob {
   int lds;
 };
 
-// sends a held launch out on its own
+// sends held launches out on their own
 static void flush_held() {
-  omnipq::HeldLaunch &h = t_held;
-  if (h.full) {
-    h.full = h.armed = false;
-    h.single(h);
-  }
+  if (t_held.held) omnipq::release_held(t_held);
 }
 
 template <int STATS, bool AFF>
@@ -1218,10 +1248,46 @@ static void launch_small_single(const omnipq::SmallProblem &p, int lds, hipStrea
 }
 
 template <int STATS, bool AFF>
-static void held_single(const omnipq::HeldLaunch &h) {
+static void held_single(const void *blob, hipStream_t stream) {
   HeldSmallBlob q;
-  __builtin_memcpy(&q, h.blob, sizeof(q));
-  launch_small_single<STATS, AFF>(q.p, q.lds, h.stream);
+  __builtin_memcpy(&q, blob, sizeof(q));
+  launch_small_single<STATS, AFF>(q.p, q.lds, stream);
+}
+
+// held launches of one variant as one grid: two through the pair kernel; more through the group kernel, which exists for the
+// variants the heads' backward issues (plain and BatchNorm-backward data gradients) -- the others go out singly, in order
+template <int STATS, bool AFF>
+static int launch_small_group(const HeldSmallBlob *q, int n, hipStream_t stream) {
+  using namespace omnipq;
+  if (n == 2) {
+    auto kern = gemm_nt_pair_kernel<STATS, AFF>;
+    static const hipError_t prepared = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)prepared;
+    const int n0 = (int)gemm_nt_grid(q[0].p.g).x, n1 = (int)gemm_nt_grid(q[1].p.g).x;
+    kern<<<dim3(n0 + n1), 256, q[0].lds > q[1].lds ? q[0].lds : q[1].lds, stream>>>(q[0].p, q[1].p, n0);
+    return 1;
+  }
+  if constexpr (!AFF && (STATS == 0 || STATS == 3)) {
+    auto kern = gemm_nt_group_kernel<STATS, AFF>;
+    static const hipError_t prepared = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)prepared;
+    NtGroupArgs a;
+    a.n = n;
+    int wgs = 0, lds = 0;
+    for (int i = 0; i < n; ++i) {
+      const SmallProblem &p = q[i].p;
+      a.item[i] = NtGroupItem{p.g, p.A, p.B, p.C, p.bias, p.stats, p.bn, wgs};
+      wgs += (int)gemm_nt_grid(p.g).x;
+      lds = q[i].lds > lds ? q[i].lds : lds;
+    }
+    kern<<<dim3(wgs), 256, lds, stream>>>(a);
+    return 1;
+  } else {
+    for (int i = 0; i < n; ++i) launch_small_single<STATS, AFF>(q[i].p, q[i].lds, stream);
+    return 0;
+  }
 }
 
 template <int STATS, bool AFF>
@@ -1234,15 +1300,7 @@ static void launch_small(const omnipq::GemmArgs &g, const void *A, const void *B
     const HeldSmallBlob q{SmallProblem{g, (const e16_t *)A, (const e16_t *)B, C, bias, stats, bn, aff}, lds};
     const bool consumed = hold_or_pair(
         q, STATS * 2 + (AFF ? 1 : 0), (hipStream_t)stream, &held_single<STATS, AFF>,
-        [&](const HeldSmallBlob &first, const HeldSmallBlob &second) {
-          auto kern = gemm_nt_pair_kernel<STATS, AFF>;
-          static const hipError_t prepared = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-          (void)prepared;
-          const int n0 = (int)gemm_nt_grid(first.p.g).x, n1 = (int)gemm_nt_grid(second.p.g).x;
-          kern<<<dim3(n0 + n1), 256, first.lds > second.lds ? first.lds : second.lds, (hipStream_t)stream>>>(first.p,
-                                                                                                           second.p, n0);
-        });
+        [&](const HeldSmallBlob *recs, int n) { return launch_small_group<STATS, AFF>(recs, n, (hipStream_t)stream); });
     if (!consumed) launch_small_single<STATS, AFF>(q.p, lds, (hipStream_t)stream);
   } else {
     flush_held();
@@ -1252,15 +1310,28 @@ static void launch_small(const omnipq::GemmArgs &g, const void *A, const void *B
 }
 
 extern "C" void omnipq_pair_hold(void) {
-  if (!t_held.full) t_held.armed = true;
+  if (!t_held.held || t_held.group) t_held.armed = true;
 }
 
-extern "C" int omnipq_pair_held(void) { return t_held.full ? 1 : 0; }
+// Opens a group of n launches on the calling thread (whatever was held goes out first): while it is open every
+// omnipq_pair_hold() arms again, and the n-th launch of the kind sends all n out as one grid.
+extern "C" int omnipq_pair_group(int n) {
+  flush_held();
+  t_held.armed = false;
+  t_held.group = 0;
+  if (n < 1 || n > omnipq::kHeldMax) return OMNIPQ_EINVAL;
+  t_held.group = n;
+  return OMNIPQ_OK;
+}
 
-// Sends out a held launch that found no partner and disarms; returns the number of pair launches made so far (diagnostic).
+extern "C" int omnipq_pair_held(void) { return t_held.held; }
+
+// Sends out held launches that found no partner, disarms and closes the group; returns the number of shared grids (pairs
+// and groups) launched so far (diagnostic).
 extern "C" long long omnipq_pair_flush(void) {
   flush_held();
   t_held.armed = false;
+  t_held.group = 0;
   return t_pairs_launched;
 }
 

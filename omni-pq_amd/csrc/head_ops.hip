@@ -355,6 +355,56 @@ __global__ __launch_bounds__(256) void decode_pair_bwd_kernel(PairHead h, HeadGr
   }
 }
 
+// decode_pair_bwd_kernel of up to kDecodeGroupMax stages of the SAME shapes in one grid (their output gradients all exist
+// when backward starts: nothing of a stage's decode feeds another stage with gradient).  Workgroups [s * per_stage,
+// (s + 1) * per_stage) run stage s.  The stages' common base-position gradient (`sink`, [Rh][3]) cannot be summed by the
+// stages' workgroups without a race, so they leave it alone (their dbase is NULL) and the workgroups from sink_begin on form
+// it: exactly one thread per (row, coordinate) adds the stages' centre gradients in stage order -- the order and the bits of
+// one launch per stage adding into the buffer.
+constexpr int kDecodeGroupMax = 4;
+struct DecodeStage {
+  PairHead h;
+  HeadGrads hg;
+  PairQuad q;
+  HeadGrads qg;
+};
+struct DecodeGroupArgs {
+  int n, per_stage, sink_begin;
+  int acc;             // sink += instead of =
+  float *sink;         // or NULL
+  DecodeStage st[kDecodeGroupMax];
+};
+static_assert(sizeof(DecodeGroupArgs) <= 4096, "kernel arguments are limited to 4 KB");
+
+__global__ __launch_bounds__(256) void decode_pair_group_bwd_kernel(DecodeGroupArgs a) {
+  __shared__ int s_pick[2];
+  __shared__ float red[4];
+  const int id = (int)blockIdx.x;
+  if (id >= a.sink_begin) {
+    const int R = a.st[0].h.R, K = a.st[0].h.K;
+    const int i = (id - a.sink_begin) * 256 + (int)threadIdx.x;
+    if (i >= R * 3) return;
+    const int r = i / 3, c = i - 3 * r, b = r / K, k = r - b * K;
+    float v = head_grad_at(a.st[0].hg.g[1], b, k, c);
+    if (a.acc) v = a.sink[i] + v;
+    for (int s = 1; s < a.n; ++s) v = v + head_grad_at(a.st[s].hg.g[1], b, k, c);
+    a.sink[i] = v;
+    return;
+  }
+  const int s = id / a.per_stage, bid = id - s * a.per_stage;
+  const DecodeStage &st = a.st[s];
+  const PairHead &h = st.h;
+  const PairQuad &q = st.q;
+  const int hb = (h.R + 1) >> 1;
+  if (bid < hb) {
+    const int half = (int)threadIdx.x >> 7, r = 2 * bid + half;
+    head_decode_bwd_body(r < h.R ? r : h.R - 1, (int)threadIdx.x & 127, r < h.R, s_pick + half, h.K, h.nh, h.ns, h.ncls, h.y,
+                         h.ldy, h.means, h.hr_scale, st.hg, h.dy, h.lddy, h.dbase, false);
+  } else {
+    quad_decode_bwd_body(bid - hb, red, q.R, q.K, q.y, q.ldy, q.norm, st.qg, q.dy, q.lddy, q.dbase, false);
+  }
+}
+
 }  // namespace omnipq
 
 // outs[4] = { scores bf16 [R][2], center f32 [R][3], normal bf16 [R][3], size bf16 [R][2] }; norm: one float
@@ -513,6 +563,64 @@ extern "C" int omnipq_decode_pair_bwd(int Rh, int Kh, int nh, int ns, int ncls, 
   const int blocks = (Rh + 1) / 2 + (Rq + kQuadRows - 1) / kQuadRows;
   decode_pair_bwd_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(h, hg, q, qg);
   OMNIPQ_LAUNCH_CHECK();
+  return OMNIPQ_OK;
+}
+
+// omnipq_decode_pair_bwd of `nstage` stages of the same shapes, four stages per launch.  Per-stage arguments are arrays of
+// nstage entries in the order the single calls would be issued (gptr_h / gbf_h: nstage x 10, gstrides_h: nstage x 40, gptr_q /
+// gbf_q: nstage x 4, gstrides_q: nstage x 16; gn2_h: 10, common).  dbaseh / dbaseq: per stage, receive (never accumulate) that
+// stage's base-position gradients; the arrays or single entries may be NULL.  sink (may be NULL; with it every dbaseh entry
+// must be NULL): [Rh][3], the SUM of the stages' object base-position gradients in stage order, bit for bit what nstage single
+// calls adding into one buffer leave; accumulate != 0: added to what the sink holds.
+extern "C" int omnipq_decode_pair_group_bwd(int nstage, int Rh, int Kh, int nh, int ns, int ncls, const void *const *yh,
+                                            int ldyh, const float *const *means, float hr_scale,
+                                            const void *const *gptr_h, const int *gstrides_h, const int *gn2_h,
+                                            const int *gbf_h, void *const *dyh, int lddyh, float *const *dbaseh, int Rq,
+                                            int Kq, const void *const *yq, int ldyq, const float *const *norm,
+                                            const void *const *gptr_q, const int *gstrides_q, const int *gbf_q,
+                                            void *const *dyq, int lddyq, float *const *dbaseq, float *sink, int accumulate,
+                                            void *stream) {
+  using namespace omnipq;
+  if (nstage < 1 || nstage > 64) return OMNIPQ_EINVAL;
+  if (Rh <= 0 || Rq <= 0 || Kh < 1 || Kq < 1 || nh < 1 || ns < 1 || ncls < 1 || (Rh % Kh) || (Rq % Kq)) return OMNIPQ_EINVAL;
+  const int width = 5 + 2 * nh + 4 * ns + ncls;
+  if (!yh || !means || !gptr_h || !gstrides_h || !gn2_h || !gbf_h || !dyh || ldyh < width || lddyh < width) return OMNIPQ_EINVAL;
+  if (!yq || !norm || !gptr_q || !gstrides_q || !gbf_q || !dyq || ldyq < 10 || lddyq < 10 || Rq > (1 << 24)) return OMNIPQ_EINVAL;
+  for (int i = 0; i < 10; ++i)
+    if (gn2_h[i] < 1) return OMNIPQ_EINVAL;
+  for (int s = 0; s < nstage; ++s) {
+    if (!yh[s] || !means[s] || !dyh[s] || !yq[s] || !norm[s] || !dyq[s]) return OMNIPQ_EINVAL;
+    if (sink && dbaseh && dbaseh[s]) return OMNIPQ_EINVAL;
+  }
+  const int per_stage = (Rh + 1) / 2 + (Rq + kQuadRows - 1) / kQuadRows;
+  for (int s0 = 0; s0 < nstage; s0 += kDecodeGroupMax) {
+    DecodeGroupArgs a;
+    a.n = nstage - s0 < kDecodeGroupMax ? nstage - s0 : kDecodeGroupMax;
+    a.per_stage = per_stage;
+    a.sink_begin = a.n * per_stage;
+    a.acc = (accumulate || s0 > 0) ? 1 : 0;
+    a.sink = sink;
+    for (int j = 0; j < a.n; ++j) {
+      const int s = s0 + j;
+      DecodeStage &st = a.st[j];
+      for (int i = 0; i < 10; ++i) {
+        const int *gs = gstrides_h + 40 * s + 4 * i;
+        st.hg.g[i] = HeadGrad{gptr_h[10 * s + i], gs[0], gs[1], gs[2], gs[3], gn2_h[i], gbf_h[10 * s + i]};
+        st.qg.g[i] = HeadGrad{nullptr, 0, 0, 0, 0, 1, 0};
+      }
+      for (int i = 0; i < 4; ++i) {
+        const int *gs = gstrides_q + 16 * s + 4 * i;
+        st.qg.g[i] = HeadGrad{gptr_q[4 * s + i], gs[0], gs[1], gs[2], gs[3], 1, gbf_q[4 * s + i]};
+      }
+      st.h = PairHead{Rh, Kh, nh, ns, ncls, ldyh, lddyh, (const e16_t *)yh[s], nullptr, means[s], hr_scale, (e16_t *)dyh[s],
+                      (sink || !dbaseh) ? nullptr : dbaseh[s], 0, PosOut{nullptr, 1, 1, 0}};
+      st.q = PairQuad{Rq, Kq, ldyq, lddyq, (const e16_t *)yq[s], nullptr, const_cast<float *>(norm[s]), (e16_t *)dyq[s],
+                      dbaseq ? dbaseq[s] : nullptr, 0, PosOut{nullptr, 1, 1, 0}};
+    }
+    const int blocks = a.sink_begin + (sink ? (Rh * 3 + 255) / 256 : 0);
+    decode_pair_group_bwd_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(a);
+    OMNIPQ_LAUNCH_CHECK();
+  }
   return OMNIPQ_OK;
 }
 

@@ -735,6 +735,22 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pair_kernel(ApplyProblem p0,
   if (id < n0) bn_bwd_apply_fused_body<1, false>(p0, id, n0);
   else bn_bwd_apply_fused_body<1, false>(p1, id - n0, (int)gridDim.x - n0);
 }
+// up to kHeldMax independent small problems in one grid (see gemm_bf16.hip: gemm_nt_group_kernel)
+struct ApplyGroupArgs {
+  int n;
+  int blk_begin[kHeldMax + 1];       // first workgroup of every problem, then the grid's size
+  ApplyProblem item[kHeldMax];
+};
+static_assert(sizeof(ApplyGroupArgs) <= 4096, "kernel arguments are limited to 4 KB");
+__global__ __launch_bounds__(256) void bn_bwd_apply_group_kernel(ApplyGroupArgs a) {
+  const int id = (int)blockIdx.x;
+  int lo = 0, hi = a.n - 1;          // last problem with blk_begin <= id
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (a.blk_begin[mid] <= id) lo = mid; else hi = mid - 1;
+  }
+  bn_bwd_apply_fused_body<1, false>(a.item[lo], id - a.blk_begin[lo], a.blk_begin[lo + 1] - a.blk_begin[lo]);
+}
 
 // sums (f64 totals) -> per-channel means as f32:  st[c] = sum dz / P,  st[C + c] = sum dz*yhat / P
 __global__ void bwd_means_kernel(int n2, double invP, const double *__restrict__ sums, float *__restrict__ st) {
@@ -2000,10 +2016,7 @@ extern "C" int omnipq_bn_bwd_apply_fused(long long P, int C, double total_positi
   const int lds = (int)sizeof(float) * 4 * C;
   if (big) {
     omnipq::HeldLaunch &h = omnipq::held_launch();
-    if (h.full) {
-      h.full = h.armed = false;
-      h.single(h);
-    }
+    if (h.held) omnipq::release_held(h);
     // (measured round 3, 1 M x 128 / 262 144 x 256: 153 / 83 us = 5.3 / 4.8 TB/s on the three streams; a capped grid with a
     // grid-stride loop and plain loads are within 2 % of it -- two reads per write do not reach the 6.2 TB/s of a 1 : 1 copy)
     const omnipq::RowPlan &rp = omnipq::row_plan();
@@ -2021,25 +2034,36 @@ extern "C" int omnipq_bn_bwd_apply_fused(long long P, int C, double total_positi
     OMNIPQ_LAUNCH_CHECK();
     return OMNIPQ_OK;
   }
-  auto single = +[](const omnipq::HeldLaunch &h) {
+  auto single = +[](const void *blob, hipStream_t s) {
     Held f;
-    __builtin_memcpy(&f, h.blob, sizeof(f));
-    bn_bwd_apply_fused_kernel<1, false><<<f.grid, 256, sizeof(float) * 4 * f.p.C, h.stream>>>(f.p);
+    __builtin_memcpy(&f, blob, sizeof(f));
+    bn_bwd_apply_fused_kernel<1, false><<<f.grid, 256, sizeof(float) * 4 * f.p.C, s>>>(f.p);
   };
   // small problems only: a launch that fills the chip on its own gains nothing from a partner
   const bool pairable = grid <= 1024;
   if (!pairable) {
     omnipq::HeldLaunch &h = omnipq::held_launch();
-    if (h.full) {
-      h.full = h.armed = false;
-      h.single(h);
-    }
+    if (h.held) omnipq::release_held(h);
   }
   if (!pairable || !omnipq::hold_or_pair(q, omnipq::kHeldApplyKey, (hipStream_t)stream, single,
-                                         [&](const Held &first, const Held &second) {
-                                           const int cmax = first.p.C > second.p.C ? first.p.C : second.p.C;
-                                           bn_bwd_apply_pair_kernel<<<first.grid + second.grid, 256, sizeof(float) * 4 * cmax,
-                                                                      (hipStream_t)stream>>>(first.p, second.p, first.grid);
+                                         [&](const Held *f, int n) {
+                                           int cmax = 0;
+                                           for (int i = 0; i < n; ++i) cmax = f[i].p.C > cmax ? f[i].p.C : cmax;
+                                           if (n == 2) {
+                                             bn_bwd_apply_pair_kernel<<<f[0].grid + f[1].grid, 256, sizeof(float) * 4 * cmax,
+                                                                        (hipStream_t)stream>>>(f[0].p, f[1].p, f[0].grid);
+                                             return 1;
+                                           }
+                                           omnipq::ApplyGroupArgs a;
+                                           a.n = n;
+                                           a.blk_begin[0] = 0;
+                                           for (int i = 0; i < n; ++i) {
+                                             a.item[i] = f[i].p;
+                                             a.blk_begin[i + 1] = a.blk_begin[i] + f[i].grid;
+                                           }
+                                           bn_bwd_apply_group_kernel<<<a.blk_begin[n], 256, sizeof(float) * 4 * cmax,
+                                                                       (hipStream_t)stream>>>(a);
+                                           return 1;
                                          }))
     bn_bwd_apply_fused_kernel<1, false><<<grid, 256, lds, (hipStream_t)stream>>>(q.p);
   OMNIPQ_LAUNCH_CHECK();

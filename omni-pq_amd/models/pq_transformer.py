@@ -424,10 +424,14 @@ _POS_KPAD = 32            # three coordinates at the row GEMMs' operand width (r
 
 
 def predict_pair(head, quad_head, net, net_q, base_xyz, base_xyz_q, end_points, prefix, rows=None, rows_q=None,
-                 sink=None, want_pos=False):
+                 sink=None, want_pos=False, group=None):
     """`head(net, ...)` then `quad_head(net_q, ...)` of one decoder stage (reference models/pq_transformer.py:230-233,
-    :262-267); with the fused decode both heads' tails share one launch each way.
+    :262-267); with the fused decode both heads' tails share one launch each way.  group (HeadsGroup | None): the stage's
+    backward is left to the joint node of all stages (see HeadsGroup).
     -> (object centres, quad centres, end_points, both centres as one (B, K + Kq, 3) tensor | None)."""
+    if group is not None and group.stage(head, quad_head, net, net_q, base_xyz, base_xyz_q, end_points, prefix, rows, rows_q,
+                                         sink, want_pos):
+        return group.last
     if not (_PAIR_DECODE and _FUSED_DECODE and net.is_cuda):
         center, _, end_points = head(net, base_xyz=base_xyz, end_points=end_points, prefix=prefix, net_rows=rows)
         center_q, _, end_points = quad_head(net_q, base_xyz=base_xyz_q, end_points=end_points, prefix=prefix,
@@ -441,6 +445,11 @@ def predict_pair(head, quad_head, net, net_q, base_xyz, base_xyz_q, end_points, 
         return center, center_q, end_points, None
     outs = DecodePair.apply(yh, base_xyz, head._mean_sizes(net.device), head.num_heading_bin, head.num_size_cluster,
                             head.num_class, yq, base_xyz_q, sink, want_pos, _POS_KPAD if (want_pos and _POS_ROWS16) else 0)
+    return _publish_pair(outs, end_points, prefix)
+
+
+def _publish_pair(outs, end_points, prefix):
+    """the outputs of a pair decode into end_points -> what predict_pair returns"""
     for key, val in zip(_HEAD_KEYS + _QUAD_KEYS, outs):
         end_points[f'{prefix}{key}'] = val
     pos = outs[14] if len(outs) > 14 else None
@@ -450,6 +459,174 @@ def predict_pair(head, quad_head, net, net_q, base_xyz, base_xyz_q, end_points, 
         rows2d.omnipq_rows_in = (rows2d._version, outs[15])
         pos.omnipq_rows2d = rows2d
     return outs[1], outs[11], end_points, pos
+
+
+# The backward of the prediction heads of ALL stages in grouped launches.  Every output of a stage's heads goes to the loss and
+# nowhere else -- the centres that feed the next layer's position embedding are detached, the base positions' gradient goes to
+# the sink -- so when backward starts the output gradients of all stages exist, yet autograd runs stage i's six small launches
+# (decode backward, three data-gradient GEMMs, two BatchNorm applies, each a fraction of the chip) between decoder layers
+# i + 1 and i.  With the switch on, a stage's forward runs where and as it does otherwise, but outside autograd: what it would
+# save is kept on a HeadsGroup, and after the last stage ONE node (HeadsJoint) puts aliases of all stages' outputs into
+# end_points.  Its backward has every output gradient at once: one grouped decode backward per four stages
+# (omnipq_decode_pair_group_bwd), then the stacks' backward programs of all stages in lockstep, every round one grid
+# (rows_mlp._lockstep, omnipq_pair_group).  Same arithmetic per problem, same bits.  False: the per-stage nodes.
+_HEADS_BWD_GROUP = True
+_HEADS_GROUP_MAX = 7         # stages; two stacks each: the 14 launches a group holds (csrc/common.h: kHeldMax)
+
+
+def heads_bwd_route(stages, pair_stacks, pair_decode, fused_decode, cuda, training, grad, world, force_collectives):
+    """"group" | "stage": how the prediction heads' backward runs, from flags alone (no tensor, no launch; the switch is read
+    now).  The grouped route is the pair route of every stage (its three switches, a GPU, training with grad) without a
+    statistics exchange (one rank, no forced collectives: the exchange is made per pair) for as many stages as a group
+    holds."""
+    if not (_HEADS_BWD_GROUP and pair_stacks and pair_decode and fused_decode and cuda and training and grad):
+        return "stage"
+    if world != 1 or force_collectives or not (1 <= stages <= _HEADS_GROUP_MAX):
+        return "stage"
+    return "group"
+
+
+class _Taped:
+    """Stands in for the autograd context of a Function whose forward is run outside autograd: keeps what it saves."""
+    saved_tensors = ()
+
+    def save_for_backward(self, *tensors):
+        self.saved_tensors = tensors
+
+    def set_materialize_grads(self, value):
+        pass
+
+    def mark_non_differentiable(self, *tensors):
+        pass
+
+
+class HeadsGroup:
+    """What the grouped stages of ONE forward pass keep for their joint backward (see _HEADS_BWD_GROUP)."""
+
+    class Stage:
+        __slots__ = ("prefix", "xa", "xb", "base_q", "params_a", "params_b", "stacks", "decode", "outs")
+
+    def __init__(self):
+        self.stages, self.sink, self.geom, self.last = [], None, None, None
+
+    def stage(self, head, quad_head, net, net_q, base_xyz, base_xyz_q, end_points, prefix, rows, rows_q, sink, want_pos):
+        """Run the stage's forward as predict_pair's pair route does, outside autograd; self.last = what predict_pair returns.
+        -> False (nothing was run): the stage is not one the joint node can take, predict_pair goes on with it."""
+        if not (head.training and quad_head.training) or (base_xyz.requires_grad and sink is None):
+            return False
+        pa = _head_problem(head, net, head.heads(), rows)
+        pb = _head_problem(quad_head, net_q, quad_head.heads(), rows_q)
+        if not (rows_mlp.usable(pa[0], pa[1], True) and rows_mlp.usable(pb[0], pb[1], True)):
+            return False
+        B, K, Bq, Kq = net.shape[0], net.shape[2], net_q.shape[0], net_q.shape[2]
+        nh, ns, ncls = head.num_heading_bin, head.num_size_cluster, head.num_class
+        geom = (B, K, nh, ns, ncls, Bq, Kq, pa[2].shape[0], pb[2].shape[0])
+        if self.stages and (geom != self.geom or sink is not self.sink):
+            return False                               # one grouped decode takes stages of the same shapes only
+        self.geom, self.sink = geom, sink
+        _head_bias(head, pa[1], head.heads(), pa[2], True, net.is_cuda)
+        _head_bias(quad_head, pb[1], quad_head.heads(), pb[2], True, net_q.is_cuda)
+        st = HeadsGroup.Stage()
+        st.prefix, st.xa, st.xb, st.base_q = prefix, pa[0], pb[0], base_xyz_q
+        spec_a, st.params_a = rows_mlp._spec_of(pa[0], pa[1], True, True)
+        spec_b, st.params_b = rows_mlp._spec_of(pb[0], pb[1], True, True)
+        st.stacks, st.decode = _Taped(), _Taped()
+        with torch.no_grad():
+            yh, yq = rows_mlp.RowsMLPPair.forward(st.stacks, pa[0], spec_a, pb[0], spec_b, True, len(st.params_a),
+                                                  *st.params_a, *st.params_b)
+            outs = DecodePair.forward(st.decode, yh, base_xyz, head._mean_sizes(net.device), nh, ns, ncls, yq, base_xyz_q,
+                                      sink, want_pos, _POS_KPAD if (want_pos and _POS_ROWS16) else 0)
+        st.outs = outs[:14]
+        self.stages.append(st)
+        self.last = _publish_pair(outs, end_points, prefix)
+        return True
+
+    def finish(self, end_points):
+        """After the last stage: the joint node, and its aliases of every grouped stage's outputs into end_points."""
+        if not self.stages:
+            return
+        flat = []
+        for st in self.stages:
+            flat += [st.xa, st.xb, st.base_q, *st.params_a, *st.params_b]
+        outs = HeadsJoint.apply(self, *flat)
+        for s, st in enumerate(self.stages):
+            for key, val in zip(_HEAD_KEYS + _QUAD_KEYS, outs[14 * s:14 * s + 14]):
+                end_points[f'{st.prefix}{key}'] = val
+
+
+class HeadsJoint(torch.autograd.Function):
+    """(group, per stage: object rows, quad rows, quad base positions, the two stacks' parameters) -> aliases of the fourteen
+    decode outputs of every stage.  backward: see _HEADS_BWD_GROUP; a stage none of whose outputs carries a gradient is left
+    out of the group."""
+
+    @staticmethod
+    def forward(ctx, group, *flat):
+        ctx.e16 = E16.dtype
+        ctx.group = group
+        ctx.set_materialize_grads(False)
+        return tuple(o.view_as(o) for st in group.stages for o in st.outs)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        E16.select(ctx.e16)
+        import ctypes
+        group, nig = ctx.group, ctx.needs_input_grad
+        grads = [None] * len(nig)
+        live, first = [], 1                                  # (stage, its gradients, index of its first input)
+        for s, st in enumerate(group.stages):
+            g = gs[14 * s:14 * s + 14]
+            if any(x is not None for x in g):
+                live.append((st, g, first))
+            first += 3 + len(st.params_a) + len(st.params_b)
+        live.reverse()                                       # the order of the per-stage nodes: the last stage first
+        if not live:
+            return tuple(grads)
+        B, K, nh, ns, ncls, Bq, Kq, _, _ = group.geom
+        n, n2 = len(live), [1, 1, 1, 1, 1, 1, 3, 3, 1, 1]
+        yh0, _, yq0, _ = live[0][0].decode.saved_tensors
+        dev = yh0.device
+        ph, sh, fh, pq, sq, fq, keep = [], [], [], [], [], [], []
+        for st, g, _ in live:
+            for dst, part in zip((ph, sh, fh, keep), _grad_descriptors(g[:10], n2)):
+                dst += part
+            for dst, part in zip((pq, sq, fq, keep), _grad_descriptors(g[10:14], [1, 1, 1, 1])):
+                dst += part
+        dyh = [torch.empty((B * K, yh0.shape[1]), device=dev, dtype=E16.dtype) for _ in live]
+        dyq = [torch.empty((Bq * Kq, yq0.shape[1]), device=dev, dtype=E16.dtype) for _ in live]
+        dbq = [torch.empty((Bq, Kq, 3), device=dev, dtype=torch.float32) if nig[first + 2] else None for _, _, first in live]
+        sink, acc = group.sink, 0
+        if sink is not None:
+            if sink.buf is None:
+                sink.buf = torch.empty((B, K, 3), device=dev, dtype=torch.float32)
+            else:
+                acc = 1
+
+        def ptrs(tensors):
+            return (ctypes.c_void_p * n)(*[None if t is None else t.data_ptr() for t in tensors])
+
+        saved = [st.decode.saved_tensors for st, _, _ in live]          # (yh, means, yq, norm) per stage
+        scale = float(np.float32(np.pi / nh))
+        sa_fused._call(sa_fused._lib.omnipq_decode_pair_group_bwd, yh0, n, B * K, K, nh, ns, ncls, ptrs([t[0] for t in saved]),
+                       yh0.stride(0), ptrs([t[1] for t in saved]), scale, (ctypes.c_void_p * (10 * n))(*ph),
+                       (ctypes.c_int * (40 * n))(*sh), (ctypes.c_int * 10)(*n2), (ctypes.c_int * (10 * n))(*fh), ptrs(dyh),
+                       dyh[0].stride(0), None, Bq * Kq, Kq, ptrs([t[2] for t in saved]), yq0.stride(0),
+                       ptrs([t[3] for t in saved]), (ctypes.c_void_p * (4 * n))(*pq), (ctypes.c_int * (16 * n))(*sq),
+                       (ctypes.c_int * (4 * n))(*fq), ptrs(dyq), dyq[0].stride(0), ptrs(dbq),
+                       sa_fused._p(sink.buf if sink is not None else None), acc)
+        programs = []
+        for j, (st, _, first) in enumerate(live):
+            na, nb = len(st.params_a), len(st.params_b)
+            nig_a = (nig[first], False, False) + tuple(nig[first + 3:first + 3 + na])
+            nig_b = (nig[first + 1], False, False) + tuple(nig[first + 3 + na:first + 3 + na + nb])
+            programs.append(rows_mlp._backward_program(st.stacks.a, True, dyh[j], nig_a))
+            programs.append(rows_mlp._backward_program(st.stacks.b, j + 1 < n, dyq[j], nig_b))
+        outs = rows_mlp._lockstep(*programs)
+        for j, (st, _, first) in enumerate(live):
+            oa, ob = outs[2 * j], outs[2 * j + 1]
+            grads[first], grads[first + 1], grads[first + 2] = oa[0], ob[0], dbq[j]
+            grads[first + 3:first + 3 + len(st.params_a) + len(st.params_b)] = tuple(oa[3:]) + tuple(ob[3:])
+        ctx.group = None
+        return tuple(grads)
 
 
 class PositionEmbeddingLearned(nn.Module):
@@ -737,9 +914,15 @@ class PQ_Transformer(nn.Module):
             sink = XyzGradSink()
             cluster_feature = SinkFlush.apply(cluster_feature, cluster_xyz, sink)
 
+        heads_group = None
+        if heads_bwd_route(self.num_layer + 1, _PAIR_STACKS, _PAIR_DECODE, _FUSED_DECODE, cluster_feature.is_cuda,
+                           self.training, torch.is_grad_enabled(), sa_fused._world(),
+                           sa_fused._FORCE_COLLECTIVES) == "group":
+            heads_group = HeadsGroup()         # the heads' backward of all stages: one node, grouped launches
+
         center, center_q, end_points, pos_joint = predict_pair(
             self.proposal, self.quad_proposal, cluster_feature, quad_feature, cluster_xyz, quad_xyz, end_points,
-            'proposal_', sink=sink, want_pos=True)
+            'proposal_', sink=sink, want_pos=True, group=heads_group)
         # the reference clones here (:236-237); nothing writes into these tensors afterwards, a detached alias suffices
         base_xyz = center.detach()
         base_xyz_q = center_q.detach()
@@ -787,9 +970,11 @@ class PQ_Transformer(nn.Module):
                 rows_obj, rows_quad = torch.split(rows16, [n_obj, n_quad], dim=1)
             base_xyz, base_xyz_q, end_points, pos_joint = predict_pair(
                 self.prediction_heads[i], self.prediction_quad_heads[i], query, query_q, cluster_xyz, quad_xyz,
-                end_points, prefix, rows_obj, rows_quad, sink=sink, want_pos=i + 1 < self.num_layer)
+                end_points, prefix, rows_obj, rows_quad, sink=sink, want_pos=i + 1 < self.num_layer, group=heads_group)
             base_xyz = base_xyz.detach()
             base_xyz_q = base_xyz_q.detach()
+        if heads_group is not None:
+            heads_group.finish(end_points)
         return end_points
 
     def __getstate__(self):

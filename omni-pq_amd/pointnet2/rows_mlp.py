@@ -207,29 +207,35 @@ def _drain(gen):
         return done.value
 
 
-def _lockstep(lead, follow):
-    """Run two independent stacks' programs GEMM by GEMM: each program stops right after issuing a GEMM; the leading one's
-    is held back and goes out in one grid with the follower's next GEMM of the same kind (a held launch that finds no
-    partner is sent out before anything else can be enqueued behind it)."""
-    out = [None, None]
-    alive = [True, True]
-    gens = (lead, follow)
+def _lockstep(*gens):
+    """Run independent stacks' programs GEMM by GEMM: each program stops right after issuing a GEMM; the leading ones' (all but
+    the last program) are held back and go out in one grid with the last program's next GEMM of the same kind (held launches
+    that find no partner are sent out before anything else can be enqueued behind them).  Two programs pair (omnipq_pair_hold);
+    more open a group per round (omnipq_pair_group: no statistics exchange is shared, the caller runs such a group only
+    where none is needed)."""
+    n = len(gens)
+    out = [None] * n
+    alive = [True] * n
     assert not _lib.omnipq_pair_held(), "rows_mlp: a pair launch was still held when a lockstep run started"
-    outer, sa_fused.PairStats.active = sa_fused.PairStats.active, sa_fused.PairStats()
+    outer, sa_fused.PairStats.active = sa_fused.PairStats.active, sa_fused.PairStats() if n == 2 else None
     try:
-        while alive[0] or alive[1]:
-            for i in (0, 1):
-                if alive[i]:
-                    try:
-                        next(gens[i])
-                    except StopIteration as done:
-                        out[i], alive[i] = done.value, False
-                if i == 0 and not _lib.omnipq_pair_held():
-                    _lib.omnipq_pair_flush()              # nothing was held: disarm before the follower runs
+        while any(alive):
+            if n > 2:
+                _lib.omnipq_pair_group(sum(alive))
+            for i in range(n):
+                if not alive[i]:
+                    continue
+                held = _lib.omnipq_pair_held()
+                try:
+                    next(gens[i])
+                except StopIteration as done:
+                    out[i], alive[i] = done.value, False
+                if i < n - 1 and _lib.omnipq_pair_held() != held + 1:
+                    _lib.omnipq_pair_flush()              # nothing was held: disarm before the next program runs
             _lib.omnipq_pair_flush()
     finally:
         sa_fused.PairStats.active = outer
-        _lib.omnipq_pair_flush()      # an exception in either program must not leave a launch held or the hold armed
+        _lib.omnipq_pair_flush()      # an exception in a program must not leave a launch held or the hold armed
     assert not _lib.omnipq_pair_held()
     return out
 
