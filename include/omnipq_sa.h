@@ -337,7 +337,11 @@ int omnipq_unprep_wgrad(int cout, int cin, int k, int rot, const float *dWp, flo
 int omnipq_sums_to_f32(int C, const double *sums, float *dbeta, float *dgamma, void *stream);
 
 /* BatchNorm training-mode bookkeeping from (possibly all-reduced) sums over `count` positions:
- * a = gamma*invstd, b = beta - mean*a, saved mean/invstd, running-stat update (NULL to skip). */
+ * a = gamma*invstd, b = beta - mean*a, saved mean/invstd, running-stat update (NULL to skip).
+ * count <= 0 is NOT rejected here or in omnipq_bn_finalize_relu (their callers pass rows * world, which is 0 for an empty
+ * batch, and still want the launch): the call returns OMNIPQ_OK; with count == 0, a / b / mean / invstd and the running
+ * statistics come out non-finite (0 / 0), with count < 0 they are meaningless.  omnipq_sa_pool_select_finalize rejects
+ * count <= 0 with OMNIPQ_EINVAL. */
 int omnipq_bn_finalize(int C, double count, const double *sums, const float *gamma, const float *beta, float eps,
                        float momentum, float *running_mean, float *running_var, float *a, float *b,
                        float *mean, float *invstd, const float *conv_bias /* NULL, or the bias a preceding
@@ -361,7 +365,9 @@ int omnipq_sa_pool_bwd_apply(int b, int m, int s, int C, double total_positions,
                              const float *mean, const float *invstd, const double *sums, const float *g_out,
                              const void *out_pm, const unsigned char *arg, void *dY, const omnipq_row_plan *plan, void *stream);
 /* The same; additionally gb_out float[2][C] = (dbeta | dgamma), the totals as f32 -- the layer's affine gradients when
- * `sums` are this rank's own totals (no process group); saves the omnipq_sums_to_f32 launch. */
+ * `sums` are this rank's own totals (no process group); saves the omnipq_sums_to_f32 launch.  An empty batch (b m s == 0)
+ * still publishes gb_out from `sums` (nothing else is read or written), as omnipq_bn_bwd_apply_fused publishes dbeta_dgamma
+ * for P == 0. */
 int omnipq_sa_pool_bwd_apply_gb(int b, int m, int s, int C, double total_positions, const void *Y, const float *a,
                                 const float *mean, const float *invstd, const double *sums, const float *g_out,
                                 const void *out_pm, const unsigned char *arg, void *dY, float *gb_out, const omnipq_row_plan *plan, void *stream);

@@ -1718,7 +1718,14 @@ static int pool_bwd_apply_impl(int b, int m, int s, int C, double total_position
                                const void *out_pm, const unsigned char *arg, void *dY, float *gb_out, void *stream) {
   if (b < 0 || m < 0 || s <= 0 || s > 255 || C <= 0 || (C % 8)) return OMNIPQ_EINVAL;
   const long long chunks = (long long)b * m * s * (C / 8);
-  if (chunks == 0) return OMNIPQ_OK;
+  if (chunks == 0) {
+    // an empty batch still publishes dbeta | dgamma (as omnipq_bn_bwd_apply_fused does): nothing else is touched
+    if (!gb_out) return OMNIPQ_OK;
+    if (!sums) return OMNIPQ_EINVAL;
+    sums_to_f32_kernel<<<(C + 127) / 128, 128, 0, (hipStream_t)stream>>>(C, sums, gb_out, gb_out + C);
+    OMNIPQ_LAUNCH_CHECK();
+    return OMNIPQ_OK;
+  }
   if (!Y || !a || !mean || !invstd || !sums || !g_out || !out_pm || !arg || !dY) return OMNIPQ_EINVAL;
   const long long items = chunks / s;                   // (ball, 8-channel piece)
   const omnipq::RowPlan &rp = omnipq::row_plan();
