@@ -16,10 +16,6 @@
 
 #include "common.h"
 
-// omnipq_tn_debug: bit 0: the register-prefetch workgroup program (tn_tile) instead of the LDS-DMA one (tn_tile_dma); bits
-// 1-3 ablations; bits 8-15: workgroup target of the grouped launch in units of 256.  A/B timing only.
-static int g_tn_debug = 0;
-
 namespace omnipq {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -837,7 +833,7 @@ struct TnGroupItem {
 };
 struct TnGroupArgs {
   int n;
-  int pad_;
+  int debug;                    // TnArgs::debug of every problem of the launch
   TnGroupItem item[kGroupMax];
 };
 static_assert(sizeof(TnGroupArgs) <= 4096, "kernel arguments are limited to 4 KB");
@@ -851,7 +847,7 @@ __global__ __launch_bounds__(256, REG ? 4 : 3) void gemm_tn_grouped_kernel(TnGro
     if (a.item[mid].wg_begin <= id) lo = mid; else hi = mid - 1;
   }
   const TnGroupItem &it = a.item[lo];
-  const TnArgs g{it.M, it.N, it.P, it.lda, it.ldb, it.p_chunk, it.m_tiles, it.n_tiles, it.rows_dev, a.pad_,
+  const TnArgs g{it.M, it.N, it.P, it.lda, it.ldb, it.p_chunk, it.m_tiles, it.n_tiles, it.rows_dev, a.debug,
                  it.colsum ? 1 : 0};
   // column sums of A (the bias gradient): per-slab partial rows right behind the problem's C slabs
   float *cpart = it.colsum ? it.part + (size_t)(it.flags >> 8) * it.M * it.N : nullptr;
@@ -930,16 +926,67 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(int n4, int slabs, int
 
 }  // namespace omnipq
 
+// ---- host side: the debug flag (TnDebug), the kernel picks, the cut of the position axis (TnCut), one plan per route (its cut
+// and workspace layout: what the size query returns AND where the launcher points) and the slab reduction, each written once
+using namespace omnipq;
+
+// omnipq_tn_debug, A/B timing only; decoded here and nowhere else
+static int g_tn_debug = 0;
 extern "C" void omnipq_tn_debug(int flags) { g_tn_debug = flags; }
+struct TnDebug {
+  bool reg;           // bit 0: the register-prefetch workgroup program (tn_tile) instead of the LDS-DMA one (tn_tile_dma)
+  int kernel;         // TnArgs::debug, the ablations the kernels test (tools/sa_ab.py --capi omnipq_tn_debug): 2 no fetches after
+                      // the prologue, 4 no fragment reads / MFMAs, 8 no C stores, 16 no hot-word DMA
+  int wg_target;      // bits 8-15, in units of 256: workgroup target of the grouped launch (tools/bench_tn_grouped.py --target)
+};
+static TnDebug tn_debug() { return TnDebug{(g_tn_debug & 1) != 0, g_tn_debug, 256 * ((g_tn_debug >> 8) & 0xFF)}; }
+
+// the kernel picks; reg: TnDebug::reg
+typedef void (*TnGroupedKernel)(TnGroupArgs);
+static TnGroupedKernel tn_grouped_kernel(bool affb, bool reg) {
+  static const TnGroupedKernel k[2][2] = {{gemm_tn_grouped_kernel<false, false>, gemm_tn_grouped_kernel<true, false>},
+                                          {gemm_tn_grouped_kernel<false, true>, gemm_tn_grouped_kernel<true, true>}};
+  return k[reg][affb];
+}
+static auto tn_affine_kernel(bool reg) { return reg ? gemm_tn_affine_kernel<true> : gemm_tn_affine_kernel<false>; }
+static auto tn_plain_kernel(bool reg) { return reg ? gemm_tn_kernel<true> : gemm_tn_kernel<false>; }
+
 // workgroups of the grouped kernel (which: 0 plain / 1 affine, + 2 for the register-prefetch program) one CU holds
 extern "C" int omnipq_tn_occupancy(int which) {
   int n = -1;
-  const void *k = which == 0   ? reinterpret_cast<const void *>(omnipq::gemm_tn_grouped_kernel<false, false>)
-                  : which == 1 ? reinterpret_cast<const void *>(omnipq::gemm_tn_grouped_kernel<true, false>)
-                  : which == 2 ? reinterpret_cast<const void *>(omnipq::gemm_tn_grouped_kernel<false, true>)
-                               : reinterpret_cast<const void *>(omnipq::gemm_tn_grouped_kernel<true, true>);
+  if (which < 0 || which > 3) which = 3;
+  const void *k = reinterpret_cast<const void *>(tn_grouped_kernel(which & 1, which & 2));
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, 256, 0) != hipSuccess) return -1;
   return n;
+}
+
+static int tn_tiles(int M, int N) { return ((M + 127) / 128) * ((N + 127) / 128); }
+
+// The cut of the position axis of one problem.  A slab policy (tn_slabs, tn_dz_slabs, tng_slabs) allows `alloc` slabs, which
+// is what the workspace holds; every slab contracts p_chunk positions, a multiple of TBK, which leaves `used` slabs with
+// work; the grid has wgs_per_tile workgroups per output tile (`used` rounded up to the 8 XCDs: see tn_tile).
+struct TnCut { int alloc, p_chunk, used, wgs_per_tile; };
+static TnCut tn_cut(int P, int alloc) {
+  TnCut c{alloc};
+  c.p_chunk = (((P + alloc - 1) / alloc) + TBK - 1) / TBK * TBK;
+  c.used = P > 0 ? (P + c.p_chunk - 1) / c.p_chunk : 1;
+  c.wgs_per_tile = (c.used + 7) / 8 * 8;
+  return c;
+}
+
+// out = the sum of `used` slabs of n4 float4 each, in a fixed order; mid: kReduceGroups such slabs (see slab_reduce_kernel)
+static int reduce_slabs(int n4, int used, const float *part, float *mid, float *out, hipStream_t stream) {
+  const f32x4 *part4 = reinterpret_cast<const f32x4 *>(part);
+  f32x4 *mid4 = reinterpret_cast<f32x4 *>(mid), *out4 = reinterpret_cast<f32x4 *>(out);
+  const unsigned blocks = (n4 + 255) / 256;
+  const bool two_level = used > 2 * kReduceGroups;
+  if (two_level) {
+    slab_reduce_kernel<<<dim3(blocks, kReduceGroups), 256, 0, stream>>>(n4, used, kReduceGroups, part4, mid4);
+    OMNIPQ_LAUNCH_CHECK();
+  }
+  slab_reduce_kernel<<<dim3(blocks, 1), 256, 0, stream>>>(n4, two_level ? kReduceGroups : used, 1, two_level ? mid4 : part4, out4);
+  OMNIPQ_LAUNCH_CHECK();
+  return OMNIPQ_OK;
 }
 
 // C[M][N] (f32) = A[P][M]^T * B[P][N]; M, N multiples of 8; lda, ldb multiples of 8.
@@ -959,32 +1006,67 @@ extern "C" int omnipq_gemm_tn_slabs(int tiles, long long P, int k_step) {
   if (slabs < 1) slabs = 1;
   return (int)slabs;
 }
-static int tn_slabs(int tiles, int P) { return omnipq_gemm_tn_slabs(tiles, P, omnipq::TBK); }
+static int tn_slabs(int tiles, int P) { return omnipq_gemm_tn_slabs(tiles, P, TBK); }
 
-extern "C" long long omnipq_gemm_tn_workspace_floats(int M, int N, int P) {
-  using namespace omnipq;
-  const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
-  const int slabs = tn_slabs(tiles, P);
-  return (long long)(slabs + kReduceGroups) * M * N;
+// workspace (offsets in floats): [part: alloc x M N] [mid: kReduceGroups x M N]
+struct TnPlan { TnCut cut; long long part, mid, total; };
+static TnPlan tn_plan(int M, int N, int P) {
+  const TnCut cut = tn_cut(P, tn_slabs(tn_tiles(M, N), P));
+  const long long mn = (long long)M * N;
+  return TnPlan{cut, 0, cut.alloc * mn, (cut.alloc + kReduceGroups) * mn};
 }
+extern "C" long long omnipq_gemm_tn_workspace_floats(int M, int N, int P) { return tn_plan(M, N, P).total; }
 
-static int gemm_tn_impl(int M, int N, int P, const void *A, int lda, const void *B, int ldb, float *C,
-                        float *workspace, float *colsum, const float *ba, const float *bb, void *stream,
-                        const void *W0 = nullptr, int ldw0 = 0);
+// One call of the plain family; the entry point states the route and has made the checks that are its own.
+enum TnRoute { kTnPlain, kTnAffine, kTnXyz };
+struct TnCall {
+  TnRoute route;
+  int M, N, P;
+  const void *A; int lda;
+  const void *B; int ldb;       // kTnXyz: X0 and its pitch ldx
+  float *C, *workspace;
+  float *colsum = nullptr;      // kTnPlain, kTnAffine: may be NULL
+  const float *ba = nullptr, *bb = nullptr;
+  const void *W0 = nullptr; int ldw0 = 0;       // kTnXyz
+};
+static int gemm_tn_run(const TnCall &c, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (c.M < 0 || c.N < 0 || c.P < 0) return OMNIPQ_EINVAL;
+  if (c.M == 0 || c.N == 0) return OMNIPQ_OK;
+  if (!c.A || !c.B || !c.C || !c.workspace || (c.M % 8) || (c.N % 8) || (c.lda % 8) || (c.route != kTnXyz && (c.ldb % 8)))
+    return OMNIPQ_EINVAL;
+  TnArgs g{c.M, c.N, c.P, c.lda, c.ldb, 0, (c.M + 127) / 128, (c.N + 127) / 128};
+  const RowPlan &rp = row_plan();                 // the calling thread's row plan, if it was made for this many positions
+  if (rp.rows_dev && rp.rows == c.P) g.rows_dev = rp.rows_dev;
+  const TnPlan plan = tn_plan(c.M, c.N, c.P);
+  g.p_chunk = plan.cut.p_chunk;
+  const dim3 grid(g.m_tiles * g.n_tiles * plan.cut.wgs_per_tile);
+  const e16_t *A = (const e16_t *)c.A, *B = (const e16_t *)c.B;
+  float *part = c.workspace + plan.part;
+  const bool reg = tn_debug().reg;
+  if (c.route == kTnXyz)
+    gemm_tn_xyz_kernel<<<grid, 256, 0, stream>>>(g, A, B, part, c.ba, c.bb, TnXyz{(const e16_t *)c.W0, c.ldw0});
+  else if (c.route == kTnAffine)
+    (tn_affine_kernel(reg))<<<grid, 256, 0, stream>>>(g, A, B, part, c.colsum, c.ba, c.bb);
+  else
+    (tn_plain_kernel(reg))<<<grid, 256, 0, stream>>>(g, A, B, part, c.colsum);
+  OMNIPQ_LAUNCH_CHECK();
+  return reduce_slabs(c.M * c.N / 4, plan.cut.used, part, c.workspace + plan.mid, c.C, stream);      // M, N multiples of 8
+}
 
 extern "C" int omnipq_gemm_tn_e16(int M, int N, int P, const void *A, int lda, const void *B, int ldb,
                                    float *C, float *workspace, const omnipq_row_plan *plan, void *stream) {
-  omnipq::PlanScope plan_scope_(plan);            // the row plan is an ARGUMENT of the call (no ambient state)
-  return gemm_tn_impl(M, N, P, A, lda, B, ldb, C, workspace, nullptr, nullptr, nullptr, stream);
+  PlanScope plan_scope_(plan);                    // the row plan is an ARGUMENT of the call (no ambient state)
+  return gemm_tn_run(TnCall{kTnPlain, M, N, P, A, lda, B, ldb, C, workspace}, stream);
 }
 
 // The same, and colsum[m] += sum_p A[p][m] (f32, zero or a running total on entry): weight and bias gradient
 // of a linear layer from one pass over dY.
 extern "C" int omnipq_gemm_tn_e16_colsum(int M, int N, int P, const void *A, int lda, const void *B, int ldb,
                                           float *C, float *workspace, float *colsum, const omnipq_row_plan *plan, void *stream) {
-  omnipq::PlanScope plan_scope_(plan);            // the row plan is an ARGUMENT of the call (no ambient state)
+  PlanScope plan_scope_(plan);
   if (!colsum) return OMNIPQ_EINVAL;
-  return gemm_tn_impl(M, N, P, A, lda, B, ldb, C, workspace, colsum, nullptr, nullptr, stream);
+  return gemm_tn_run(TnCall{kTnPlain, M, N, P, A, lda, B, ldb, C, workspace, colsum}, stream);
 }
 
 // C = A^T relu(ba .* B + bb): the B operand (activations of a conv+BN+ReLU layer) rebuilt from that layer's
@@ -992,9 +1074,9 @@ extern "C" int omnipq_gemm_tn_e16_colsum(int M, int N, int P, const void *A, int
 extern "C" int omnipq_gemm_tn_e16_affine(int M, int N, int P, const void *A, int lda, const void *B, int ldb,
                                           const float *ba, const float *bb, float *C, float *workspace,
                                           float *colsum, const omnipq_row_plan *plan, void *stream) {
-  omnipq::PlanScope plan_scope_(plan);            // the row plan is an ARGUMENT of the call (no ambient state)
+  PlanScope plan_scope_(plan);
   if (!ba || !bb) return OMNIPQ_EINVAL;
-  return gemm_tn_impl(M, N, P, A, lda, B, ldb, C, workspace, colsum, ba, bb, stream);
+  return gemm_tn_run(TnCall{kTnAffine, M, N, P, A, lda, B, ldb, C, workspace, colsum, ba, bb}, stream);
 }
 
 // C = A^T relu(ba .* (X0 W0^T) + bb): the weight gradient of the layer ABOVE a never-materialised first layer (see TnXyz).
@@ -1002,53 +1084,9 @@ extern "C" int omnipq_gemm_tn_e16_affine(int M, int N, int P, const void *A, int
 extern "C" int omnipq_gemm_tn_e16_xyz_affine(int M, int N, int P, const void *A, int lda, const void *X0, int ldx,
                                               const void *W0, int ldw0, const float *ba, const float *bb, float *C,
                                               float *workspace, const omnipq_row_plan *plan, void *stream) {
-  omnipq::PlanScope plan_scope_(plan);            // the row plan is an ARGUMENT of the call (no ambient state)
+  PlanScope plan_scope_(plan);
   if (!ba || !bb || !W0 || (ldx % 4) || (ldw0 % 4) || ldx < 3 || ldw0 < 3) return OMNIPQ_EINVAL;
-  return gemm_tn_impl(M, N, P, A, lda, X0, ldx, C, workspace, nullptr, ba, bb, stream, W0, ldw0);
-}
-
-static int gemm_tn_impl(int M, int N, int P, const void *A, int lda, const void *B, int ldb, float *C,
-                        float *workspace, float *colsum, const float *ba, const float *bb, void *stream,
-                        const void *W0, int ldw0) {
-  using namespace omnipq;
-  if (M < 0 || N < 0 || P < 0) return OMNIPQ_EINVAL;
-  if (M == 0 || N == 0) return OMNIPQ_OK;
-  if (!A || !B || !C || !workspace || (M % 8) || (N % 8) || (lda % 8) || (!W0 && (ldb % 8))) return OMNIPQ_EINVAL;
-  TnArgs g{M, N, P, lda, ldb, 0, (M + 127) / 128, (N + 127) / 128};
-  {
-    const RowPlan &rp = row_plan();               // the calling thread's row plan, if it was made for this many positions
-    if (rp.rows_dev && rp.rows == P) g.rows_dev = rp.rows_dev;
-  }
-  const int tiles = g.m_tiles * g.n_tiles;
-  const int slabs = tn_slabs(tiles, P);
-  g.p_chunk = (((P + slabs - 1) / slabs) + TBK - 1) / TBK * TBK;
-  const int used = P > 0 ? (P + g.p_chunk - 1) / g.p_chunk : 1;
-  dim3 grid(tiles * ((used + 7) / 8) * 8);
-  if (W0)
-    gemm_tn_xyz_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)A, (const e16_t *)B, workspace, ba, bb,
-                                                            TnXyz{(const e16_t *)W0, ldw0});
-  else if (ba)
-    (g_tn_debug & 1 ? gemm_tn_affine_kernel<true> : gemm_tn_affine_kernel<false>)<<<grid, 256, 0, (hipStream_t)stream>>>(
-        g, (const e16_t *)A, (const e16_t *)B, workspace, colsum, ba, bb);
-  else
-    (g_tn_debug & 1 ? gemm_tn_kernel<true> : gemm_tn_kernel<false>)<<<grid, 256, 0, (hipStream_t)stream>>>(
-        g, (const e16_t *)A, (const e16_t *)B, workspace, colsum);
-  OMNIPQ_LAUNCH_CHECK();
-  const int n4 = M * N / 4;        // M, N multiples of 8
-  const f32x4 *part = reinterpret_cast<const f32x4 *>(workspace);
-  f32x4 *mid = reinterpret_cast<f32x4 *>(workspace + (size_t)slabs * M * N);
-  if (used > 2 * kReduceGroups) {
-    slab_reduce_kernel<<<dim3((n4 + 255) / 256, kReduceGroups), 256, 0, (hipStream_t)stream>>>(n4, used, kReduceGroups,
-                                                                                           part, mid);
-    OMNIPQ_LAUNCH_CHECK();
-    slab_reduce_kernel<<<dim3((n4 + 255) / 256, 1), 256, 0, (hipStream_t)stream>>>(n4, kReduceGroups, 1, mid,
-                                                                               reinterpret_cast<f32x4 *>(C));
-  } else {
-    slab_reduce_kernel<<<dim3((n4 + 255) / 256, 1), 256, 0, (hipStream_t)stream>>>(n4, used, 1, part,
-                                                                               reinterpret_cast<f32x4 *>(C));
-  }
-  OMNIPQ_LAUNCH_CHECK();
-  return OMNIPQ_OK;
+  return gemm_tn_run(TnCall{kTnXyz, M, N, P, A, lda, X0, ldx, C, workspace, nullptr, ba, bb, W0, ldw0}, stream);
 }
 
 // ---- last layer of a planned stage: [hit | w X2]^T X2 (see gemm_tn_dz_kernel) -------------------------------------------
@@ -1063,85 +1101,52 @@ static int tn_dz_slabs(int tiles, int P) {
   return slabs < 1 ? 1 : (int)slabs;
 }
 
-extern "C" long long omnipq_gemm_tn_dz_workspace_floats(int C3, int N, int P) {
-  const long long M = (long long)C3 + N;
-  const int tiles = (int)(M / 128) * ((N + 127) / 128);
-  const long long slabs = tn_dz_slabs(tiles, P);
-  // [R: M N] [mid: kReduceGroups M N] [slabs: slabs M N] [cs: slabs M]
-  return M * N * (1 + omnipq::kReduceGroups + slabs) + slabs * M;
+// workspace (offsets in floats), M = C3 + N: [R: M N] [mid: kReduceGroups x M N] [part: alloc x M N] [cs: alloc x M]
+struct TnDzPlan { TnCut cut; long long R, mid, part, cs, total; };
+static TnDzPlan tn_dz_plan(int C3, int N, int P) {
+  const long long M = (long long)C3 + N, mn = M * N;
+  const TnCut cut = tn_cut(P, tn_dz_slabs((int)(M / 128) * ((N + 127) / 128), P));
+  const long long part = mn * (1 + kReduceGroups), cs = part + mn * cut.alloc;
+  return TnDzPlan{cut, 0, mn, part, cs, cs + (long long)cut.alloc * M};
 }
+extern "C" long long omnipq_gemm_tn_dz_workspace_floats(int C3, int N, int P) { return tn_dz_plan(C3, N, P).total; }
 
 extern "C" int omnipq_gemm_tn_dz(int C3, int N, int P, const void *Y2, int ldb, const float *ba, const float *bb,
                                   const unsigned *hot, const int *unit_src, int nsample, float *workspace, int *slabs_out,
-                                  long long *cs_offset_out, const omnipq_row_plan *plan, void *stream) {
-  omnipq::PlanScope plan_scope_(plan);
-  using namespace omnipq;
+                                  long long *cs_offset_out, const omnipq_row_plan *plan_, void *stream) {
+  PlanScope plan_scope_(plan_);
   if (C3 <= 0 || N <= 0 || P <= 0 || (C3 % 128) || (N % 128) || (ldb % 8) || ldb < N) return OMNIPQ_EINVAL;
   if (!Y2 || ((ba != nullptr) != (bb != nullptr)) || !hot || !unit_src || !workspace || nsample < 8 || (nsample & (nsample - 1)))
     return OMNIPQ_EINVAL;
   const RowPlan &rp = row_plan();
   if (!rp.rows_dev || !rp.row_w || rp.rows != P) return OMNIPQ_EINVAL;
   const int M = C3 + N;
-  TnArgs g{M, N, P, ldb, ldb, 0, M / 128, N / 128};
+  const TnDzPlan plan = tn_dz_plan(C3, N, P);
+  TnArgs g{M, N, P, ldb, ldb, plan.cut.p_chunk, M / 128, N / 128};
   g.rows_dev = rp.rows_dev;
-  const int tiles = g.m_tiles * g.n_tiles;
-  const int slabs = tn_dz_slabs(tiles, P);
-  g.p_chunk = (((P + slabs - 1) / slabs) + TBK - 1) / TBK * TBK;
-  const int used = (P + g.p_chunk - 1) / g.p_chunk;
   g.colsum_rows = 1;
-  g.debug = g_tn_debug;                           // (ablation bits for tools/sa_ab.py --capi omnipq_tn_debug: 2 no fetches after
-                                                  // the prologue, 4 no fragment reads / MFMAs, 16 no hot-word DMA)
+  g.debug = tn_debug().kernel;
   int sh = 0;
   while ((1 << sh) < nsample) ++sh;
-  const size_t mn = (size_t)M * N;
-  float *R = workspace, *mid = workspace + mn, *part = workspace + mn * (1 + kReduceGroups);
-  float *cs = part + mn * (size_t)slabs;
-  TnDz dz{hot, unit_src, rp.row_w, C3, sh};
+  float *part = workspace + plan.part;
   // (every slab in use writes its partial column-sum row, also one that holds no rows in use: zeros)
-  gemm_tn_dz_kernel<<<dim3(tiles * ((used + 7) / 8) * 8), 256, 0, (hipStream_t)stream>>>(g, (const e16_t *)Y2, part, cs, ba, bb,
-                                                                                       dz);
+  gemm_tn_dz_kernel<<<dim3(g.m_tiles * g.n_tiles * plan.cut.wgs_per_tile), 256, 0, (hipStream_t)stream>>>(
+      g, (const e16_t *)Y2, part, workspace + plan.cs, ba, bb, TnDz{hot, unit_src, rp.row_w, C3, sh});
   OMNIPQ_LAUNCH_CHECK();
-  const int n4 = (int)(mn / 4);
-  const f32x4 *part4 = reinterpret_cast<const f32x4 *>(part);
-  if (used > 2 * kReduceGroups) {
-    slab_reduce_kernel<<<dim3((n4 + 255) / 256, kReduceGroups), 256, 0, (hipStream_t)stream>>>(
-        n4, used, kReduceGroups, part4, reinterpret_cast<f32x4 *>(mid));
-    OMNIPQ_LAUNCH_CHECK();
-    slab_reduce_kernel<<<dim3((n4 + 255) / 256, 1), 256, 0, (hipStream_t)stream>>>(
-        n4, kReduceGroups, 1, reinterpret_cast<const f32x4 *>(mid), reinterpret_cast<f32x4 *>(R));
-  } else {
-    slab_reduce_kernel<<<dim3((n4 + 255) / 256, 1), 256, 0, (hipStream_t)stream>>>(n4, used, 1, part4,
-                                                                               reinterpret_cast<f32x4 *>(R));
-  }
-  OMNIPQ_LAUNCH_CHECK();
-  if (slabs_out) *slabs_out = used;
-  if (cs_offset_out) *cs_offset_out = (long long)(cs - workspace);
-  return OMNIPQ_OK;
+  if (slabs_out) *slabs_out = plan.cut.used;
+  if (cs_offset_out) *cs_offset_out = plan.cs;
+  return reduce_slabs((int)((size_t)M * N / 4), plan.cut.used, part, workspace + plan.mid, workspace + plan.R, (hipStream_t)stream);
 }
 
-// ---- grouped weight gradients ---------------------------------------------------------------------------
-// Mirrors include/omnipq_sa.h: omnipq_tn_problem.
-struct omnipq_tn_problem_ {
-  const void *A, *B;        // bf16 [P][M] (pitch lda), [P][N] (pitch ldb)
-  float *colsum;            // NULL or float[M]: += column sums of A
-  float *out;               // f32 [out_rows][out_cols], pitch out_ld: the cropped C
-  int M, N, P, lda, ldb;
-  int out_rows, out_cols, out_ld;
-  int flags;                // bit 0: out += C
-  int rot;                  // rot | split << 8 (0: none): out column c = C column (c < rot ? split + c : c - rot)
-  const float *ba, *bb;     // NULL, or: B stands for relu(ba .* B + bb)
-  const int *rows_dev;      // NULL, or the row plan of the stage the operands belong to: positions in use (device memory)
-};
-
+// ---- grouped weight gradients (include/omnipq_sa.h: omnipq_tn_problem) ------------------------------------------------------
 // Positions per workgroup in a grouped launch, the same for every problem of the call (balance): at least 16 K-steps
 // (the ~115 per-point layers of 4096 rows: the grid is full anyway), and for calls that carry the SA stages' layers (up to
 // 1 M rows each) as many as it takes to bring the call down to ~2048 workgroups (~8192 without such layers) -- a workgroup leaves a 64 KB f32 slab
 // behind, the bytes of four K-steps of operands, so slabs of 16 steps on a million-row problem would move more than the
 // operands do.
-static int tng_chunk(int nprob, const omnipq_tn_problem_ *pr) {
+static int tng_chunk(int nprob, const omnipq_tn_problem *pr) {
   long long tile_steps = 0;
-  for (int i = 0; i < nprob; ++i)
-    tile_steps += (long long)((pr[i].M + 127) / 128) * ((pr[i].N + 127) / 128) * ((pr[i].P + omnipq::TBK - 1) / omnipq::TBK);
+  for (int i = 0; i < nprob; ++i) tile_steps += (long long)tn_tiles(pr[i].M, pr[i].N) * ((pr[i].P + TBK - 1) / TBK);
   // ~8192 workgroups for the calls of per-point layers (4096 .. 8192 rows each; they run on a side stream underneath the
   // backbone's backward pass: step 11.15 / 10.85 / 10.76 / 10.81 ms with ~2048 / 4096 / 8192 / 16384),
   // ~2048 for calls that carry SA-stage layers (measured on their 13-problem call, tools/bench_tn_grouped.py: slabs of
@@ -1149,11 +1154,11 @@ static int tng_chunk(int nprob, const omnipq_tn_problem_ *pr) {
   int max_p = 0;
   for (int i = 0; i < nprob; ++i) max_p = pr[i].P > max_p ? pr[i].P : max_p;
   long long target = max_p >= 65536 ? 2048 : 8192;
-  if ((g_tn_debug >> 8) & 0xFF) target = 256LL * ((g_tn_debug >> 8) & 0xFF);      // (A/B runs: tools/bench_tn_grouped.py --target)
+  if (tn_debug().wg_target) target = tn_debug().wg_target;      // (A/B runs)
   long long steps = (tile_steps + target - 1) / target;
   if (steps < 16) steps = 16;
   if (steps > 1024) steps = 1024;
-  return omnipq::TBK * (int)steps;
+  return TBK * (int)steps;
 }
 
 static int tng_slabs(int P, int chunk) {
@@ -1161,23 +1166,46 @@ static int tng_slabs(int P, int chunk) {
   return s < 1 ? 1 : s;
 }
 
-extern "C" long long omnipq_gemm_tn_grouped_workspace_floats(int nprob, const void *probs_) {
-  const omnipq_tn_problem_ *pr = (const omnipq_tn_problem_ *)probs_;
-  const int chunk = tng_chunk(nprob, pr);
+// workspace (offsets in floats), in problem order: problem i has [part: alloc_i x M N] and, with a colsum, behind it
+// [column-sum partial rows: alloc_i x M].  off (may be NULL): receives every problem's offset; returns the total.
+static long long tng_layout(int nprob, const omnipq_tn_problem *pr, int chunk, long long *off) {
   long long total = 0;
   for (int i = 0; i < nprob; ++i) {
-    const long long slabs = tng_slabs(pr[i].P, chunk);
-    total += slabs * pr[i].M * pr[i].N + (pr[i].colsum ? slabs * pr[i].M : 0);      // + the column-sum partial rows
+    if (off) off[i] = total;
+    const long long alloc = tng_slabs(pr[i].P, chunk);
+    total += alloc * pr[i].M * pr[i].N + (pr[i].colsum ? alloc * pr[i].M : 0);
   }
   return total;
 }
+extern "C" long long omnipq_gemm_tn_grouped_workspace_floats(int nprob, const void *probs) {
+  const omnipq_tn_problem *pr = (const omnipq_tn_problem *)probs;
+  return tng_layout(nprob, pr, tng_chunk(nprob, pr), nullptr);
+}
 
-extern "C" int omnipq_gemm_tn_grouped(int nprob, const void *probs_, float *workspace, void *stream) {
-  using namespace omnipq;
-  const omnipq_tn_problem_ *pr = (const omnipq_tn_problem_ *)probs_;
+// the launch record of problem q, whose slabs start at `part`; wg / blk: the launch's running workgroup and reduction-block counts
+static void tng_item(TnGroupItem &it, const omnipq_tn_problem &q, float *part, int chunk, int &wg, int &blk) {
+  const TnCut cut = tn_cut(q.P, tng_slabs(q.P, chunk));
+  it.A = (const e16_t *)q.A; it.B = (const e16_t *)q.B;
+  it.part = part; it.colsum = q.colsum; it.out = q.out;
+  it.ba = q.ba; it.bb = q.bb; it.rows_dev = q.rows_dev;
+  it.M = q.M; it.N = q.N; it.P = q.P; it.lda = q.lda; it.ldb = q.ldb;
+  it.m_tiles = (q.M + 127) / 128; it.n_tiles = (q.N + 127) / 128;
+  it.p_chunk = cut.p_chunk; it.slabs = cut.used;
+  it.wg_begin = wg;
+  wg += it.m_tiles * it.n_tiles * cut.wgs_per_tile;
+  it.out_rows = q.out_rows; it.out_cols = q.out_cols; it.out_ld = q.out_ld;
+  it.blk_begin = blk;
+  blk += (q.out_rows * q.out_cols + 255) / 256 + (q.colsum ? (q.M + 255) / 256 : 0);
+  it.flags = (q.flags & 0xff) | (cut.alloc << 8);
+  it.rot = q.rot;
+}
+
+extern "C" int omnipq_gemm_tn_grouped(int nprob, const void *probs, float *workspace, void *stream_) {
+  const omnipq_tn_problem *pr = (const omnipq_tn_problem *)probs;
+  hipStream_t stream = (hipStream_t)stream_;
   if (nprob < 0 || (nprob > 0 && (!pr || !workspace))) return OMNIPQ_EINVAL;
   for (int i = 0; i < nprob; ++i) {
-    const omnipq_tn_problem_ &q = pr[i];
+    const omnipq_tn_problem &q = pr[i];
     if (q.M <= 0 || q.N <= 0 || q.P < 0 || (q.P > 0 && (!q.A || !q.B)) || !q.out || (q.M % 8) || (q.N % 8) || (q.lda % 8) || (q.ldb % 8) ||
         q.out_rows <= 0 || q.out_cols <= 0 || q.out_rows > q.M || q.out_cols > q.N || q.out_ld < q.out_cols ||
         ((q.ba != nullptr) != (q.bb != nullptr)) || q.rot < 0 || (q.rot >> 8) + (q.rot & 255) > q.N ||
@@ -1185,57 +1213,23 @@ extern "C" int omnipq_gemm_tn_grouped(int nprob, const void *probs_, float *work
       return OMNIPQ_EINVAL;
   }
   const int chunk = tng_chunk(nprob, pr);
-  // workspace offsets follow the problem order (as omnipq_gemm_tn_grouped_workspace_floats counts them)
-  size_t off = 0;
-  static thread_local std::vector<size_t> ws_off;
+  static thread_local std::vector<long long> ws_off;
   ws_off.resize(nprob);
-  for (int i = 0; i < nprob; ++i) {
-    ws_off[i] = off;
-    const size_t slabs_i = (size_t)tng_slabs(pr[i].P, chunk);
-    off += slabs_i * pr[i].M * pr[i].N + (pr[i].colsum ? slabs_i * pr[i].M : 0);
-  }
+  tng_layout(nprob, pr, chunk, ws_off.data());
+  const TnDebug dbg = tn_debug();
   for (int pass = 0; pass < 2; ++pass) {              // plain problems, then the ones with a transformed B operand
     int next = 0;
     for (;;) {
       TnGroupArgs a;
       a.n = 0;
-      a.pad_ = g_tn_debug;
+      a.debug = dbg.kernel;
       int wg = 0, blk = 0;
-      while (next < nprob && a.n < kGroupMax) {
-        const omnipq_tn_problem_ &q = pr[next];
-        if ((q.ba != nullptr) == (pass == 1)) {
-          TnGroupItem &it = a.item[a.n++];
-          it.A = (const e16_t *)q.A;
-          it.B = (const e16_t *)q.B;
-          it.part = workspace + ws_off[next];
-          it.colsum = q.colsum;
-          it.out = q.out;
-          it.ba = q.ba;
-          it.bb = q.bb;
-          it.rows_dev = q.rows_dev;
-          it.M = q.M; it.N = q.N; it.P = q.P; it.lda = q.lda; it.ldb = q.ldb;
-          it.m_tiles = (q.M + 127) / 128;
-          it.n_tiles = (q.N + 127) / 128;
-          const int slabs = tng_slabs(q.P, chunk);
-          it.p_chunk = (((q.P + slabs - 1) / slabs) + TBK - 1) / TBK * TBK;
-          it.slabs = q.P > 0 ? (q.P + it.p_chunk - 1) / it.p_chunk : 1;
-          it.wg_begin = wg;
-          wg += it.m_tiles * it.n_tiles * ((it.slabs + 7) / 8) * 8;
-          it.out_rows = q.out_rows; it.out_cols = q.out_cols; it.out_ld = q.out_ld;
-          it.blk_begin = blk;
-          blk += (q.out_rows * q.out_cols + 255) / 256 + (q.colsum ? (q.M + 255) / 256 : 0);
-          it.flags = (q.flags & 0xff) | (slabs << 8);
-          it.rot = q.rot;
-        }
-        ++next;
-      }
+      for (; next < nprob && a.n < kGroupMax; ++next)
+        if ((pr[next].ba != nullptr) == (pass == 1)) tng_item(a.item[a.n++], pr[next], workspace + ws_off[next], chunk, wg, blk);
       if (a.n == 0) break;
-      if (pass == 0)
-        (g_tn_debug & 1 ? gemm_tn_grouped_kernel<false, true> : gemm_tn_grouped_kernel<false, false>)<<<dim3(wg), 256, 0, (hipStream_t)stream>>>(a);
-      else
-        (g_tn_debug & 1 ? gemm_tn_grouped_kernel<true, true> : gemm_tn_grouped_kernel<true, false>)<<<dim3(wg), 256, 0, (hipStream_t)stream>>>(a);
+      tn_grouped_kernel(pass == 1, dbg.reg)<<<dim3(wg), 256, 0, stream>>>(a);
       OMNIPQ_LAUNCH_CHECK();
-      tn_grouped_reduce_kernel<<<dim3(blk), 256, 0, (hipStream_t)stream>>>(a);
+      tn_grouped_reduce_kernel<<<dim3(blk), 256, 0, stream>>>(a);
       OMNIPQ_LAUNCH_CHECK();
     }
   }
