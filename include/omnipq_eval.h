@@ -51,6 +51,26 @@ int omnipq_box_corners(long long n, const float *center, const double *size, con
 int omnipq_points_in_boxes(int b, int n, int k, const float *xyz, const float *center, const double *size,
                            const float *heading, int min_points, unsigned char *nonempty, void *stream);
 
+/* Oriented-box IoU of the detection metrics (utils/box_util.py:93-118 `box3d_iou`, as omni-pq_amd/eval_det.py restates it;
+ * csrc/eval_iou.hip).  A box is its corners (8, 3) f64 in get_3d_box's layout: rows 0-3 the top face, 4-7 the bottom face,
+ * up = -Y.  Everything is f64 and nothing is contracted: the footprints (x, z) of corners 3, 2, 1, 0 are clipped with the
+ * host's strict `inside` test and the host's intersection point (n1, n2, the reciprocal n3, two multiplications), the areas
+ * are shoelace areas, the heights and volumes are formed as on the host.  Only the order in which the shoelace sums add
+ * their terms differs from numpy's dot.
+ *
+ * Elementwise: iou3d[i], iou2d[i] (n) of a8[i] against b8[i] ((n, 8, 3) each; a8 is box3d_iou's first argument).  Either
+ * output may be NULL, not both. */
+int omnipq_obb_iou_pairs(long long n, const double *a8, const double *b8, double *iou3d, double *iou2d, void *stream);
+
+/* The inner loop of utils/eval_det.py:75-161 `eval_det_cls` for every detection at once.  Detection i, pred8 (n_pred, 8, 3),
+ * belongs to segment pred_seg[i] in [0, n_seg) -- one (class, scan) group -- whose ground-truth boxes are
+ * gt8[seg_start[s] .. seg_start[s + 1]) of gt8 (n_gt, 8, 3); seg_start has n_seg + 1 entries.  Per detection: start at
+ * (-inf, -1), visit the segment's boxes in order, replace on iou3d(pred, gt) > ovmax.  So the first maximum wins among equal
+ * values, a NaN overlap never wins, an empty segment yields (-inf, -1).  ovmax (n_pred) f64, jmax (n_pred) int32: the index
+ * WITHIN the segment.  The greedy matching that consumes the two stays on the host (eval_det.match_from_best). */
+int omnipq_obb_iou_best(long long n_pred, const double *pred8, const int *pred_seg, int n_seg, const long long *seg_start,
+                        long long n_gt, const double *gt8, double *ovmax, int *jmax, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

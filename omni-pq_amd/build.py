@@ -37,7 +37,10 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 # out and back around the matrix instructions of EVERY key block: 64 v_accvgpr_read / _write + 26 v_mov of the ~570 VALU
 # instructions of a forward iteration.  With the flag: no copies, 160 / 184 / 204 registers instead of 192 / 212 / 236
 # (forward: three waves per SIMD instead of two).
-EXTRA = {"fps.hip": ["-fno-slp-vectorize"], "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+# eval_iou.hip: restates eval_det.box3d_iou in f64 product by product; a fused multiply-add would change an `inside`
+# decision of the clipping.  COMMON says so already: the file's own entry keeps that true should COMMON ever change.
+EXTRA = {"fps.hip": ["-fno-slp-vectorize"], "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+         "eval_iou.hip": ["-ffp-contract=off"]}
 
 
 def hipcc():

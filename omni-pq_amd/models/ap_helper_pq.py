@@ -14,6 +14,9 @@ all proposals (omnipq_parse_quads), one launch suppresses per scene (omnipq_nms3
 device-to-host copy; only the ragged Python lists the calculators consume are assembled on the host, as they must be.
 QUADAPCalculator itself is host bookkeeping in the reference too (lists of 4 x 3 corner arrays per scan) and stays so.
 There is no CPU path for the parsing: CPU tensors are refused (oracle/ap_oracle.py is the tests' CPU twin).
+Both calculators take `iou="device"` (default "host", the reference's route): compute_metrics then gets the box overlaps from
+csrc/eval_iou.hip through eval_det.eval_det_device, and compute_metrics_at(calculator, thresholds) scores several IoU thresholds
+from one pass.
 """
 import ctypes
 
@@ -278,15 +281,18 @@ def parse_groundtruths(end_points, config_dict):
 class APCalculator(object):
     ''' Calculating Average Precision '''
 
-    def __init__(self, ap_iou_thresh=0.25, class2type_map=None):
+    def __init__(self, ap_iou_thresh=0.25, class2type_map=None, iou="host"):
         """
         Args:
             ap_iou_thresh: float between 0 and 1.0
                 IoU threshold to judge whether a prediction is positive.
             class2type_map: [optional] dict {class_int:class_name}
+            iou: "host" (the reference's route, the default) or "device": the box overlaps of compute_metrics on the
+                kernels of csrc/eval_iou.hip (eval_det.eval_det_device)
         """
         self.ap_iou_thresh = ap_iou_thresh
         self.class2type_map = class2type_map
+        self.iou = _iou_route(iou)
         self.reset()
 
     def step(self, batch_pred_map_cls, batch_gt_map_cls):
@@ -300,6 +306,8 @@ class APCalculator(object):
 
     def compute_metrics(self):
         """ Use accumulated predictions and groundtruths to compute Average Precision. """
+        if self.iou == "device":
+            return compute_metrics_at(self, (self.ap_iou_thresh,))[0]
         rec, prec, ap = eval_det.eval_det(self.pred_map_cls, self.gt_map_cls, ovthresh=self.ap_iou_thresh,
                                           get_iou_func=eval_det.get_iou_obb)
         return _metrics_dict(rec, ap, self.class2type_map)
@@ -308,6 +316,27 @@ class APCalculator(object):
         self.gt_map_cls = {}          # {scan_id: [(classname, bbox)]}
         self.pred_map_cls = {}        # {scan_id: [(classname, bbox, score)]}
         self.scan_cnt = 0
+
+
+def _iou_route(iou):
+    if iou not in ("host", "device"):
+        raise ValueError(f"ap_helper_pq: iou must be 'host' or 'device', not {iou!r}")
+    return iou
+
+
+def compute_metrics_at(calculator, thresholds):
+    """The metric dicts of `calculator.compute_metrics()` at every IoU threshold of `thresholds`, from ONE pass over the box
+    overlaps of its accumulated lists (they do not depend on the threshold; the reference keeps one calculator per
+    threshold and computes them once each).  The pass runs where the calculator's `iou` says: "device" on the kernels of
+    csrc/eval_iou.hip, "host" through eval_det.box3d_iou."""
+    thresholds = list(thresholds)
+    if calculator.iou == "device":
+        triples = eval_det.eval_det_device(calculator.pred_map_cls, calculator.gt_map_cls, ovthresh=thresholds)
+    else:
+        pack = eval_det.pack_segments(calculator.pred_map_cls, calculator.gt_map_cls)
+        ovmax, jmax = eval_det.best_on_host(pack)
+        triples = [eval_det.eval_from_best(pack, ovmax, jmax, t) for t in thresholds]
+    return [_metrics_dict(rec, ap, calculator.class2type_map) for rec, _, ap in triples]
 
 
 def _metrics_dict(rec, ap, class2type_map):
@@ -329,15 +358,17 @@ def _metrics_dict(rec, ap, class2type_map):
 class QUADAPCalculator(object):
     ''' Average precision and F1 of the predicted layout quads, accumulated over the scans of an evaluation run '''
 
-    def __init__(self, ap_iou_thresh=0.25, class2type_map=None, logger=None, logger_i=None):
+    def __init__(self, ap_iou_thresh=0.25, class2type_map=None, logger=None, logger_i=None, iou="host"):
         """
         Args:
             ap_iou_thresh: float between 0 and 1.0
                 IoU threshold to judge whether a prediction is positive.
             class2type_map: [optional] dict {class_int:class_name}
+            iou: "host" (the default) or "device", as for APCalculator
         """
         self.ap_iou_thresh = ap_iou_thresh
         self.class2type_map = class2type_map
+        self.iou = _iou_route(iou)
         self.logger = logger
         self.I = logger_i
         self.reset()
@@ -358,6 +389,8 @@ class QUADAPCalculator(object):
 
     def compute_metrics(self):
         """ Average precision / recall of the accumulated quads as oriented boxes (IoU of get_iou_obb). """
+        if self.iou == "device":
+            return compute_metrics_at(self, (self.ap_iou_thresh,))[0]
         rec, prec, ap = eval_det.eval_det(self.pred_map_cls, self.gt_map_cls, ovthresh=self.ap_iou_thresh,
                                           get_iou_func=eval_det.get_iou_obb)
         return _metrics_dict(rec, ap, self.class2type_map)
