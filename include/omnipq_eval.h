@@ -71,6 +71,52 @@ int omnipq_obb_iou_pairs(long long n, const double *a8, const double *b8, double
 int omnipq_obb_iou_best(long long n_pred, const double *pred8, const int *pred_seg, int n_seg, const long long *seg_start,
                         long long n_gt, const double *gt8, double *ovmax, int *jmax, void *stream);
 
+/* ---- packed detections (csrc/detect.hip) ---------------------------------------------------------------
+ * What models/ap_helper_pq.py:73-236 `parse_predictions` computes in front of the suppression, for all b * k proposals in one
+ * launch, one thread per proposal.  Inputs f32, contiguous: center (b, k, 3), heading_scores / heading_residuals (b, k, nh),
+ * size_scores (b, k, ns), size_residuals (b, k, ns, 3), sem_cls_scores (b, k, ncls), objectness_scores (b, k, 2); mean_size
+ * (ns, 3) f64.  heading_rule: 0 = the dataset's class2angle returns 0 (axis-aligned boxes), 1 = class * 2 pi / nh + residual
+ * folded into (-pi, pi].  Outputs:
+ *   heading_cls, size_cls, sem_cls (b, k) i32   the first maximum of the row; a NaN counts as larger than every number, the
+ *                                               first NaN wins (torch.argmax on the device)
+ *   size     (b, k, 3) f64   mean_size[size_cls] + (double)residual[size_cls]
+ *   heading  (b, k)    f32   rule 1: (float)(a > pi ? a - 2 pi : a), a = (double)cls * (2 pi / nh) + (double)residual[cls],
+ *                            product and sum rounded separately; rule 0: 0
+ *   obj_prob (b, k)    f32   1 / (1 + exp(-logit 1)) evaluated in f64, rounded once
+ *   sem_prob (b, k, ncls) f32 or NULL   softmax in f64 (row maximum subtracted, sum in index order), rounded once
+ *   corners8 (b, k, 8, 3) f64, aabb (b, k, 6) f64   as omnipq_box_corners (the same device function); with bev != 0 the
+ *                            second axis of aabb is [0, 1]: bird's-eye-view suppression through omnipq_nms3d*
+ * Every output but sem_prob is required.  nh, ns, ncls in [1, omnipq_decode_boxes_max_classes()], k <= 4096 (the limit of
+ * omnipq_nms3d); anything else is OMNIPQ_EINVAL.  b == 0 or k == 0: nothing is launched. */
+int omnipq_decode_boxes(int b, int k, int nh, int ns, int ncls, const float *center, const float *heading_scores,
+                        const float *heading_residuals, const float *size_scores, const float *size_residuals,
+                        const float *sem_cls_scores, const float *objectness_scores, const double *mean_size,
+                        int heading_rule, int bev, int *heading_cls, int *size_cls, int *sem_cls, double *size,
+                        float *heading, float *obj_prob, float *sem_prob, double *corners8, double *aabb, void *stream);
+
+/* The largest nh, ns and ncls omnipq_decode_boxes and omnipq_pack_boxes accept (host only). */
+int omnipq_decode_boxes_max_classes(void);
+
+/* Stable compaction of the proposals a scene keeps, one workgroup per scene, no atomics.  Proposal j of scene s is selected
+ * when keep[s, j] != 0 && score[s, j] > conf (strict, f32); the selected ones are written in increasing j to rows
+ * [0, count[s]) of the outputs:
+ *   count (b) i32; index (b, k) i32 = j; out_cls (b, k) i32 = cls[s, j]; out_score (b, k) f32 = score[s, j];
+ *   out_corners8 (b, k, 8, 3) f64 = corners8[s, j]; out_sem_prob (b, k, ncls) f32 = sem_prob[s, j] (both NULL: not wanted)
+ * Rows [count[s], k) hold index -1 and zeros everywhere else, so every output byte is a function of the inputs.
+ * keep (b, k) u8, score (b, k) f32, cls (b, k) i32, corners8 (b, k, 8, 3) f64.  k <= 4096, ncls as above (ignored without
+ * sem_prob); anything else, or sem_prob without out_sem_prob, is OMNIPQ_EINVAL.  b == 0 or k == 0: nothing is launched. */
+int omnipq_pack_boxes(int b, int k, int ncls, const unsigned char *keep, const float *score, float conf, const int *cls,
+                      const double *corners8, const float *sem_prob, int *count, int *index, int *out_cls, float *out_score,
+                      double *out_corners8, float *out_sem_prob, void *stream);
+
+/* The same for the quads, on the outputs of omnipq_parse_quads and omnipq_nms3d, two lists per scene:
+ *   the AP list  keep && prob > conf:        count (b), index (b, k), out_score (b, k) f32, out_corners8 (b, k, 8, 3) f64
+ *   the F1 list  keep && prob > quad_thres:  count_f1 (b), index_f1 (b, k), out_verts4 (b, k, 4, 3) f32
+ * Tail rows as above.  k <= 4096. */
+int omnipq_pack_quads(int b, int k, const unsigned char *keep, const float *prob, float conf, float quad_thres,
+                      const double *corners8, const float *verts4, int *count, int *index, float *out_score,
+                      double *out_corners8, int *count_f1, int *index_f1, float *out_verts4, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,8 +39,10 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 # (forward: three waves per SIMD instead of two).
 # eval_iou.hip: restates eval_det.box3d_iou in f64 product by product; a fused multiply-add would change an `inside`
 # decision of the clipping.  COMMON says so already: the file's own entry keeps that true should COMMON ever change.
+# detect.hip: the decoded heading is a product and a sum in f64, each rounded on its own, and its corners must keep the bits
+# of eval_ops.hip's (csrc/box_geom.h); the same reason for an entry of its own.
 EXTRA = {"fps.hip": ["-fno-slp-vectorize"], "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
-         "eval_iou.hip": ["-ffp-contract=off"]}
+         "eval_iou.hip": ["-ffp-contract=off"], "detect.hip": ["-ffp-contract=off"]}
 
 
 def hipcc():

@@ -1,6 +1,7 @@
 // Evaluation-side consumer of the layout branch (include/omnipq_eval.h): quad proposals -> oriented thin boxes, their
 // axis-aligned extents, the four F1 corners, the quad probability; greedy 3D NMS per scene.
 // Reference: models/ap_helper_pq.py:323-460, utils/box_util.py:185-233, utils/nms.py:77-113.
+#include "box_geom.h"
 #include "common.h"
 #include "omnipq_eval.h"
 
@@ -75,28 +76,8 @@ __global__ __launch_bounds__(256) void box_corners_kernel(long long n, const flo
                                                           double *__restrict__ corners8, double *__restrict__ aabb) {
   const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
   if (r >= n) return;
-  const float ang = heading ? heading[r] : 0.f;
-  const double c = (double)cosf(ang), s = (double)sinf(ang);
-  const double l = size[r * 3], w = size[r * 3 + 1], h = size[r * 3 + 2];
-  const double ccx = (double)center[r * 3], ccy = (double)(-center[r * 3 + 2]), ccz = (double)center[r * 3 + 1];
-  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const double x = ((i & 3) < 2 ? l : -l) / 2;
-    const double y = (i < 4 ? h : -h) / 2;
-    const double z = ((i & 3) == 0 || (i & 3) == 3 ? w : -w) / 2;
-    const double p[3] = {c * x + s * z + ccx, y + ccy, -s * x + c * z + ccz};
-    for (int a = 0; a < 3; ++a) {
-      if (corners8) corners8[(r * 8 + i) * 3 + a] = p[a];
-      lo[a] = fmin(lo[a], p[a]);
-      hi[a] = fmax(hi[a], p[a]);
-    }
-  }
-  if (aabb)
-    for (int a = 0; a < 3; ++a) {
-      aabb[r * 6 + a] = lo[a];
-      aabb[r * 6 + 3 + a] = hi[a];
-    }
+  box_corners_of(heading ? heading[r] : 0.f, size[r * 3], size[r * 3 + 1], size[r * 3 + 2], center[r * 3], center[r * 3 + 1],
+                 center[r * 3 + 2], corners8 ? corners8 + r * 24 : nullptr, aabb ? aabb + r * 6 : nullptr);
 }
 
 // nonempty[b][k] = the box holds at least `min_points` of the scene's points.  One workgroup per box; a point is inside when

@@ -17,6 +17,8 @@ There is no CPU path for the parsing: CPU tensors are refused (oracle/ap_oracle.
 Both calculators take `iou="device"` (default "host", the reference's route): compute_metrics then gets the box overlaps from
 csrc/eval_iou.hip through eval_det.eval_det_device, and compute_metrics_at(calculator, thresholds) scores several IoU thresholds
 from one pass.
+detect_predictions / detect_quad_predictions leave the same results ON THE DEVICE in one fixed-shape record (Detections) without
+a host read, so they can sit in a captured graph (inference.CapturedInference); the two parse functions are unchanged.
 """
 import ctypes
 
@@ -276,6 +278,233 @@ def parse_groundtruths(end_points, config_dict):
     batch_gt_map_cls = [[(int(sem[i, j]), corners8[i, j]) for j in range(K2) if mask[i, j] == 1] for i in range(B)]
     end_points['batch_gt_map_cls'] = batch_gt_map_cls
     return batch_gt_map_cls
+
+
+# ------------------------------------------------------------------------------------------------- packed detections
+# The same results as the two parse functions above, left ON THE DEVICE in one fixed-shape record: decode,
+# (points in boxes,) suppression and a stable compaction, four launches at most for the objects and three for the quads,
+# no host read and -- with `out=` -- no allocation, so the calls can sit in a captured graph (inference.CapturedInference).
+MAX_DECODE_CLASSES = int(_lib.omnipq_decode_boxes_max_classes())        # nh, ns, ncls: the library's own limit
+MAX_PROPOSALS = 4096                                                    # k: the suppression kernel's limit
+
+_I32, _F32, _F64, _U8 = torch.int32, torch.float32, torch.float64, torch.uint8
+_NUMPY = {_I32: np.dtype(np.int32), _F32: np.dtype(np.float32), _F64: np.dtype(np.float64), _U8: np.dtype(np.uint8)}
+
+
+def detections_layout(kind, B, K, ncls=0, ns=0, per_class=False):
+    """-> ([(name, dtype, shape, byte offset)], result bytes, total bytes) of a record.  Pure.  The RESULT fields, what
+    to_lists() reads, come first and are what to_host() copies; the decode's intermediates follow.  Every offset is a multiple
+    of 16."""
+    if kind == "boxes":
+        result = [("count", _I32, (B,)), ("index", _I32, (B, K)), ("cls", _I32, (B, K)), ("score", _F32, (B, K)),
+                  ("corners8", _F64, (B, K, 8, 3)), ("keep", _U8, (B, K))]
+        if per_class:
+            result.append(("sem_prob", _F32, (B, K, ncls)))
+        rest = [("obj_prob", _F32, (B, K)), ("heading_cls", _I32, (B, K)), ("size_cls", _I32, (B, K)),
+                ("sem_cls", _I32, (B, K)), ("size", _F64, (B, K, 3)), ("heading", _F32, (B, K)),
+                ("all_corners8", _F64, (B, K, 8, 3)), ("aabb", _F64, (B, K, 6)), ("valid", _U8, (B, K)),
+                ("mean_size", _F64, (ns, 3))]
+        if per_class:
+            rest.append(("all_sem_prob", _F32, (B, K, ncls)))
+    elif kind == "quads":
+        result = [("count", _I32, (B,)), ("index", _I32, (B, K)), ("score", _F32, (B, K)), ("corners8", _F64, (B, K, 8, 3)),
+                  ("count_f1", _I32, (B,)), ("index_f1", _I32, (B, K)), ("verts4", _F32, (B, K, 4, 3)), ("keep", _U8, (B, K))]
+        rest = [("prob", _F32, (B, K)), ("all_corners8", _F64, (B, K, 8, 3)), ("aabb", _F64, (B, K, 6)),
+                ("all_verts4", _F32, (B, K, 4, 3))]
+    else:
+        raise ValueError(f"ap_helper_pq: a record is of kind 'boxes' or 'quads', not {kind!r}")
+    fields, off, result_bytes = [], 0, 0
+    for i, (name, dtype, shape) in enumerate(result + rest):
+        fields.append((name, dtype, tuple(shape), off))
+        off += -(-int(np.prod(shape, dtype=np.int64)) * _NUMPY[dtype].itemsize // 16) * 16
+        if i == len(result) - 1:
+            result_bytes = off
+    return fields, result_bytes, off
+
+
+class Detections(object):
+    """The detections of a batch on the device.  `record` is ONE contiguous uint8 tensor; every field is a typed view into
+    it (attributes, and `fields` by name): count (B) i32, then per scene rows [0, count) of index / cls / score / corners8
+    (/ sem_prob) in increasing proposal index -- rows behind count hold index -1 and zeros -- keep (B,K) u8, and the
+    decode's intermediates (obj_prob, size, heading, aabb, ...).  A record is a pure function of the inputs it was computed
+    from.  Made by detect_predictions / detect_quad_predictions; hand it back as `out=` to have it rewritten in place."""
+
+    def __init__(self, kind, B, K, device, ncls=0, ns=0, per_class=False, meta=None):
+        self.kind, self.B, self.K, self.ncls, self.ns, self.per_class = kind, B, K, ncls, ns, per_class
+        self.layout, self.result_bytes, nbytes = detections_layout(kind, B, K, ncls, ns, per_class)
+        self.record = torch.zeros((max(nbytes, 16),), device=device, dtype=torch.uint8)
+        self.fields = _views(self.record, self.layout)
+        self.meta = dict(meta or {})                 # host-side constants to_lists() needs (asserting mode, class count)
+        self._host = self._event = None
+
+    def __getattr__(self, name):
+        fields = self.__dict__.get("fields")
+        if fields is not None and name in fields:
+            return fields[name]
+        raise AttributeError(name)
+
+    def matches(self, kind, B, K, device, ncls=0, ns=0, per_class=False):
+        return (self.kind, self.B, self.K, self.ncls, self.ns, self.per_class, self.record.device) == \
+            (kind, B, K, ncls, ns, per_class, device)
+
+    def to_host(self):
+        """Copies the record's result fields into a pinned twin with ONE non-blocking copy on the current stream and records
+        an event behind it.  Returns self."""
+        if self._host is None:
+            self._host = torch.empty((self.record.numel(),), dtype=torch.uint8, pin_memory=True)
+            self._event = torch.cuda.Event()
+        n = self.result_bytes
+        self._host[:n].copy_(self.record[:n], non_blocking=True)
+        self._event.record()
+        return self
+
+    def host_fields(self):
+        """{name: numpy copy} of the result fields as the last to_host() left them; waits on its event."""
+        if self._event is None:
+            self.to_host()
+        self._event.synchronize()
+        flat = self._host.numpy()
+        out = {}
+        for name, dtype, shape, off in self.layout:
+            if off >= self.result_bytes:
+                break
+            a = _NUMPY[dtype]
+            n = int(np.prod(shape, dtype=np.int64))
+            out[name] = flat[off:off + n * a.itemsize].view(a).reshape(shape).copy()
+        return out
+
+    def to_lists(self):
+        """What the parse function of this record's kind returns, built from the pinned twin alone:
+        (batch_pred_map_cls, pred_mask) for objects, (batch_pred_map_cls, pred_mask, batch_pred_corners_list) for quads.
+        Asserts a non-empty pick per scene where the parse function does."""
+        h = self.host_fields()
+        keep = h["keep"].astype(bool)
+        if self.meta.get("assert_pick", False):
+            assert all(keep[i].any() for i in range(self.B))
+        pred_mask = keep.astype(np.float64)
+        corners8, score, count = h["corners8"], h["score"], h["count"]
+        if self.kind == "quads":
+            pred = [[(1, corners8[i, r], score[i, r]) for r in range(count[i])] for i in range(self.B)]
+            return pred, pred_mask, [[h["verts4"][i, r] for r in range(h["count_f1"][i])] for i in range(self.B)]
+        pred = []
+        for i in range(self.B):
+            if self.per_class:
+                sem = h["sem_prob"]
+                pred.append([(ii, corners8[i, r], sem[i, r, ii] * score[i, r])
+                             for ii in range(self.meta["num_class"]) for r in range(count[i])])
+            else:
+                pred.append([(int(h["cls"][i, r]), corners8[i, r], score[i, r]) for r in range(count[i])])
+        return pred, pred_mask
+
+
+def _views(record, layout):
+    out = {}
+    for name, dtype, shape, off in layout:
+        n = int(np.prod(shape, dtype=np.int64)) * _NUMPY[dtype].itemsize
+        out[name] = record[off:off + n].view(dtype).view(shape)
+    return out
+
+
+def _record_for(out, kind, B, K, device, **kw):
+    meta = kw.pop("meta")
+    if out is None:
+        return Detections(kind, B, K, device, meta=meta, **kw), True
+    if not isinstance(out, Detections) or not out.matches(kind, B, K, device, **kw):
+        raise ValueError(f"ap_helper_pq: `out` is not a {kind} record of this batch's shape, class counts and device")
+    out.meta.update(meta)
+    return out, False
+
+
+def detect_predictions(end_points, config_dict, prefix="", out=None):
+    """parse_predictions with its results left on the device: -> Detections (kind "boxes").  Same arguments; the inputs under
+    `prefix` must be float32 for the call to launch nothing but its own kernels (other dtypes are converted first):
+    omnipq_decode_boxes, omnipq_points_in_boxes if remove_empty_box, omnipq_nms3d / _samecls, omnipq_pack_boxes.  No host
+    read.  out: a Detections of an earlier call with the same shapes and modes, rewritten in place -- then nothing is
+    allocated either (the class mean sizes are uploaded when a record is made, not per call).
+    `.to_host()` / `.to_lists()` give parse_predictions' return values."""
+    DC = config_dict['dataset_config']
+    center = _f32(end_points[f'{prefix}center'], 'center')
+    hs = _f32(end_points[f'{prefix}heading_scores'], 'heading_scores')
+    hr = _f32(end_points[f'{prefix}heading_residuals'], 'heading_residuals')
+    ss = _f32(end_points[f'{prefix}size_scores'], 'size_scores')
+    sr = _f32(end_points[f'{prefix}size_residuals'], 'size_residuals')
+    sem = _f32(end_points[f'{prefix}sem_cls_scores'], 'sem_cls_scores')
+    obj = _f32(end_points[f'{prefix}objectness_scores'], 'objectness_scores')
+    B, K = center.shape[:2]
+    nh, ns, ncls = hs.shape[-1], ss.shape[-1], sem.shape[-1]
+    if max(nh, ns, ncls) > MAX_DECODE_CLASSES or min(nh, ns, ncls) < 1:
+        raise ValueError(f"ap_helper_pq: heading bins, size clusters and classes must be in [1, {MAX_DECODE_CLASSES}] "
+                         f"(got {nh}, {ns}, {ncls})")
+    if K > MAX_PROPOSALS:
+        raise ValueError(f"ap_helper_pq: at most {MAX_PROPOSALS} proposals per scene (got {K})")
+    if tuple(sr.shape) != (B, K, ns, 3) or tuple(hr.shape) != (B, K, nh) or tuple(obj.shape) != (B, K, 2):
+        raise ValueError("ap_helper_pq: heading_residuals (B,K,nh), size_residuals (B,K,ns,3), objectness_scores (B,K,2)")
+    means = np.ascontiguousarray(DC.mean_size_arr, dtype=np.float64)
+    if means.shape != (ns, 3):
+        raise ValueError(f"ap_helper_pq: mean_size_arr must be ({ns}, 3)")
+    per_class = bool(config_dict['per_class_proposal'])
+    use_3d, cls_nms = bool(config_dict['use_3d_nms']), bool(config_dict['cls_nms'])
+    if per_class and int(DC.num_class) > ncls:
+        raise ValueError("ap_helper_pq: dataset_config.num_class exceeds the classes of sem_cls_scores")
+    det, fresh = _record_for(out, "boxes", B, K, center.device, ncls=ncls, ns=ns, per_class=per_class,
+                             meta={"assert_pick": use_3d and not cls_nms, "num_class": int(DC.num_class)})
+    f = det.fields
+    if fresh:
+        f["mean_size"].copy_(torch.from_numpy(means))
+    rule = _heading_rule(DC)
+    null = ctypes.c_void_p(0)
+    _ext._run(_lib.omnipq_decode_boxes, center, B, K, nh, ns, ncls, _ext._ptr(center), _ext._ptr(hs), _ext._ptr(hr),
+              _ext._ptr(ss), _ext._ptr(sr), _ext._ptr(sem), _ext._ptr(obj), _ext._ptr(f["mean_size"]),
+              1 if rule == "bins" else 0, 0 if use_3d else 1, _ext._ptr(f["heading_cls"]), _ext._ptr(f["size_cls"]),
+              _ext._ptr(f["sem_cls"]), _ext._ptr(f["size"]), _ext._ptr(f["heading"]), _ext._ptr(f["obj_prob"]),
+              _ext._ptr(f["all_sem_prob"]) if per_class else null, _ext._ptr(f["all_corners8"]), _ext._ptr(f["aabb"]))
+    hptr = _ext._ptr(f["heading"]) if rule == "bins" else null           # rule "zero": the axis-aligned path, as above
+    vptr = null
+    if config_dict['remove_empty_box']:
+        pc = _f32(end_points['point_clouds'][:, :, 0:3], 'point_clouds')
+        _ext._run(_lib.omnipq_points_in_boxes, pc, B, pc.shape[1], K, _ext._ptr(pc), _ext._ptr(center), _ext._ptr(f["size"]),
+                  hptr, 5, _ext._ptr(f["valid"]))
+        vptr = _ext._ptr(f["valid"])
+    thr, old = float(config_dict['nms_iou']), int(bool(config_dict['use_old_type_nms']))
+    if use_3d and cls_nms:
+        _ext._run(_lib.omnipq_nms3d_samecls, center, B, K, _ext._ptr(f["aabb"]), _ext._ptr(f["obj_prob"]), vptr,
+                  _ext._ptr(f["sem_cls"]), thr, old, _ext._ptr(f["keep"]))
+    else:                                            # plain 3D, or bird's-eye view: the decode flattened the extents
+        _ext._run(_lib.omnipq_nms3d, center, B, K, _ext._ptr(f["aabb"]), _ext._ptr(f["obj_prob"]), vptr, thr, old,
+                  _ext._ptr(f["keep"]))
+    _ext._run(_lib.omnipq_pack_boxes, center, B, K, ncls, _ext._ptr(f["keep"]), _ext._ptr(f["obj_prob"]),
+              float(config_dict['conf_thresh']), _ext._ptr(f["sem_cls"]), _ext._ptr(f["all_corners8"]),
+              _ext._ptr(f["all_sem_prob"]) if per_class else null, _ext._ptr(f["count"]), _ext._ptr(f["index"]),
+              _ext._ptr(f["cls"]), _ext._ptr(f["score"]), _ext._ptr(f["corners8"]),
+              _ext._ptr(f["sem_prob"]) if per_class else null)
+    return det
+
+
+def detect_quad_predictions(end_points, config_dict, prefix="", out=None):
+    """parse_quad_predictions with its results left on the device: -> Detections (kind "quads"), three launches
+    (omnipq_parse_quads, omnipq_nms3d, omnipq_pack_quads), no host read, no allocation with `out=`.  The tensor twins
+    parse_quad_predictions leaves in end_points are not made."""
+    c = _f32(end_points[f'{prefix}quad_center'], "quad_center")
+    n = _f32(end_points[f'{prefix}normal_vector'], "normal_vector")
+    s = _f32(end_points[f'{prefix}quad_size'], "quad_size")
+    sc = _f32(end_points[f'{prefix}quad_scores'], "quad_scores")
+    B, K, _ = c.shape
+    if n.shape != c.shape or tuple(s.shape) != (B, K, 2) or tuple(sc.shape) != (B, K, 2):
+        raise ValueError("ap_helper_pq: quad_center / normal_vector must be (B, K, 3), quad_size and quad_scores (B, K, 2)")
+    if K > MAX_PROPOSALS:
+        raise ValueError(f"ap_helper_pq: at most {MAX_PROPOSALS} proposals per scene (got {K})")
+    det, _ = _record_for(out, "quads", B, K, c.device, meta={"assert_pick": True})
+    f = det.fields
+    thr = config_dict['nms_iou_quad'] if 'nms_iou_quad' in config_dict else config_dict['nms_iou']
+    _ext._run(_lib.omnipq_parse_quads, c, B, K, _ext._ptr(c), _ext._ptr(n), _ext._ptr(s), _ext._ptr(sc), LENGTH,
+              _ext._ptr(f["all_corners8"]), _ext._ptr(f["aabb"]), _ext._ptr(f["all_verts4"]), _ext._ptr(f["prob"]))
+    _ext._run(_lib.omnipq_nms3d, c, B, K, _ext._ptr(f["aabb"]), _ext._ptr(f["prob"]), ctypes.c_void_p(0), float(thr),
+              int(bool(config_dict['use_old_type_nms'])), _ext._ptr(f["keep"]))
+    _ext._run(_lib.omnipq_pack_quads, c, B, K, _ext._ptr(f["keep"]), _ext._ptr(f["prob"]), float(config_dict['conf_thresh']),
+              QUAD_THRES, _ext._ptr(f["all_corners8"]), _ext._ptr(f["all_verts4"]), _ext._ptr(f["count"]),
+              _ext._ptr(f["index"]), _ext._ptr(f["score"]), _ext._ptr(f["corners8"]), _ext._ptr(f["count_f1"]),
+              _ext._ptr(f["index_f1"]), _ext._ptr(f["verts4"]))
+    return det
 
 
 class APCalculator(object):
