@@ -407,17 +407,74 @@ __global__ __launch_bounds__(256) void decode_pair_group_bwd_kernel(DecodeGroupA
 
 }  // namespace omnipq
 
+// ---- host side of the head decodes: the argument checks and the kernels' argument records, each written once -------------
+namespace {
+using namespace omnipq;
+
+// An object-head problem: its sizes, its rows and (backward: lddy >= 0) the gradient descriptors and the row gradient.
+bool head_dims_ok(int nh, int ns, int ncls) { return nh >= 1 && ns >= 1 && ncls >= 1; }
+
+bool head_fwd_ok(int nh, int ns, int ncls, const void *y, int ldy, const float *base, const float *means, void *const *outs) {
+  return y && base && means && outs && ldy >= 5 + 2 * nh + 4 * ns + ncls;
+}
+
+bool head_bwd_ok(int nh, int ns, int ncls, const void *y, int ldy, const void *means, const void *gptr, const int *gstrides,
+                 const int *gn2, const int *gbf, const void *dy, int lddy) {
+  const int width = 5 + 2 * nh + 4 * ns + ncls;
+  return y && means && gptr && gstrides && gn2 && gbf && dy && ldy >= width && lddy >= width;
+}
+
+// A quad-head problem (R: its rows, at most 2^24: the norm's partial sums).
+bool quad_fwd_ok(int R, const void *y, int ldy, const float *base, void *const *outs, const float *norm) {
+  return y && base && outs && norm && ldy >= 10 && R <= (1 << 24);
+}
+
+bool quad_bwd_ok(int R, const void *y, int ldy, const void *norm, const void *gptr, const int *gstrides, const int *gbf,
+                 const void *dy, int lddy) {
+  return y && norm && gptr && gstrides && gbf && dy && ldy >= 10 && lddy >= 10 && R <= (1 << 24);
+}
+
+// Both heads' row counts of a pair: whole scenes of at least one row.
+bool pair_rows_ok(int Rh, int Kh, int Rq, int Kq) { return Rh > 0 && Rq > 0 && Kh >= 1 && Kq >= 1 && !(Rh % Kh) && !(Rq % Kq); }
+
+// The first `count` gradients from the host descriptors (gn2 NULL: all 1), the others absent.  false: an n2 below 1.
+bool head_grads(HeadGrads &gs, const void *const *gptr, const int *gstrides, const int *gn2, const int *gbf, int count) {
+  for (int i = 0; i < 10; ++i) gs.g[i] = HeadGrad{nullptr, 0, 0, 0, 0, 1, 0};
+  for (int i = 0; i < count; ++i) {
+    if (gn2 && gn2[i] < 1) return false;
+    const int *st = gstrides + 4 * i;
+    gs.g[i] = HeadGrad{gptr[i], st[0], st[1], st[2], st[3], gn2 ? gn2[i] : 1, gbf[i]};
+  }
+  return true;
+}
+
+// false: an output pointer is missing
+bool head_out(HeadOut &o, void *const *outs) {
+  for (int i = 0; i < 10; ++i)
+    if (!outs[i]) return false;
+  o = HeadOut{(e16_t *)outs[0], (float *)outs[1], (e16_t *)outs[2], (e16_t *)outs[3], (e16_t *)outs[4],
+              (e16_t *)outs[5], (e16_t *)outs[6], (float *)outs[7], (float *)outs[8], (e16_t *)outs[9]};
+  return true;
+}
+
+bool quad_out(QuadOut &o, void *const *outs) {
+  for (int i = 0; i < 4; ++i)
+    if (!outs[i]) return false;
+  o = QuadOut{(e16_t *)outs[0], (float *)outs[1], (e16_t *)outs[2], (e16_t *)outs[3]};
+  return true;
+}
+
+int pair_blocks(int Rh, int Rq) { return (Rh + 1) / 2 + (Rq + kQuadRows - 1) / kQuadRows; }
+}  // namespace
+
 // outs[4] = { scores bf16 [R][2], center f32 [R][3], normal bf16 [R][3], size bf16 [R][2] }; norm: one float
 // (the rounded 2-norm of all normals, kept for the backward pass).
 extern "C" int omnipq_quad_decode(int R, const void *y, int ldy, const float *base, void *const *outs, float *norm,
                                   void *stream) {
-  using namespace omnipq;
   if (R < 0) return OMNIPQ_EINVAL;
   if (R == 0) return OMNIPQ_OK;
-  if (!y || !base || !outs || !norm || ldy < 10 || R > (1 << 24)) return OMNIPQ_EINVAL;
-  for (int i = 0; i < 4; ++i)
-    if (!outs[i]) return OMNIPQ_EINVAL;
-  QuadOut o{(e16_t *)outs[0], (float *)outs[1], (e16_t *)outs[2], (e16_t *)outs[3]};
+  QuadOut o;
+  if (!quad_fwd_ok(R, y, ldy, base, outs, norm) || !quad_out(o, outs)) return OMNIPQ_EINVAL;
   quad_decode_kernel<<<(R + kQuadRows - 1) / kQuadRows, 256, 0, (hipStream_t)stream>>>(R, (const e16_t *)y, ldy, base, o, norm);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
@@ -427,16 +484,11 @@ extern "C" int omnipq_quad_decode(int R, const void *y, int ldy, const float *ba
 extern "C" int omnipq_quad_decode_bwd(int R, int K, const void *y, int ldy, const float *norm,
                                       const void *const *gptr, const int *gstrides, const int *g_is_bf16, void *dy,
                                       int lddy, float *dbase, void *stream) {
-  using namespace omnipq;
   if (R < 0 || K < 1) return OMNIPQ_EINVAL;
   if (R == 0) return OMNIPQ_OK;
-  if (!y || !norm || !gptr || !gstrides || !g_is_bf16 || !dy || ldy < 10 || lddy < 10 || (R % K) || R > (1 << 24))
-    return OMNIPQ_EINVAL;
+  if (!quad_bwd_ok(R, y, ldy, norm, gptr, gstrides, g_is_bf16, dy, lddy) || (R % K)) return OMNIPQ_EINVAL;
   HeadGrads gs;
-  for (int i = 0; i < 10; ++i) gs.g[i] = HeadGrad{nullptr, 0, 0, 0, 0, 1, 0};
-  for (int i = 0; i < 4; ++i)
-    gs.g[i] = HeadGrad{gptr[i], gstrides[4 * i], gstrides[4 * i + 1], gstrides[4 * i + 2], gstrides[4 * i + 3], 1,
-                       g_is_bf16[i]};
+  head_grads(gs, gptr, gstrides, nullptr, g_is_bf16, 4);
   quad_decode_bwd_kernel<<<(R + kQuadRows - 1) / kQuadRows, 256, 0, (hipStream_t)stream>>>(R, K, (const e16_t *)y, ldy, norm, gs, (e16_t *)dy, lddy,
                                                               dbase);
   OMNIPQ_LAUNCH_CHECK();
@@ -446,14 +498,10 @@ extern "C" int omnipq_quad_decode_bwd(int R, int K, const void *y, int ldy, cons
 // outs: the ten output pointers in HeadOut order.
 extern "C" int omnipq_head_decode(int R, int nh, int ns, int ncls, const void *y, int ldy, const float *base,
                                   const float *means, float hr_scale, void *const *outs, void *stream) {
-  using namespace omnipq;
-  if (R < 0 || nh < 1 || ns < 1 || ncls < 1) return OMNIPQ_EINVAL;
+  if (R < 0 || !head_dims_ok(nh, ns, ncls)) return OMNIPQ_EINVAL;
   if (R == 0) return OMNIPQ_OK;
-  if (!y || !base || !means || !outs || ldy < 5 + 2 * nh + 4 * ns + ncls) return OMNIPQ_EINVAL;
-  for (int i = 0; i < 10; ++i)
-    if (!outs[i]) return OMNIPQ_EINVAL;
-  HeadOut o{(e16_t *)outs[0], (float *)outs[1], (e16_t *)outs[2], (e16_t *)outs[3], (e16_t *)outs[4],
-            (e16_t *)outs[5], (e16_t *)outs[6], (float *)outs[7], (float *)outs[8], (e16_t *)outs[9]};
+  HeadOut o;
+  if (!head_fwd_ok(nh, ns, ncls, y, ldy, base, means, outs) || !head_out(o, outs)) return OMNIPQ_EINVAL;
   head_decode_kernel<<<R, 128, 0, (hipStream_t)stream>>>(R, nh, ns, ncls, (const e16_t *)y, ldy, base, means, hr_scale,
                                                          o);
   OMNIPQ_LAUNCH_CHECK();
@@ -467,18 +515,11 @@ extern "C" int omnipq_head_decode_bwd(int R, int K, int nh, int ns, int ncls, co
                                       const float *means, float hr_scale, const void *const *gptr,
                                       const int *gstrides, const int *gn2, const int *g_is_bf16, void *dy, int lddy,
                                       float *dbase, void *stream) {
-  using namespace omnipq;
-  if (R < 0 || K < 1 || nh < 1 || ns < 1 || ncls < 1) return OMNIPQ_EINVAL;
+  if (R < 0 || K < 1 || !head_dims_ok(nh, ns, ncls)) return OMNIPQ_EINVAL;
   if (R == 0) return OMNIPQ_OK;
-  const int width = 5 + 2 * nh + 4 * ns + ncls;
-  if (!y || !means || !gptr || !gstrides || !gn2 || !g_is_bf16 || !dy || ldy < width || lddy < width || (R % K))
-    return OMNIPQ_EINVAL;
+  if (!head_bwd_ok(nh, ns, ncls, y, ldy, means, gptr, gstrides, gn2, g_is_bf16, dy, lddy) || (R % K)) return OMNIPQ_EINVAL;
   HeadGrads gs;
-  for (int i = 0; i < 10; ++i) {
-    if (gn2[i] < 1) return OMNIPQ_EINVAL;
-    gs.g[i] = HeadGrad{gptr[i], gstrides[4 * i], gstrides[4 * i + 1], gstrides[4 * i + 2], gstrides[4 * i + 3], gn2[i],
-                       g_is_bf16[i]};
-  }
+  if (!head_grads(gs, gptr, gstrides, gn2, g_is_bf16, 10)) return OMNIPQ_EINVAL;
   head_decode_bwd_kernel<<<R, 128, 0, (hipStream_t)stream>>>(R, K, nh, ns, ncls, (const e16_t *)y, ldy, means, hr_scale,
                                                              gs, (e16_t *)dy, lddy, dbase);
   OMNIPQ_LAUNCH_CHECK();
@@ -492,24 +533,18 @@ static int decode_pair_impl(int Rh, int Kh, int nh, int ns, int ncls, const void
                             const float *means, float hr_scale, void *const *outs_h, int Rq, int Kq, const void *yq,
                             int ldyq, const float *baseq, void *const *outs_q, float *norm, float *pos, void *pos16,
                             int kpad, void *stream) {
-  using namespace omnipq;
-  if (Rh <= 0 || Rq <= 0 || nh < 1 || ns < 1 || ncls < 1 || Kh < 1 || Kq < 1 || (Rh % Kh) || (Rq % Kq)) return OMNIPQ_EINVAL;
+  if (!pair_rows_ok(Rh, Kh, Rq, Kq) || !head_dims_ok(nh, ns, ncls)) return OMNIPQ_EINVAL;
   if (pos && Rh / Kh != Rq / Kq) return OMNIPQ_EINVAL;
-  if (!yh || !baseh || !means || !outs_h || ldyh < 5 + 2 * nh + 4 * ns + ncls) return OMNIPQ_EINVAL;
-  if (!yq || !baseq || !outs_q || !norm || ldyq < 10 || Rq > (1 << 24)) return OMNIPQ_EINVAL;
-  for (int i = 0; i < 10; ++i)
-    if (!outs_h[i]) return OMNIPQ_EINVAL;
-  for (int i = 0; i < 4; ++i)
-    if (!outs_q[i]) return OMNIPQ_EINVAL;
-  HeadOut ho{(e16_t *)outs_h[0], (float *)outs_h[1], (e16_t *)outs_h[2], (e16_t *)outs_h[3], (e16_t *)outs_h[4],
-             (e16_t *)outs_h[5], (e16_t *)outs_h[6], (float *)outs_h[7], (float *)outs_h[8], (e16_t *)outs_h[9]};
-  QuadOut qo{(e16_t *)outs_q[0], (float *)outs_q[1], (e16_t *)outs_q[2], (e16_t *)outs_q[3]};
+  if (!head_fwd_ok(nh, ns, ncls, yh, ldyh, baseh, means, outs_h)) return OMNIPQ_EINVAL;
+  if (!quad_fwd_ok(Rq, yq, ldyq, baseq, outs_q, norm)) return OMNIPQ_EINVAL;
+  HeadOut ho;
+  QuadOut qo;
+  if (!head_out(ho, outs_h) || !quad_out(qo, outs_q)) return OMNIPQ_EINVAL;
   PairHead h{Rh, Kh, nh, ns, ncls, ldyh, 0, (const e16_t *)yh, baseh, means, hr_scale, nullptr, nullptr, 0,
              PosOut{pos, Kh, Kh + Kq, 0, (e16_t *)pos16, kpad}};
   PairQuad q{Rq, Kq, ldyq, 0, (const e16_t *)yq, baseq, norm, nullptr, nullptr, 0,
              PosOut{pos, Kq, Kh + Kq, Kh, (e16_t *)pos16, kpad}};
-  const int blocks = (Rh + 1) / 2 + (Rq + kQuadRows - 1) / kQuadRows;
-  decode_pair_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(h, ho, q, qo);
+  decode_pair_kernel<<<pair_blocks(Rh, Rq), 256, 0, (hipStream_t)stream>>>(h, ho, q, qo);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }
@@ -541,27 +576,17 @@ extern "C" int omnipq_decode_pair_bwd(int Rh, int Kh, int nh, int ns, int ncls, 
                                       int ldyq, const float *norm, const void *const *gptr_q, const int *gstrides_q,
                                       const int *gbf_q, void *dyq, int lddyq, float *dbaseq, int accumulate,
                                       void *stream) {
-  using namespace omnipq;
-  if (Rh <= 0 || Rq <= 0 || Kh < 1 || Kq < 1 || nh < 1 || ns < 1 || ncls < 1 || (Rh % Kh) || (Rq % Kq)) return OMNIPQ_EINVAL;
-  const int width = 5 + 2 * nh + 4 * ns + ncls;
-  if (!yh || !means || !gptr_h || !gstrides_h || !gn2_h || !gbf_h || !dyh || ldyh < width || lddyh < width) return OMNIPQ_EINVAL;
-  if (!yq || !norm || !gptr_q || !gstrides_q || !gbf_q || !dyq || ldyq < 10 || lddyq < 10 || Rq > (1 << 24)) return OMNIPQ_EINVAL;
+  if (!pair_rows_ok(Rh, Kh, Rq, Kq) || !head_dims_ok(nh, ns, ncls)) return OMNIPQ_EINVAL;
+  if (!head_bwd_ok(nh, ns, ncls, yh, ldyh, means, gptr_h, gstrides_h, gn2_h, gbf_h, dyh, lddyh)) return OMNIPQ_EINVAL;
+  if (!quad_bwd_ok(Rq, yq, ldyq, norm, gptr_q, gstrides_q, gbf_q, dyq, lddyq)) return OMNIPQ_EINVAL;
   HeadGrads hg, qg;
-  for (int i = 0; i < 10; ++i) {
-    if (gn2_h[i] < 1) return OMNIPQ_EINVAL;
-    hg.g[i] = HeadGrad{gptr_h[i], gstrides_h[4 * i], gstrides_h[4 * i + 1], gstrides_h[4 * i + 2], gstrides_h[4 * i + 3],
-                       gn2_h[i], gbf_h[i]};
-    qg.g[i] = HeadGrad{nullptr, 0, 0, 0, 0, 1, 0};
-  }
-  for (int i = 0; i < 4; ++i)
-    qg.g[i] = HeadGrad{gptr_q[i], gstrides_q[4 * i], gstrides_q[4 * i + 1], gstrides_q[4 * i + 2], gstrides_q[4 * i + 3], 1,
-                       gbf_q[i]};
+  if (!head_grads(hg, gptr_h, gstrides_h, gn2_h, gbf_h, 10)) return OMNIPQ_EINVAL;
+  head_grads(qg, gptr_q, gstrides_q, nullptr, gbf_q, 4);
   PairHead h{Rh, Kh, nh, ns, ncls, ldyh, lddyh, (const e16_t *)yh, nullptr, means, hr_scale, (e16_t *)dyh, dbaseh,
              accumulate & 1, PosOut{nullptr, 1, 1, 0}};
   PairQuad q{Rq, Kq, ldyq, lddyq, (const e16_t *)yq, nullptr, const_cast<float *>(norm), (e16_t *)dyq, dbaseq,
              (accumulate >> 1) & 1, PosOut{nullptr, 1, 1, 0}};
-  const int blocks = (Rh + 1) / 2 + (Rq + kQuadRows - 1) / kQuadRows;
-  decode_pair_bwd_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(h, hg, q, qg);
+  decode_pair_bwd_kernel<<<pair_blocks(Rh, Rq), 256, 0, (hipStream_t)stream>>>(h, hg, q, qg);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }
@@ -580,19 +605,17 @@ extern "C" int omnipq_decode_pair_group_bwd(int nstage, int Rh, int Kh, int nh, 
                                             const void *const *gptr_q, const int *gstrides_q, const int *gbf_q,
                                             void *const *dyq, int lddyq, float *const *dbaseq, float *sink, int accumulate,
                                             void *stream) {
-  using namespace omnipq;
   if (nstage < 1 || nstage > 64) return OMNIPQ_EINVAL;
-  if (Rh <= 0 || Rq <= 0 || Kh < 1 || Kq < 1 || nh < 1 || ns < 1 || ncls < 1 || (Rh % Kh) || (Rq % Kq)) return OMNIPQ_EINVAL;
-  const int width = 5 + 2 * nh + 4 * ns + ncls;
-  if (!yh || !means || !gptr_h || !gstrides_h || !gn2_h || !gbf_h || !dyh || ldyh < width || lddyh < width) return OMNIPQ_EINVAL;
-  if (!yq || !norm || !gptr_q || !gstrides_q || !gbf_q || !dyq || ldyq < 10 || lddyq < 10 || Rq > (1 << 24)) return OMNIPQ_EINVAL;
+  if (!pair_rows_ok(Rh, Kh, Rq, Kq) || !head_dims_ok(nh, ns, ncls)) return OMNIPQ_EINVAL;
+  if (!head_bwd_ok(nh, ns, ncls, yh, ldyh, means, gptr_h, gstrides_h, gn2_h, gbf_h, dyh, lddyh)) return OMNIPQ_EINVAL;
+  if (!quad_bwd_ok(Rq, yq, ldyq, norm, gptr_q, gstrides_q, gbf_q, dyq, lddyq)) return OMNIPQ_EINVAL;
   for (int i = 0; i < 10; ++i)
     if (gn2_h[i] < 1) return OMNIPQ_EINVAL;
   for (int s = 0; s < nstage; ++s) {
     if (!yh[s] || !means[s] || !dyh[s] || !yq[s] || !norm[s] || !dyq[s]) return OMNIPQ_EINVAL;
     if (sink && dbaseh && dbaseh[s]) return OMNIPQ_EINVAL;
   }
-  const int per_stage = (Rh + 1) / 2 + (Rq + kQuadRows - 1) / kQuadRows;
+  const int per_stage = pair_blocks(Rh, Rq);
   for (int s0 = 0; s0 < nstage; s0 += kDecodeGroupMax) {
     DecodeGroupArgs a;
     a.n = nstage - s0 < kDecodeGroupMax ? nstage - s0 : kDecodeGroupMax;
@@ -603,15 +626,8 @@ extern "C" int omnipq_decode_pair_group_bwd(int nstage, int Rh, int Kh, int nh, 
     for (int j = 0; j < a.n; ++j) {
       const int s = s0 + j;
       DecodeStage &st = a.st[j];
-      for (int i = 0; i < 10; ++i) {
-        const int *gs = gstrides_h + 40 * s + 4 * i;
-        st.hg.g[i] = HeadGrad{gptr_h[10 * s + i], gs[0], gs[1], gs[2], gs[3], gn2_h[i], gbf_h[10 * s + i]};
-        st.qg.g[i] = HeadGrad{nullptr, 0, 0, 0, 0, 1, 0};
-      }
-      for (int i = 0; i < 4; ++i) {
-        const int *gs = gstrides_q + 16 * s + 4 * i;
-        st.qg.g[i] = HeadGrad{gptr_q[4 * s + i], gs[0], gs[1], gs[2], gs[3], 1, gbf_q[4 * s + i]};
-      }
+      head_grads(st.hg, gptr_h + 10 * s, gstrides_h + 40 * s, gn2_h, gbf_h + 10 * s, 10);
+      head_grads(st.qg, gptr_q + 4 * s, gstrides_q + 16 * s, nullptr, gbf_q + 4 * s, 4);
       st.h = PairHead{Rh, Kh, nh, ns, ncls, ldyh, lddyh, (const e16_t *)yh[s], nullptr, means[s], hr_scale, (e16_t *)dyh[s],
                       (sink || !dbaseh) ? nullptr : dbaseh[s], 0, PosOut{nullptr, 1, 1, 0}};
       st.q = PairQuad{Rq, Kq, ldyq, lddyq, (const e16_t *)yq[s], nullptr, const_cast<float *>(norm[s]), (e16_t *)dyq[s],

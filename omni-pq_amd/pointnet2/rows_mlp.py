@@ -604,7 +604,7 @@ class RowsMLPPair(torch.autograd.Function):
                 outs.append(_drain(_backward_program(c, False, g, n)) if g is not None else (None,) * len(n))
             oa, ob = outs
         else:
-            oa, ob = _lockstep(_backward_program(ctx.a, True, ga, nig_a), _backward_program(ctx.b, False, gb, nig_b))
+            oa, ob = _lockstep(*tape_programs(ctx, ga, gb, nig_a, nig_b))
         return (oa[0], None, ob[0], None, None, None) + tuple(oa[3:]) + tuple(ob[3:])
 
 
@@ -637,3 +637,37 @@ def run_pair(xa, layers_a, xb, layers_b, training, padded=False, eval_chain=Fals
     spec_a, params_a = _spec_of(xa, layers_a, training, padded)
     spec_b, params_b = _spec_of(xb, layers_b, training, padded)
     return RowsMLPPair.apply(xa, spec_a, xb, spec_b, bool(training), len(params_a), *params_a, *params_b)
+
+
+class _Taped:
+    """Stands in for the autograd context of a Function whose forward is run outside autograd: keeps what it saves."""
+    saved_tensors = ()
+
+    def save_for_backward(self, *tensors):
+        self.saved_tensors = tensors
+
+    def set_materialize_grads(self, value):
+        pass
+
+    def mark_non_differentiable(self, *tensors):
+        pass
+
+
+def tape_pair(xa, layers_a, xb, layers_b, training, padded=False):
+    """The forward of `run_pair`'s node OUTSIDE autograd, for a caller that runs the backward of several pairs itself (the
+    prediction heads of all stages: models/pred_heads.py).  -> (ya, yb, tape); tape.params_a / tape.params_b are the two
+    stacks' parameters in the order `tape_programs` reports their gradients."""
+    spec_a, params_a = _spec_of(xa, layers_a, training, padded)
+    spec_b, params_b = _spec_of(xb, layers_b, training, padded)
+    tape = _Taped()
+    tape.params_a, tape.params_b = tuple(params_a), tuple(params_b)
+    with torch.no_grad():
+        ya, yb = RowsMLPPair.forward(tape, xa, spec_a, xb, spec_b, bool(training), len(params_a), *params_a, *params_b)
+    return ya, yb, tape
+
+
+def tape_programs(tape, ga, gb, nig_a, nig_b, b_leads=False):
+    """-> the two backward programs of a pair (a tape, or the pair node's own context) for `_lockstep`: each returns (dx,
+    None, None, *parameter gradients).  nig_a / nig_b: (input, False, False, *parameters) need a gradient; the first program
+    always leads, the second where further programs follow it in the same lockstep run."""
+    return _backward_program(tape.a, True, ga, nig_a), _backward_program(tape.b, b_leads, gb, nig_b)

@@ -399,7 +399,7 @@ def test_head_decode_kernel_equals_the_op_by_op_composition(monkeypatch):
     head with `decode_scores` op by op (reference pq_transformer.py:35-59): the ten end_points entries are the same
     bits and dtypes; gradients (dense f32 / bf16 and broadcast ones, as a mean-style loss produces) agree to bf16
     rounding of the row gradient."""
-    import pq_transformer as pq
+    import pred_heads as pq
     torch.manual_seed(3)
     B, K, C = 4, 256, 288
     means = (torch.rand(18, 3) + 0.2).numpy()
@@ -447,7 +447,7 @@ def test_quad_decode_kernel_equals_the_op_by_op_composition(monkeypatch):
     """QuadPredictHead with the fused decode against the op-by-op composition (reference pq_transformer.py:105-120,
     normal divided by the 2-norm of the whole tensor): scores / centre / size are the same bits, the normal agrees to
     one bf16 ulp (the norm is summed in a different order before its rounding to bf16), gradients to bf16 rounding."""
-    import pq_transformer as pq
+    import pred_heads as pq
     torch.manual_seed(4)
     B, K, C = 4, 256, 288
     head = pq.QuadPredictHead(C).to(dev())
@@ -497,7 +497,7 @@ def test_decode_pair_is_the_two_decodes_bit_for_bit(monkeypatch):
     entry and every gradient the kernels produce is the same bits (the parameter gradients behind them agree to the order
     of the stacks' f32 atomics); odd row counts on both sides (the head half of the grid takes two rows
     per block, the quad half 32)."""
-    import pq_transformer as pq
+    import pred_heads as pq
     torch.manual_seed(5)
     C = 288
     means = (torch.rand(18, 3) + 0.2).numpy()
@@ -583,7 +583,7 @@ def test_model_forward_with_pair_launches_equals_the_separate_launches(monkeypat
     end_points entry is the same bits as with one launch per head."""
     import bench
     import synth
-    import pq_transformer as pq
+    import pred_heads as pq
     import capi
     torch.manual_seed(1)
     net = bench.build_model(0).to(dev()).eval()

@@ -9,7 +9,7 @@ from conftest import REPO  # noqa: F401  (sys.path set-up)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-SWITCHES = (("decoder_rows", "LN_SPLIT"), ("pq_transformer", "_POS_ROWS16"), ("pq_transformer", "_JOIN_ROWS"))
+SWITCHES = (("decoder_rows", "LN_SPLIT"), ("pred_heads", "_POS_ROWS16"), ("pq_transformer", "_JOIN_ROWS"))
 
 
 def run_once(net, pc, on):
@@ -48,9 +48,10 @@ def test_whole_model_is_bit_equal_with_the_boundary_folds_on_and_off():
     import bench
     import decoder_rows
     import pq_transformer
+    import pred_heads
     import synth
     from procedural import load_procedural
-    assert decoder_rows.LN_SPLIT is True and pq_transformer._POS_ROWS16 is True          # the defaults ship on
+    assert decoder_rows.LN_SPLIT is True and pred_heads._POS_ROWS16 is True          # the defaults ship on
     B, P = 2, 256 + 256
     pc = synth.make_clouds(90, B, 8192, kind="room").to(DEV)
     net = load_procedural(bench.build_model(0)).to(DEV).train()

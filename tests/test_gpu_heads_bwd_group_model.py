@@ -1,5 +1,5 @@
 """GPU: the whole model, one forward + backward (batch 2, 8192 points, bf16, dropout on, the same dropout seed) with the
-prediction heads' backward grouped over all stages (pq_transformer._HEADS_BWD_GROUP) and per stage: every `end_points` entry
+prediction heads' backward grouped over all stages (pred_heads._HEADS_BWD_GROUP) and per stage: every `end_points` entry
 and every parameter gradient bit-equal, and the C-ABI calls made (pointnet2/_ext.py: set_timing_sink) show which route ran."""
 import pytest
 import torch
@@ -14,12 +14,12 @@ def run_once(net, pc, on, only=None):
     """only: prefixes of the stages whose outputs reach the loss (None: every end_points entry, as bench.py's loss)"""
     import bench
     import dropout_state
-    import pq_transformer
+    import pred_heads
     import sa_fused
-    before = pq_transformer._HEADS_BWD_GROUP
+    before = pred_heads._HEADS_BWD_GROUP
     calls = []
     try:
-        pq_transformer._HEADS_BWD_GROUP = on
+        pred_heads._HEADS_BWD_GROUP = on
         dropout_state.STATE.set_state(torch.device(DEV), 0x5EED5EED)
         net.zero_grad(set_to_none=True)
         sa_fused._ext.set_timing_sink(calls)
@@ -31,7 +31,7 @@ def run_once(net, pc, on, only=None):
         torch.cuda.synchronize()
     finally:
         sa_fused._ext.set_timing_sink(None)
-        pq_transformer._HEADS_BWD_GROUP = before
+        pred_heads._HEADS_BWD_GROUP = before
     grads = {k: (None if p.grad is None else p.grad.detach().clone()) for k, p in net.named_parameters()}
     return {k: v.detach().clone() for k, v in ep.items()}, grads, loss.detach().clone(), [(n, a) for n, a, _, _ in calls]
 
@@ -72,9 +72,9 @@ def model():
 
 
 def test_whole_model_is_bit_equal_with_the_heads_backward_grouped_and_per_stage(model):
-    import pq_transformer
+    import pred_heads
     net, pc = model
-    assert pq_transformer._HEADS_BWD_GROUP is True                                   # the default ships on
+    assert pred_heads._HEADS_BWD_GROUP is True                                   # the default ships on
     stages = len(net.decoder) + 1
     off = run_once(net, pc, False)
     on = run_once(net, pc, True)

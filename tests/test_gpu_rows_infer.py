@@ -205,10 +205,10 @@ MODULES = {"voting": _voting, "head": _head, "posembed": _posembed, "fp": _fp}
 
 
 def _heads_opt_in(monkeypatch, on=True):
-    """the prediction heads' stacks opt into the chain through pq_transformer._HEAD_EVAL_CHAIN (shipped off: an existing test
+    """the prediction heads' stacks opt into the chain through pred_heads._HEAD_EVAL_CHAIN (shipped off: an existing test
     pins the eval forward's head stacks as pair launches)"""
-    import pq_transformer
-    monkeypatch.setattr(pq_transformer, "_HEAD_EVAL_CHAIN", on)
+    import pred_heads
+    monkeypatch.setattr(pred_heads, "_HEAD_EVAL_CHAIN", on)
 
 
 def _flat(out):

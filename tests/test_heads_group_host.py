@@ -1,4 +1,4 @@
-"""CPU only: the host side of the grouped backward of the prediction heads.  pq_transformer.heads_bwd_route decides from
+"""CPU only: the host side of the grouped backward of the prediction heads.  pred_heads.heads_bwd_route decides from
 flags alone; rows_mlp._lockstep runs n backward programs round by round -- on the recorder of
 tests/golden/make_golden_rows_calls.py (nothing is launched) the calls of three pairs run as ONE lockstep are the calls of the
 three pairs run one after the other, interleaved round by round, with every program but the last one leading."""
@@ -17,7 +17,7 @@ def _generator():
 
 
 def test_route_is_a_function_of_its_flags(built_lib, monkeypatch):
-    import pq_transformer as pq
+    import pred_heads as pq
     assert pq._HEADS_BWD_GROUP is True                                       # ships on
     on = dict(stages=7, pair_stacks=True, pair_decode=True, fused_decode=True, cuda=True, training=True, grad=True, world=1,
               force_collectives=False)
@@ -32,6 +32,57 @@ def test_route_is_a_function_of_its_flags(built_lib, monkeypatch):
     monkeypatch.setattr(pq, "_HEADS_BWD_GROUP", False)
     assert pq.heads_bwd_route(**on) == "stage"
     assert 2 * pq._HEADS_GROUP_MAX == 14                                     # csrc/common.h: kHeldMax
+
+
+MOVED_SWITCHES = ("_JOINT_HEADS", "_HEAD_EVAL_CHAIN", "_FUSED_DECODE", "_PAIR_DECODE", "_PAIR_STACKS", "_XYZ_SINK", "_POS_ROWS16",
+                  "_POS_KPAD", "_HEADS_BWD_GROUP", "_HEADS_GROUP_MAX")
+
+
+def test_every_switch_of_the_heads_exists_in_one_module_only(built_lib):
+    """(a copy in pq_transformer would be dead: `bench.py --set` and monkeypatch.setattr would set it and measure nothing)"""
+    import pq_transformer
+    import pred_heads
+    for name in MOVED_SWITCHES:
+        assert hasattr(pred_heads, name) and not hasattr(pq_transformer, name), name
+    assert pq_transformer.PredictHead is pred_heads.PredictHead and pq_transformer.QuadPredictHead is pred_heads.QuadPredictHead
+    assert pq_transformer.seat_head_parameters is pred_heads.seat_head_parameters
+    assert pred_heads.PredictHead.__module__ == "pred_heads"
+
+
+def _stage_route_restated(pair_decode, fused_decode, grouped, like_first, cuda, usable_a, usable_b, head_training, quad_training,
+                          base_grad, has_sink):
+    """The conditions as predict_pair, head_stack_pair and HeadsGroup.stage spelled them while they looked at tensors."""
+    if grouped:                                            # predict_pair: a group was handed in -- HeadsGroup.stage
+        refused = not (head_training and quad_training) or (base_grad and not has_sink)
+        if not refused:
+            refused = not (usable_a and usable_b)
+        if not refused:
+            refused = not like_first
+        if not refused:
+            return "group"
+    if not (pair_decode and fused_decode and cuda):
+        return "single"
+    if usable_a and usable_b:                              # both stacks' rows come from the row kernels: the pair decode
+        return "pair"
+    return "stacks"
+
+
+def test_stage_route_over_every_combination_of_its_inputs(built_lib, monkeypatch):
+    import pred_heads
+    n = 0
+    for pair_decode, fused_decode in itertools.product((False, True), repeat=2):
+        monkeypatch.setattr(pred_heads, "_PAIR_DECODE", pair_decode)
+        monkeypatch.setattr(pred_heads, "_FUSED_DECODE", fused_decode)
+        for facts in itertools.product((False, True), repeat=9):
+            assert pred_heads.stage_route(*facts) == _stage_route_restated(pair_decode, fused_decode, *facts), \
+                (pair_decode, fused_decode, facts)
+            n += 1
+    assert n == 2048
+    # whether two usable stacks of one mode share their launches is the one reading of _PAIR_STACKS
+    for on in (False, True):
+        monkeypatch.setattr(pred_heads, "_PAIR_STACKS", on)
+        for same_mode, ua, ub in itertools.product((False, True), repeat=3):
+            assert pred_heads.stacks_paired(same_mode, ua, ub) is (on and same_mode and ua and ub)
 
 
 def _rounds(events):
@@ -54,7 +105,6 @@ def test_lockstep_of_n_programs_interleaves_the_pairs(built_lib):
     import dropout_state
     import rows_mlp
     import sa_fused
-    import pq_transformer as pq
     gen = _generator()
     rec = gen.Recorder()
     patches = [(rows_mlp, "_call", rec.call), (sa_fused, "_call", rec.call), (rows_mlp, "_hold", rec.hold),
@@ -70,17 +120,13 @@ def test_lockstep_of_n_programs_interleaves_the_pairs(built_lib):
         pairs.append((stacks, xs))
 
     def forward(stacks, xs):
-        """the pair's forward outside autograd, as pq_transformer.HeadsGroup runs it -> (its context, output gradients)"""
-        ctx = pq._Taped()
-        spec_a, params_a = rows_mlp._spec_of(xs[0], stacks[0], True, True)
-        spec_b, params_b = rows_mlp._spec_of(xs[1], stacks[1], True, True)
-        with torch.no_grad():
-            ya, yb = rows_mlp.RowsMLPPair.forward(ctx, xs[0], spec_a, xs[1], spec_b, True, len(params_a), *params_a, *params_b)
-        return ctx, torch.ones_like(ya), torch.ones_like(yb)
+        """the pair's forward outside autograd, as pred_heads runs a grouped stage -> (its tape, output gradients)"""
+        ya, yb, tape = rows_mlp.tape_pair(xs[0], stacks[0], xs[1], stacks[1], True, padded=True)
+        return tape, torch.ones_like(ya), torch.ones_like(yb)
 
     def programs(ctx, ga, gb, last):
         nig = (True, False, False) + (True,) * 12
-        return [rows_mlp._backward_program(ctx.a, True, ga, nig), rows_mlp._backward_program(ctx.b, not last, gb, nig)]
+        return list(rows_mlp.tape_programs(ctx, ga, gb, nig, nig, b_leads=not last))
 
     with gen._patched(patches):
         # each pair on its own: a lockstep of two

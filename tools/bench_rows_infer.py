@@ -7,10 +7,10 @@ model in eval mode under torch.no_grad() and bf16 autocast.
 
 Per batch size the five kinds of stack the eval forward runs are event-timed one by one through the model's own call sites, on
 inputs of the model's shapes (1024 seeds and 256 proposals per scene): the position-embedding pair of two decoder layers
-(decoder_rows.posembed_pair), the voting module, the object + quad head pair of a decoder stage (pq_transformer.head_stack_pair)
+(decoder_rows.posembed_pair), the voting module, the object + quad head pair of a decoder stage (pred_heads.head_stack_pair)
 and the two feature-propagation modules.  A call holds what the call site does besides the stack (the vote decode, the
 three-neighbour interpolation) on both routes alike.  The whole eval forward is timed on the host clock, ending in a device
-synchronise, in scenes/s -- as shipped (`forward`: the heads stay on the stored route, pq_transformer._HEAD_EVAL_CHAIN) and with
+synchronise, in scenes/s -- as shipped (`forward`: the heads stay on the stored route, pred_heads._HEAD_EVAL_CHAIN) and with
 the heads opted in as well (`forward+heads`); the head pair itself is measured with the switch on.  The two routes alternate
 inside every round (same process, same inputs); the table reports the median over the rounds and the spread (max - min) next to
 it.  A kind's verdict is `chain` when the chain's median is below the stored route's by more than the two spreads together, at
@@ -36,7 +36,7 @@ NAMES = ["pos_pair", "vote", "head_pair", "fp1", "fp2"]
 def stack_calls(net, B, dev):
     """-> {kind: (callable, chain launches per call)} on inputs of the model's shapes"""
     import decoder_rows
-    import pq_transformer
+    import pred_heads
     gen = torch.Generator(device=dev).manual_seed(5)
 
     def rand(*shape, scale=1.0):
@@ -54,7 +54,7 @@ def stack_calls(net, B, dev):
     return {
         "pos_pair": (lambda: decoder_rows.posembed_pair(pe[0], pe[1], key_xyz), 2),
         "vote": (lambda: net.vote(seed_xyz, seed_feat, normalized=True), 1),
-        "head_pair": (lambda: pq_transformer.head_stack_pair(net.prediction_heads[0], net.prediction_quad_heads[0], feat, feat_q), 2),
+        "head_pair": (lambda: pred_heads.head_stack_pair(net.prediction_heads[0], net.prediction_quad_heads[0], feat, feat_q), 2),
         "fp1": (lambda: bb.fp1(xyz3, xyz4, f3, f4), 1),
         "fp2": (lambda: bb.fp2(xyz2, xyz3, f2, f1out), 1),
     }
@@ -97,14 +97,14 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_rows_infer: needs a GPU (nothing is timed without one)")
-    import pq_transformer
+    import pred_heads
     import rows_mlp
     import synth
     dev = torch.device("cuda", 0)
     torch.manual_seed(1)
     net = bench.build_model(0).to(dev).eval()
-    shipped, shipped_heads = rows_mlp.EVAL_CHAIN, pq_transformer._HEAD_EVAL_CHAIN
-    pq_transformer._HEAD_EVAL_CHAIN = True           # the head pair is measured on the chain like the others (shipped off)
+    shipped, shipped_heads = rows_mlp.EVAL_CHAIN, pred_heads._HEAD_EVAL_CHAIN
+    pred_heads._HEAD_EVAL_CHAIN = True           # the head pair is measured on the chain like the others (shipped off)
     lines = [f"# python tools/bench_rows_infer.py --points {args.points} --batches {' '.join(map(str, args.batches))} "
              f"--rounds {args.rounds} --iters {args.iters}        ({torch.cuda.get_device_name(0)}, one process)",
              "# eval / no_grad / bf16; stored = rows_mlp.EVAL_CHAIN off, chain = on, alternating inside every round; ms per call: "
@@ -125,7 +125,7 @@ def main():
                     ran = rows_mlp.eval_chain_uses - uses
                     assert ran == (launches if mode else 0), f"{n}: {ran} chain launches with EVAL_CHAIN = {mode}"
                 for heads in (False, True, False, True):     # warm-up of the whole forward, every configuration timed
-                    pq_transformer._HEAD_EVAL_CHAIN = heads
+                    pred_heads._HEAD_EVAL_CHAIN = heads
                     uses = rows_mlp.eval_chain_uses
                     net({"point_clouds": pc})
                     forward_chains[mode, heads] = rows_mlp.eval_chain_uses - uses
@@ -146,10 +146,10 @@ def main():
                     t[n, mode].append(time_call(calls[n][0], args.iters))
                 # the whole forward as shipped (the heads on the stored route), and with the heads opted in as well
                 for n, heads in (("forward", False), ("forward+heads", True)):
-                    pq_transformer._HEAD_EVAL_CHAIN = heads
+                    pred_heads._HEAD_EVAL_CHAIN = heads
                     time_forward(net, pc, 2)
                     t[n, mode].append(time_forward(net, pc, max(args.iters // 2, 3)))      # about a second per sample
-                pq_transformer._HEAD_EVAL_CHAIN = True
+                pred_heads._HEAD_EVAL_CHAIN = True
         for n in NAMES + ["forward", "forward+heads"]:
             med = {m: statistics.median(t[n, m]) for m in (False, True)}
             spr = {m: max(t[n, m]) - min(t[n, m]) for m in (False, True)}
@@ -162,7 +162,7 @@ def main():
             lines.append(f"batch {B} {n:13s} stored {med[False]:8.4f} ms ({spr[False]:.4f})   chain {med[True]:8.4f} ms "
                          f"({spr[True]:.4f})   stored / chain {med[False] / med[True]:5.2f}   "
                          f"{'chain faster' if faster else 'not faster beyond the spreads'}{extra}")
-    rows_mlp.EVAL_CHAIN, pq_transformer._HEAD_EVAL_CHAIN = shipped, shipped_heads
+    rows_mlp.EVAL_CHAIN, pred_heads._HEAD_EVAL_CHAIN = shipped, shipped_heads
     for n in NAMES:
         lines.append(f"verdict {n}: {'chain' if wins[n] else 'stored'}")
     text = "\n".join(lines) + "\n"
