@@ -315,38 +315,20 @@ _GEMM = {"stats": _gemm_stats, "relu_dropout": _gemm_relu_dropout, "plain": _gem
 
 
 # where a BatchNorm layer gets its constants, by LayerRoute.finalize: (lay, N, count, sums, bn, bias, gamma, beta) -> lay.X
-def _batch_constants(lay, bias):
-    stats = torch.empty((4, lay.C), device=lay.Y.device)            # a | b | mean | invstd
-    lay.a, lay.b, lay.mean, lay.invstd = stats[0], stats[1], stats[2], stats[3]
-    return bias.detach().float().contiguous() if lay.has_bias else None          # only the running mean accounts for the bias
-
-
 def _finalize_in_consumer(lay, N, count, sums, bn, bias, gamma, beta):
     """by the GEMM this layer feeds (sa_fused.gemm_nt_affine takes `fin`); relu(bn(Y)) is never stored"""
-    cb = _batch_constants(lay, bias)
-    lay.fin = (sums, count, gamma.detach(), beta.detach(), bn.eps, bn.momentum, bn.running_mean, bn.running_var, cb)
+    lay.fin = sa_fused.batch_constants(lay, sums, count, gamma, beta, bn, bias)
     lay.X = None
     return None
 
 
 def _finalize_launch(lay, N, count, sums, bn, bias, gamma, beta):
-    cb = _batch_constants(lay, bias)
-    lay.X = torch.empty_like(lay.Y)
-    _call(_lib.omnipq_bn_finalize_relu, lay.Y, N, lay.C, count, _p(sums), _p(gamma.detach()), _p(beta.detach()), bn.eps,
-          bn.momentum, _p(bn.running_mean), _p(bn.running_var), _p(cb), _p(lay.Y), _p(lay.X), _p(lay.a), _p(lay.b), _p(lay.mean),
-          _p(lay.invstd))
-    return lay.X
+    return sa_fused.finalize_launch(lay, N, sa_fused.batch_constants(lay, sums, count, gamma, beta, bn, bias), relu=True)
 
 
 def _finalize_running(lay, N, count, sums, bn, bias, gamma, beta):
     """eval mode: constants from the running estimates, then normalise + ReLU"""
-    lay.invstd = torch.rsqrt(bn.running_var + bn.eps)
-    lay.mean = bn.running_mean - bias.detach().float() if lay.has_bias else bn.running_mean
-    lay.a = (gamma.detach() * lay.invstd).contiguous()
-    lay.b = (beta.detach() - lay.mean * lay.a).contiguous()
-    lay.X = torch.empty_like(lay.Y)
-    _call(_lib.omnipq_bnrelu, lay.Y, N, lay.C, _p(lay.Y), _p(lay.a), _p(lay.b), _p(lay.X))
-    return lay.X
+    return sa_fused.running_constants(lay, N, gamma, beta, bn, bias)
 
 
 _FINALIZE = {"consumer": _finalize_in_consumer, "launch": _finalize_launch, "running": _finalize_running}

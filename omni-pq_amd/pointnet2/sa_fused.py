@@ -89,12 +89,6 @@ class _tagged:
             _lib.omnipq_span_marker(1, _ext._stream())
 
 
-_STAGE_LABEL = None  # set by run(): the stage's name for the timing sink ("sa1" .. "vote", or m<npoint>s<nsample>)
-_SYNC = True       # set by run() per stage: do this stage's BatchNorm layers synchronise across ranks (SyncBatchNorm)?
-_NO_GRAD = False   # set by run() for the duration of the stage: was it called with autograd off (`not torch.is_grad_enabled()`)?
-                   # Asked there, not in FusedSAStage.forward: inside a Function's forward grad mode is always off
-
-
 def _world():
     return dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
 
@@ -244,15 +238,33 @@ def _partial_sum_rows(P):
     return int(_lib.omnipq_gemm_nt_stats_workspace_floats(P, 8)) > 0
 
 
+class Finalize(collections.namedtuple("Finalize", "sums count gamma beta eps momentum running_mean running_var conv_bias",
+                                      defaults=(None,))):
+    """What the launch that reads a training BatchNorm layer's constants first forms them from (`lay.fin`: the first consumer
+    finalises and clears it).  conv_bias: what a preceding linear layer would add (only the running mean sees it)."""
+
+    def tail(self):
+        """the argument run every finalising entry point shares; its head is the call site's (include/omnipq_sa.h: the GEMM
+        prologues and the pool-select launch take `sums, count`, omnipq_bn_finalize / _relu take `count, sums`)"""
+        return _p(self.gamma), _p(self.beta), self.eps, self.momentum, _p(self.running_mean), _p(self.running_var)
+
+
+class BallExtrema(collections.namedtuple("BallExtrema", "per ymax ymin amax amin")):
+    """The extrema of every `per` consecutive rows (a ball, or a group of a planned stage's compact row space) that the last GEMM
+    records per column (csrc/gemm_bf16.hip: PoolOut): values and the rows that attain them."""
+
+    def args(self):
+        return _p(self.ymax), _p(self.ymin), _p(self.amax), _p(self.amin)
+
+
 def _gemm_nt_stats(A, B, M, N, K, sums, bias=None, pool=None):
     """bf16 C = A B^T and, in the same pass, sums (f64 [2][N], zero on entry) += column sum / sum of squares;
-    pool = (S, ymax, ymin, amax, amin): also the extrema of every ball of S rows (csrc/gemm_bf16.hip: PoolOut)."""
+    pool (a BallExtrema): also the extrema of every ball."""
     C = torch.empty((M, N), device=A.device, dtype=E16.dtype)
     ws = _stats_workspace(M, N, A.device)
     if pool is not None:
-        S, ymax, ymin, amax, amin = pool
         _call(_lib.omnipq_gemm_nt_e16_stats_pool, A, M, N, K, _p(A), K, _p(B), K, _p(C), N, _p(bias), _p(sums), _p(ws),
-              S, _p(ymax), _p(ymin), _p(amax), _p(amin))
+              pool.per, *pool.args())
         return C
     _call(_lib.omnipq_gemm_nt_e16_stats, A, M, N, K, _p(A), K, _p(B), K, _p(C), N, _p(bias), _p(sums), _p(ws))
     return C
@@ -402,36 +414,28 @@ def plan_from_state(flat, B, M, P):
 
 
 class _PlanState(threading.local):       # per Python thread (forward thread / autograd thread): which plan _call passes
-    arg = None                           # ctypes pointer to a RowPlanArg, or None
-    struct = None
+    arg = None                           # ctypes pointer to a RowPlanArg (which it keeps alive), or None
 
 
 _plan_state = _PlanState()
 
 
 class _row_plan:
-    """The launches inside the block get `plan` (plan-aware entry points: as their `plan` argument, see _call)."""
+    """The launches inside the block get `plan` (plan-aware entry points: as their `plan` argument, see _call).  pool_gamma:
+    the plan also says that the ball extrema hold only the side this gamma's sign selects (omnipq_row_plan.pool_gamma) -- for
+    the launches of THIS block: the struct is built on entry and not written afterwards."""
 
-    def __init__(self, plan, rows):
-        self.plan, self.rows = plan, rows
+    def __init__(self, plan, rows, pool_gamma=None):
+        self.plan, self.rows, self.pool_gamma = plan, rows, pool_gamma
 
     def __enter__(self):
-        self.prev = (_plan_state.arg, _plan_state.struct)
-        if self.plan is not None:
-            st = RowPlanArg(_p(self.plan.rows_dev).value, _p(self.plan.row_w).value, _p(self.plan.goff).value, self.rows,
-                            self.plan.gs, None)
-        else:
-            st = None
-        _plan_state.struct = st
-        _plan_state.arg = ctypes.pointer(st) if st is not None else None
+        self.prev = _plan_state.arg
+        plan = self.plan
+        _plan_state.arg = None if plan is None else ctypes.pointer(RowPlanArg(
+            _p(plan.rows_dev).value, _p(plan.row_w).value, _p(plan.goff).value, self.rows, plan.gs, _p(self.pool_gamma).value))
 
     def __exit__(self, *exc):
-        _plan_state.arg, _plan_state.struct = self.prev
-
-
-def _plan_pool_gamma(gamma):
-    """from here to the end of the block the plan says: extrema of the side gamma's sign selects only (omnipq_row_plan.pool_gamma)"""
-    _plan_state.struct.pool_gamma = _p(gamma).value
+        _plan_state.arg = self.prev
 
 
 def gemm_nt_affine(Y, below, Bw, M, N, K, sums=None, bias=None, out=None, pool=None, store=True):
@@ -443,18 +447,13 @@ def gemm_nt_affine(Y, below, Bw, M, N, K, sums=None, bias=None, out=None, pool=N
     if fin is not None:
         # the layer below has not been finalised yet: this GEMM's prologue derives a / b from its totals (and stores
         # them, with mean / invstd and the running-statistics update) -- one launch less per BatchNorm layer
-        fsums, count, gamma, beta, eps, momentum, rm, rv, cb = fin
         below.fin = None
+        head = (Y, M, N, K, _p(Y), K, _p(fin.sums), fin.count, *fin.tail(), _p(fin.conv_bias), _p(below.a), _p(below.b),
+                _p(below.mean), _p(below.invstd), _p(Bw), K, _p(C), N, _p(bias), _p(sums), _p(ws))
         if pool is not None:
-            S, ymax, ymin, amax, amin = pool
-            _call(_lib.omnipq_gemm_nt_e16_bnaffine_pool, Y, M, N, K, _p(Y), K, _p(fsums), count,
-                  _p(gamma), _p(beta), eps, momentum, _p(rm), _p(rv), _p(cb), _p(below.a),
-                  _p(below.b), _p(below.mean), _p(below.invstd), _p(Bw), K, _p(C), N, _p(bias), _p(sums), _p(ws), S,
-                  _p(ymax), _p(ymin), _p(amax), _p(amin))
-            return C
-        _call(_lib.omnipq_gemm_nt_e16_bnaffine, Y, M, N, K, _p(Y), K, _p(fsums), count, _p(gamma),
-              _p(beta), eps, momentum, _p(rm), _p(rv), _p(cb), _p(below.a), _p(below.b),
-              _p(below.mean), _p(below.invstd), _p(Bw), K, _p(C), N, _p(bias), _p(sums), _p(ws))
+            _call(_lib.omnipq_gemm_nt_e16_bnaffine_pool, *head, pool.per, *pool.args())
+        else:
+            _call(_lib.omnipq_gemm_nt_e16_bnaffine, *head)
         return C
     if pool is not None:
         raise RuntimeError("gemm_nt_affine: ball extrema need the layer below to be finalised in the prologue")
@@ -567,11 +566,10 @@ def gemm_nt_xyz(X0c, below, Bw, M, N, K, sums):
     """bf16 C = relu(bn(X0c W0^T)) Bw^T + its statistics: `below` is the never-materialised first layer (Wp, fin)."""
     C = torch.empty((M, N), device=X0c.device, dtype=E16.dtype)
     ws = _stats_workspace(M, N, X0c.device)
-    fsums, count, gamma, beta, eps, momentum, rm, rv, _ = below.fin
-    below.fin = None
+    below.fin, fin = None, below.fin                 # the first consumer finalises
     _call(_lib.omnipq_gemm_nt_e16_xyz_bnaffine, X0c, M, N, K, _p(X0c), X0c.shape[1], _p(below.Wp), below.Wp.shape[1],
-          _p(fsums), count, _p(gamma), _p(beta), eps, momentum, _p(rm),
-          _p(rv), _p(below.a), _p(below.b), _p(below.mean), _p(below.invstd), _p(Bw), K, _p(C), N, _p(sums), _p(ws))
+          _p(fin.sums), fin.count, *fin.tail(), _p(below.a), _p(below.b), _p(below.mean), _p(below.invstd), _p(Bw), K, _p(C), N,
+          _p(sums), _p(ws))
     return C
 
 
@@ -1196,17 +1194,15 @@ def _middle_layer(route, g, l, lay, below, X, X0, sums):
         lay.Y = _gemm_nt_stats(X, lay.Wp, g.P, lay.C, lay.K, sums)
 
 
-def _last_layer(route, g, lay, below, X, gamma, sums, dev):
+def _last_layer(route, g, lay, below, X, sums, dev):
     """The last GEMM; route.extrema: it also records every ball's extrema, so the pooling pass needs no Y (a planned stage
-    records them per group of the compact row space; pool_select merges a ball's).  -> pool (see _gemm_nt_stats) or None"""
+    records them per group of the compact row space; pool_select merges a ball's).  -> its BallExtrema or None"""
     pool = None
     if route.extrema:
         per = route.plan_gs or g.S
         ext16 = torch.empty((2, g.P // per, lay.C), device=dev, dtype=E16.dtype)
         ext8 = torch.empty((2, g.P // per, lay.C), device=dev, dtype=torch.uint8)
-        pool = (per, ext16[0], ext16[1], ext8[0], ext8[1])
-        if route.extrema == "one":
-            _plan_pool_gamma(gamma.detach())         # include/omnipq_sa.h: omnipq_row_plan.pool_gamma
+        pool = BallExtrema(per, ext16[0], ext16[1], ext8[0], ext8[1])
     if below is not None and route.feed[-1] == "yab":
         lay.Y = gemm_nt_affine(below.Y, below, lay.Wp, g.P, lay.C, lay.K, sums=sums, pool=pool, store=route.last != "no_dy")
     else:
@@ -1214,100 +1210,112 @@ def _last_layer(route, g, lay, below, X, gamma, sums, dev):
     return pool
 
 
-def _finalize(how, g, lay, sums, gamma, beta, bn, dev):
-    """Layer constants a | b | mean | invstd and the running-statistics update, where the route puts them.  -> lay.X"""
-    rm, rv, _, momentum, eps = bn
-    stats = torch.empty((4, lay.C), device=dev)
+# The BatchNorm finalise steps of a layer `lay` (a _Layer here, a rows_mlp._L), for the SA stage and the rows engine alike.
+# bn: running_mean, running_var, momentum, eps (a StageBN, a rows_mlp.Layer); conv_bias: the bias of the linear layer in front
+def batch_constants(lay, sums, count, gamma, beta, bn, conv_bias=None):
+    """training: the (4, C) buffer a | b | mean | invstd and its four views on `lay` -> the Finalize of the launch that fills
+    them: the layer's own (finalize_launch) or its first consumer's (lay.fin: gemm_nt_affine / _xyz, _pool_forward)"""
+    stats = torch.empty((4, lay.C), device=sums.device)
     lay.a, lay.b, lay.mean, lay.invstd = stats[0], stats[1], stats[2], stats[3]
-    count = float(g.P) * g.world
-    if how in ("consumer", "pool"):
-        # by the launch that reads the constants first: gemm_nt_affine / gemm_nt_xyz, omnipq_sa_pool_select_finalize
-        lay.fin = (sums, count, gamma.detach(), beta.detach(), eps, momentum, rm, rv, None)
-    elif how == "relu":
+    return Finalize(sums, count, gamma.detach(), beta.detach(), bn.eps, bn.momentum, bn.running_mean, bn.running_var,
+                    None if conv_bias is None else conv_bias.detach().float().contiguous())
+
+
+def finalize_launch(lay, rows, fin, relu):
+    """the layer's own launch: constants and running-statistics update; relu: with the normalise + ReLU pass.  -> lay.X"""
+    if relu:
         lay.X = torch.empty_like(lay.Y)
-        _call(_lib.omnipq_bn_finalize_relu, lay.Y, g.P, lay.C, count, _p(sums), _p(gamma.detach()), _p(beta.detach()), eps,
-              momentum, _p(rm), _p(rv), _p(None), _p(lay.Y), _p(lay.X), _p(lay.a), _p(lay.b), _p(lay.mean), _p(lay.invstd))
+        _call(_lib.omnipq_bn_finalize_relu, lay.Y, rows, lay.C, fin.count, _p(fin.sums), *fin.tail(), _p(fin.conv_bias),
+              _p(lay.Y), _p(lay.X), _p(lay.a), _p(lay.b), _p(lay.mean), _p(lay.invstd))
     else:
-        _call(_lib.omnipq_bn_finalize, sums, lay.C, count, _p(sums), _p(gamma.detach()), _p(beta.detach()), eps, momentum,
-              _p(rm), _p(rv), _p(lay.a), _p(lay.b), _p(lay.mean), _p(lay.invstd), _p(None))
+        _call(_lib.omnipq_bn_finalize, fin.sums, lay.C, fin.count, _p(fin.sums), *fin.tail(), _p(lay.a), _p(lay.b), _p(lay.mean),
+              _p(lay.invstd), _p(fin.conv_bias))
     return lay.X
 
 
-def _eval_layer(g, lay, X, gamma, beta, bn, last):
-    """eval mode: constants from the running estimates, every activation stored.  -> lay.X"""
-    rm, rv, _, _, eps = bn
-    lay.Y = _gemm_nt(X, lay.Wp, g.P, lay.C, lay.K)
-    lay.invstd = torch.rsqrt(rv + eps)
-    lay.mean = rm
+def running_constants(lay, rows, gamma, beta, bn, conv_bias=None, relu=True):
+    """eval mode: constants from the running estimates (the bias only shifts the mean); relu: then the normalise + ReLU pass
+    (the last layer of an SA stage leaves it to the pool).  -> lay.X"""
+    lay.invstd = torch.rsqrt(bn.running_var + bn.eps)
+    lay.mean = bn.running_mean - conv_bias.detach().float() if conv_bias is not None else bn.running_mean
     lay.a = (gamma.detach() * lay.invstd).contiguous()
-    lay.b = (beta.detach() - rm * lay.a).contiguous()
-    if not last:
+    lay.b = (beta.detach() - lay.mean * lay.a).contiguous()
+    if relu:
         lay.X = torch.empty_like(lay.Y)
-        _call(_lib.omnipq_bnrelu, lay.Y, g.P, lay.C, _p(lay.Y), _p(lay.a), _p(lay.b), _p(lay.X))
+        _call(_lib.omnipq_bnrelu, lay.Y, rows, lay.C, _p(lay.Y), _p(lay.a), _p(lay.b), _p(lay.X))
     return lay.X
 
 
-def _eval_chain(g, xyz_c, cen_c, idx, feat_pm, params, bn_cfg, dev):
-    """route "chain" (see EVAL_CHAIN): the whole stage as ONE launch.  -> (layers, (out f32 [B][M][C], its 16-bit twin))"""
-    L = len(bn_cfg)
+def _batch_norm(how, g, lay, sums, gamma, beta, bn):
+    """a training layer's statistics exchange, its finalise where the route puts it (StageRoute.finalize), its step counter"""
+    _allreduce_(sums, g.world)
+    fin = batch_constants(lay, sums, float(g.P) * g.world, gamma, beta, bn)
+    if how in ("consumer", "pool"):
+        lay.fin = fin
+    else:
+        finalize_launch(lay, g.P, fin, relu=how == "relu")
+    bump(bn.num_batches_tracked)
+    return lay.X
+
+
+def _eval_chain(route, g, plan, xyz_c, cen_c, idx, feat_pm, params, bn, dev):
+    """route "chain" (see EVAL_CHAIN): the whole stage as ONE launch.  -> what _forward_layers returns: no stored rows, pooled
+    inside the launch, and no arg-max -- there is no backward"""
+    L = len(bn)
     layers = [_new_layer(l, params[3 * l], g, False) for l in range(L)]
     recs = (_InferLayer * L)()
     keep = []                                   # the f32 vectors the records point to (copies, where a buffer is not f32)
     for l, (lay, rec) in enumerate(zip(layers, recs)):
-        rm, rv, _, _, eps = bn_cfg[l]
-        vecs = [v.detach().float().contiguous() for v in (params[3 * l + 1], params[3 * l + 2], rm, rv)]
+        vecs = [v.detach().float().contiguous() for v in (*params[3 * l + 1:3 * l + 3], bn[l].running_mean, bn[l].running_var)]
         keep.append(vecs)
         rec.W, rec.ldw, rec.C = lay.Wp.data_ptr(), lay.Wp.stride(0), lay.C
         rec.gamma, rec.beta, rec.running_mean, rec.running_var = (v.data_ptr() for v in vecs)
-        rec.eps = eps
+        rec.eps = bn[l].eps
     C = layers[-1].C
     out_f32 = torch.empty((g.B, g.M, C), device=dev, dtype=torch.float32)
     out_pm = torch.empty((g.B * g.M, C), device=dev, dtype=E16.dtype)
     _call(_lib.omnipq_sa_infer, xyz_c, g.B, g.N, g.M, g.S, g.cin, g.kpad, g.inv_r, _p(xyz_c), _p(cen_c), _p(idx), _p(feat_pm), L,
           ctypes.byref(recs), _p(out_f32), _p(out_pm))
-    return layers, (out_f32, out_pm)
+    return layers, None, None, (out_f32, out_pm, None, None)
 
 
-def _forward_layers(route, g, plan, xyz_c, cen_c, idx, feat_pm, params, bn_cfg, dev):
-    """-> (layers, X0, the relative coordinates of a "source" first layer, pool of the last GEMM | the outputs of "chain")"""
-    L = len(bn_cfg)
-    layers, X0, Xrel, pool = [], None, None, None
-    if route.first == "chain":
-        layers, pool = _eval_chain(g, xyz_c, cen_c, idx, feat_pm, params, bn_cfg, dev)
-        return layers, None, None, pool
-    if route.first != "source":
-        X0 = _gather_rows(g, xyz_c, cen_c, idx, feat_pm, 8 if route.first == "xyz" else g.kpad, dev)
-    X = X0
+def _forward_layers(route, g, plan, xyz_c, cen_c, idx, feat_pm, params, bn, dev):
+    """every route but "chain": layer by layer, then the pool.  -> (layers, X0, the relative coordinates of a "source" first
+    layer, what _pool_forward returns)"""
+    L = len(bn)
+    layers, Xrel, pooled = [], None, None
+    xpad = 8 if route.first == "xyz" else g.kpad
+    X = X0 = None if route.first == "source" else _gather_rows(g, xyz_c, cen_c, idx, feat_pm, xpad, dev)
     for l in range(L):
-        W, gamma, beta = params[3 * l], params[3 * l + 1], params[3 * l + 2]
+        W, gamma, beta = params[3 * l:3 * l + 3]
         lay = _new_layer(l, W, g, route.training)
+        sums = zeros_f64(2, lay.C, dev) if route.training else None
         if not route.training:
-            X = _eval_layer(g, lay, X, gamma, beta, bn_cfg[l], l == L - 1)
-            layers.append(lay)
-            continue
-        sums = zeros_f64(2, lay.C, dev)
-        if l == L - 1:
-            pool = _last_layer(route, g, lay, layers[-1] if l else None, X, gamma, sums, dev)
-        elif l > 0:
-            _middle_layer(route, g, l, lay, layers[-1], X, X0, sums)
-        elif route.first == "xyz":
-            _first_generated(g, lay, X0, sums, dev)
-        elif route.first == "source":
-            Xrel = _first_on_source(g, lay, plan, xyz_c, cen_c, idx, feat_pm.reshape(g.B * g.N, g.cin), sums, dev)
+            lay.Y = _gemm_nt(X, lay.Wp, g.P, lay.C, lay.K)         # eval mode: every activation stored, the last one for the pool
+            X = running_constants(lay, g.P, gamma, beta, bn[l], relu=l < L - 1)
+        elif l == L - 1:
+            # route.extrema "one": for the last GEMM and the pool-select launch the plan names the gamma whose sign selects
+            with _row_plan(plan, g.P, pool_gamma=gamma.detach() if route.extrema == "one" else None):
+                pool = _last_layer(route, g, lay, layers[-1] if l else None, X, sums, dev)
+                _batch_norm(route.finalize[l], g, lay, sums, gamma, beta, bn[l])
+                pooled = _pool_forward(route, g, lay, pool, dev)
         else:
-            lay.Y = _gemm_nt_stats(X0, lay.Wp, g.P, lay.C, lay.K, sums)       # first layer "grouped": GEMM + batch statistics
-        _allreduce_(sums, g.world)
-        X = _finalize(route.finalize[l], g, lay, sums, gamma, beta, bn_cfg[l], dev)
-        bump(bn_cfg[l][2])
+            if l > 0:
+                _middle_layer(route, g, l, lay, layers[-1], X, X0, sums)
+            elif route.first == "xyz":
+                _first_generated(g, lay, X0, sums, dev)
+            elif route.first == "source":
+                Xrel = _first_on_source(g, lay, plan, xyz_c, cen_c, idx, feat_pm.reshape(g.B * g.N, g.cin), sums, dev)
+            else:
+                lay.Y = _gemm_nt_stats(X0, lay.Wp, g.P, lay.C, lay.K, sums)   # first layer "grouped": GEMM + batch statistics
+            X = _batch_norm(route.finalize[l], g, lay, sums, gamma, beta, bn[l])
         layers.append(lay)
-    return layers, X0, Xrel, pool
+    return layers, X0, Xrel, pooled or _pool_forward(route, g, layers[-1], None, dev)      # (eval mode: the pool scans Y)
 
 
 def _pool_forward(route, g, last, pool, dev):
     """max-pool over every ball -> (out f32 [B][M][C], its 16-bit twin, the arg-max rows, the selected pre-BN values | None)"""
     B, M, S = g.B, g.M, g.S
-    if route.first == "chain":                  # pooled inside the stage's one launch; no arg-max: there is no backward
-        return pool[0], pool[1], None, None
     out_f32 = torch.empty((B, M, last.C), device=dev, dtype=torch.float32)
     out_pm = torch.empty((B * M, last.C), device=dev, dtype=E16.dtype)
     arg = torch.empty((B * M, last.C), device=dev, dtype=torch.uint8)
@@ -1316,14 +1324,12 @@ def _pool_forward(route, g, last, pool, dev):
         return out_f32, out_pm, arg, None
     ysel = torch.empty((B * M, last.C), device=dev, dtype=E16.dtype)
     if route.finalize[-1] == "pool":
-        fsums, count, pg, pb, peps, pmom, prm, prv, _ = last.fin
-        last.fin = None
-        _call(_lib.omnipq_sa_pool_select_finalize, out_pm, B * M, last.C, _p(pool[1]), _p(pool[2]), _p(pool[3]), _p(pool[4]),
-              _p(fsums), count, _p(pg), _p(pb), peps, pmom, _p(prm), _p(prv), _p(last.a), _p(last.b), _p(last.mean),
-              _p(last.invstd), _p(out_f32), _p(out_pm), _p(arg), _p(ysel))
+        last.fin, fin = None, last.fin                # the first consumer finalises
+        _call(_lib.omnipq_sa_pool_select_finalize, out_pm, B * M, last.C, *pool.args(), _p(fin.sums), fin.count, *fin.tail(),
+              _p(last.a), _p(last.b), _p(last.mean), _p(last.invstd), _p(out_f32), _p(out_pm), _p(arg), _p(ysel))
     else:
-        _call(_lib.omnipq_sa_pool_select, out_pm, B * M, last.C, _p(pool[1]), _p(pool[2]), _p(pool[3]), _p(pool[4]),
-              _p(last.a), _p(last.b), _p(out_f32), _p(out_pm), _p(arg), _p(ysel))
+        _call(_lib.omnipq_sa_pool_select, out_pm, B * M, last.C, *pool.args(), _p(last.a), _p(last.b), _p(out_f32), _p(out_pm),
+              _p(arg), _p(ysel))
     return out_f32, out_pm, arg, ysel
 
 
@@ -1540,41 +1546,62 @@ def _tail_on_source(ctx, dY, grads, dfr):
     return d_xyz, d_cen, d_feat
 
 
-_PARAMS_AT = 11         # FusedSAStage.apply: its arguments in front of *params
+# a layer's BatchNorm state as the stage uses it: the module's own buffers, and its two numbers
+StageBN = collections.namedtuple("StageBN", "running_mean running_var num_batches_tracked momentum eps")
+
+
+class StageCall(typing.NamedTuple):
+    """What run() knows of a stage pass and the tensors do not say: ONE argument of FusedSAStage.apply."""
+    label: str             # the stage's name for the timing sink, forward and backward ("sa1" .. "vote", or m<npoint>s<nsample>)
+    radius: float
+    normalize_xyz: bool
+    training: bool
+    sync: bool             # do the stage's BatchNorm layers exchange their statistics across ranks (SyncBatchNorm)?
+    no_grad: bool          # autograd was off at the call: asked by apply's caller, inside a Function's forward it is always off
+    bn: tuple              # a StageBN per layer
+    plan: typing.Any       # the stage's _Plan and the chain_plan.Csr of its backward where they were made ahead of the stage
+    csr: typing.Any        # (run(group=)), else None
+
+
+def stage_call(module, grad_enabled, plan=None, csr=None):
+    """The StageCall of a PointnetSAModuleVotes (no launch, no tensor made)."""
+    bns = [_bn_of(layer)[1] for layer in module.mlp_module]
+    return StageCall(getattr(module, "omnipq_stage", None) or f"m{module.npoint}s{module.nsample}", float(module.radius),
+                     bool(module.normalize_xyz), bool(module.training), all(bool(bn_syncs(bn)) for bn in bns), not grad_enabled,
+                     tuple(StageBN(bn.running_mean, bn.running_var, bn.num_batches_tracked, float(bn.momentum), float(bn.eps))
+                           for bn in bns), plan, csr)
+
+
+_PARAMS_AT = 6          # FusedSAStage.apply: its arguments in front of *params
 
 
 class FusedSAStage(torch.autograd.Function):
-    """forward(xyz, new_xyz, features|None, feat_pm|None, idx, radius, normalize_xyz, training, bn_cfg, plan, csr, *params)
-
-    params = (W_0, gamma_0, beta_0, W_1, ...); bn_cfg = list of (running_mean, running_var,
-    num_batches_tracked, momentum, eps) per layer; plan, csr: the stage's _Plan and the chain_plan.Csr of its backward where
-    they were made ahead of the stage (run(group=)), else None.  Returns (B, C_last, M) f32.
-    """
+    """forward(xyz, new_xyz, features|None, feat_pm|None, idx, call, *params) -> (B, C_last, M) f32 and its 16-bit
+    position-major twin.  call: the pass's StageCall; params = (W_0, gamma_0, beta_0, W_1, ...)."""
 
     @staticmethod
-    def forward(ctx, xyz, new_xyz, features, feat_pm, idx, radius, normalize_xyz, training, bn_cfg, plan, csr, *params):
+    def forward(ctx, xyz, new_xyz, features, feat_pm, idx, call, *params):
         ctx.e16 = E16.dtype
         ctx.n_inputs = _PARAMS_AT + len(params)
-        ctx.stage_label = _STAGE_LABEL
+        ctx.stage_label = call.label
         with _tagged("@sa", ctx.stage_label):
-            return FusedSAStage._forward(ctx, xyz, new_xyz, features, feat_pm, idx, radius, normalize_xyz, training,
-                                         bn_cfg, plan, csr, *params)
+            return FusedSAStage._forward(ctx, xyz, new_xyz, features, feat_pm, idx, call, *params)
 
     @staticmethod
-    def _forward(ctx, xyz, new_xyz, features, feat_pm, idx, radius, normalize_xyz, training, bn_cfg, plan, csr, *params):
+    def _forward(ctx, xyz, new_xyz, features, feat_pm, idx, call, *params):
         dev = xyz.device
         B, N, _ = xyz.shape
         M, S = idx.shape[1], idx.shape[2]
         L = len(params) // 3
+        training, plan = call.training, call.plan
         cin_raw = 0 if features is None else features.shape[1]
         cin = _round_up(cin_raw, 8)
-        g = _Geom(B, N, M, S, B * M * S, cin, cin_raw, _round_up(cin + 3, 32), (1.0 / radius) if normalize_xyz else 1.0,
-                  _world() if (training and _SYNC) else 1)
+        g = _Geom(B, N, M, S, B * M * S, cin, cin_raw, _round_up(cin + 3, 32),
+                  (1.0 / call.radius) if call.normalize_xyz else 1.0, _world() if (training and call.sync) else 1)
         route = stage_route(training, B, N, M, S, cin_raw, [params[3 * l].shape[0] for l in range(L)], features is not None,
                             ctx.needs_input_grad[0] or ctx.needs_input_grad[1],
                             features is not None and ctx.needs_input_grad[2], None if plan is None else plan.gs,
-                            plan is not None and plan.unit_src is not None,
-                            no_grad=_NO_GRAD)
+                            plan is not None and plan.unit_src is not None, no_grad=call.no_grad)
         _count_uses(route)
         if features is None:
             feat_pm = None
@@ -1589,14 +1616,14 @@ class FusedSAStage(torch.autograd.Function):
         elif not route.plan_arrives:
             plan = make_row_plan(idx, g.P)
         with _row_plan(plan, g.P):
-            layers, X0, Xrel, pool = _forward_layers(route, g, plan, xyz_c, cen_c, idx, feat_pm, params, bn_cfg, dev)
-            out_f32, out_pm, arg, ysel = _pool_forward(route, g, layers[-1], pool, dev)
+            layers, X0, Xrel, (out_f32, out_pm, arg, ysel) = (_eval_chain if route.first == "chain" else _forward_layers)(
+                route, g, plan, xyz_c, cen_c, idx, feat_pm, params, call.bn, dev)
         ctx.route, ctx.geom, ctx.plan = route, g, plan
         ctx.layers, ctx.X0 = layers, X0
         ctx.hoist = (feat_pm.reshape(B * N, cin), Xrel) if route.first == "source" else None
         # where a layer's weight gradient may be written behind autograd's back (deferred_wgrads): Parameters only
         ctx.wtargets = [grad_target(params[3 * l]) for l in range(L)] if training else None
-        ctx.idx, ctx.csr_ahead = idx, csr
+        ctx.idx, ctx.csr_ahead = idx, call.csr
         ctx.out_pm, ctx.arg, ctx.ysel = out_pm, arg, ysel
         ctx.has_features = features is not None
         ctx.feat_dtype = features.dtype if features is not None else None
@@ -1702,8 +1729,6 @@ def run(module, xyz, new_xyz, features, group=None):
     """ball query + fused stage -> (B, C_out, npoint) f32.  group: a chain_plan.StageAhead -- the ball query (and row plan,
     and backward CSR with the row space it was built in) of this stage made ahead of it (they depend on coordinates only:
     Pointnet2Backbone's sampling chain)."""
-    global _STAGE_LABEL
-    _STAGE_LABEL = getattr(module, "omnipq_stage", None) or f"m{module.npoint}s{module.nsample}"
     idx = plan = csr = None
     if group is not None and group.idx is not None and \
             tuple(group.idx.shape) == (xyz.shape[0], new_xyz.shape[1], module.nsample) and group.idx.dtype == torch.int32:
@@ -1711,24 +1736,16 @@ def run(module, xyz, new_xyz, features, group=None):
         if group.plan_state is not None:
             B_, M_, S_ = idx.shape
             plan = plan_from_state(group.plan_state, B_, M_, B_ * M_ * S_)
+    call = stage_call(module, torch.is_grad_enabled(), plan, csr)
     if idx is None:
-        with _tagged("@sa", _STAGE_LABEL):
+        with _tagged("@sa", call.label):
             idx = pointnet2_utils.ball_query(module.radius, module.nsample, xyz, new_xyz)
-    params, bn_cfg = [], []
+    params = []
     for layer in module.mlp_module:
         conv, bn = _bn_of(layer)
         params += [conv.weight, bn.weight, bn.bias]
-        bn_cfg.append((bn.running_mean, bn.running_var, bn.num_batches_tracked, float(bn.momentum), float(bn.eps)))
-    global _SYNC
-    _SYNC = all(bool(bn_syncs(_bn_of(layer)[1])) for layer in module.mlp_module)
     feat_pm = None if features is None else rows16_of(features, (features.shape[0], features.shape[2], features.shape[1]))
-    global _NO_GRAD
-    _NO_GRAD = not torch.is_grad_enabled()
-    try:
-        out, twin = FusedSAStage.apply(xyz, new_xyz, features, feat_pm, idx, float(module.radius),
-                                       bool(module.normalize_xyz), bool(module.training), bn_cfg, plan, csr, *params)
-    finally:
-        _NO_GRAD = False
+    out, twin = FusedSAStage.apply(xyz, new_xyz, features, feat_pm, idx, call, *params)
     out.omnipq_rows16 = twin        # consumers that work on bf16 rows (next SA stage, FP modules) skip their cast
     return out
 
