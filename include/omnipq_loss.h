@@ -55,7 +55,11 @@ int omnipq_loss_assign(int b, int k, int k2, const float *query, const float *gt
  *   terms[h][7] 0
  * with a = assignment.  terms: float[heads][8].  sums: double[heads][8] scratch.
  * Backward (omnipq_loss_box_rows_grad): g_terms float[heads][8] = dLoss/dterms; every g_* tensor (same shape as its
- * input, all overwritten, any may be NULL) receives the gradient. */
+ * input, all overwritten, any may be NULL) receives the gradient.
+ * Out-of-range indices are clamped, never refused: assignment to [0, k2 - 1], gt_heading_class to [0, nh - 1],
+ * gt_size_class to [0, ns - 1], gt_sem_cls to [0, nc - 1]; a call gives what the clamped index gives.  A gradient entry the
+ * formulas make zero (an unlabelled row, a masked-out row of the objectness scores, a class column other than the assigned
+ * one in the two residual tensors) is written as +0.0. */
 typedef struct {
   int heads, b, k, k2, nh, ns, nc;             /* heading bins, size clusters, semantic classes (each <= 64) */
   const float *objectness_scores[OMNIPQ_LOSS_MAX_HEADS];           /* (b, k, 2) */
@@ -99,7 +103,9 @@ int omnipq_loss_box_rows_grad(const omnipq_box_rows_desc *d, const float *g_term
  *   terms[h][0] score   w[label] CE(quad_scores, label) * mask                     / (sum mask + 1e-6)
  *   terms[h][1] centre  smoothl1(gt_center[a] - quad_center) * label               / (sum label + 1e-6)
  *   terms[h][2] normal  (1 - cos(normal_vector, gt_normal[a])) * label             (torch.cosine_similarity, eps 1e-8)
- *   terms[h][3] size    smoothl1(quad_size - gt_size[a]) * label */
+ *   terms[h][3] size    smoothl1(quad_size - gt_size[a]) * label
+ *   terms[h][4..7] 0
+ * assignment is clamped to [0, k2 - 1] as in the box call; gradients of unlabelled rows are +0.0. */
 typedef struct {
   int heads, b, k, k2;
   const float *quad_scores[OMNIPQ_LOSS_MAX_HEADS];     /* (b, k, 2) */
@@ -132,7 +138,10 @@ int omnipq_loss_quad_rows_grad(const omnipq_quad_rows_desc *d, const float *g_te
  * vote_label_mask is set:  loss = sum_s mask_s min_j min_i |vote_i - gt_j|_1 / (sum_s mask_s + 1e-6).
  * seed_xyz (b, s, 3), vote_xyz (b, s * vote_factor, 3), seed_inds (b, s) int32, vote_label (b, n, 3 * gt_votes),
  * vote_label_mask (b, n) int64.  sums: double[2] scratch; loss: float[1].
- * Backward: g_loss float[1] -> g_vote_xyz (b, s * vote_factor, 3), overwritten. */
+ * seed_inds is clamped to [0, n - 1].  On ties the first vote and the first ground-truth vote win.
+ * Backward: g_loss float[1] -> g_vote_xyz (b, s * vote_factor, 3), overwritten: the winning vote of a seed whose mask is set
+ * receives g_loss sign(vote - gt) / (sum mask + 1e-6), every other entry +0.0.  `sums` must be the buffer the forward call
+ * filled. */
 int omnipq_loss_votes(int b, int s, int n, int vote_factor, int gt_votes, const float *seed_xyz, const float *vote_xyz,
                       const int *seed_inds, const float *vote_label, const long long *vote_label_mask, double *sums,
                       float *loss, void *stream);
@@ -149,10 +158,13 @@ int omnipq_loss_votes_grad(int b, int s, int n, int vote_factor, int gt_votes, c
  *   loss += relu(-delta) * inside / (number of such boxes in the scene);   collisions += relu(-delta) * inside > 1e-4
  * center (b, k, 3), size_scores (b, k, ns), size_residuals (b, k, ns, 3) [metres, NOT normalised], object_label /
  * object_assignment (b, k) int64, sem_cls_label (b, k2) int64, mean_size64 double (ns, 3), quad_center / normal (b, q, 3),
- * quad_size (b, q, 2), quad_label (b, q) int64, not_solid = bit mask over class ids (< 64).
+ * quad_size (b, q, 2), quad_label (b, q) int64, not_solid = bit mask over class ids (< 64): a class id outside 0..63
+ * (64 and above, or negative) has no bit and counts as solid.  object_assignment is clamped to [0, k2 - 1]; on equal
+ * size scores the first maximum wins; a scene without such a box contributes nothing (no division by zero).
  * out: float[2] = (loss, collisions); sums: double[2] scratch.
  * Backward: g_out float[1] = dLoss/d(loss); g_center (b, k, 3), g_size_residuals (b, k, ns, 3), g_quad_center (b, q, 3),
- * g_normal (b, q, 3) -- all overwritten (quad_size only gates: no gradient, as in the reference). */
+ * g_normal (b, q, 3) -- all overwritten (quad_size only gates: no gradient, as in the reference); the z components, the
+ * boxes and quads that take no part and the size classes other than the argmax receive +0.0. */
 typedef struct {
   int b, k, k2, ns, q;
   const float *center, *size_scores, *size_residuals;

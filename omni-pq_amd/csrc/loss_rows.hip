@@ -316,7 +316,7 @@ __global__ __launch_bounds__(kLossThreads) void votes_kernel(long long seeds, in
         const float *v = vote_xyz + (t * vf + i) * 3;
         float *o = g_vote + (t * vf + i) * 3;
         const float ex = v[0] - gx[bj], ey = v[1] - gy[bj], ez = v[2] - gz[bj];
-        const bool hit = i == bi;
+        const bool hit = i == bi && m != 0.f;                // a seed without a vote label: +0, not g_loss * 0 * sign
         o[0] = hit ? coef * (ex > 0.f ? 1.f : (ex < 0.f ? -1.f : 0.f)) : 0.f;
         o[1] = hit ? coef * (ey > 0.f ? 1.f : (ey < 0.f ? -1.f : 0.f)) : 0.f;
         o[2] = hit ? coef * (ez > 0.f ? 1.f : (ez < 0.f ? -1.f : 0.f)) : 0.f;

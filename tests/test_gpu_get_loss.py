@@ -9,7 +9,8 @@ import torch
 
 from conftest import REPO  # noqa: F401  (sys.path set-up)
 import loss_inputs
-from test_get_loss_oracle import CASES, GRAD_RTOL, TERM_RTOL, build, case_inputs, check_against_golden
+from test_get_loss_oracle import (CASES, GRAD_RTOL, TERM_RTOL, HeadingConfig, build, case_inputs, check_against_golden,
+                                  heading_case_inputs)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,14 +28,14 @@ def test_get_loss_reproduces_the_reference_fixture(name):
     check_against_golden(name, loss, ep, leaves)
 
 
-def compare_with_oracle(seed, pc_loss, **kw):
+def compare_with_oracle(seed, pc_loss, make=loss_inputs.make, config=loss_inputs.Config, **kw):
     from oracle import get_loss_oracle
-    lab, pred = loss_inputs.make(seed, **kw)
+    lab, pred = make(seed, **kw)
     ep_o, leaves_o = build(lab, pred, "cpu")
-    loss_o, ep_o = get_loss_oracle.get_loss(ep_o, loss_inputs.Config, pc_loss=pc_loss)
+    loss_o, ep_o = get_loss_oracle.get_loss(ep_o, config, pc_loss=pc_loss)
     loss_o.backward()
     ep, leaves = build(lab, pred, "cuda")
-    loss, ep = hip().get_loss(ep, loss_inputs.Config, pc_loss=pc_loss)
+    loss, ep = hip().get_loss(ep, config, pc_loss=pc_loss)
     loss.backward()
     for k, want in ep_o.items():
         if "loss" in k:
@@ -57,6 +58,13 @@ def test_get_loss_against_the_oracle_at_the_benchmark_batch():
 
 def test_get_loss_without_the_constraint_term_and_other_head_counts():
     compare_with_oracle(31, False, B=2, K=100, KQ=37, num_seed=300, N=1000)
+
+
+def test_get_loss_with_twelve_heading_bins_against_the_oracle():
+    """num_heading_bin = 12 with heading labels spread over all bins and residual labels over +-pi / 12: the heading cross
+    entropy over twelve columns, the residual's column choice and its pi / nh scale, none of which one bin exercises (the
+    oracle's side of it: test_oracle_with_twelve_heading_bins_against_autograd_of_the_plain_formula)."""
+    compare_with_oracle(6, True, make=heading_case_inputs, config=HeadingConfig, B=2)
 
 
 def test_pieces_called_one_by_one_agree_with_get_loss():
