@@ -41,8 +41,12 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 # decision of the clipping.  COMMON says so already: the file's own entry keeps that true should COMMON ever change.
 # detect.hip: the decoded heading is a product and a sum in f64, each rounded on its own, and its corners must keep the bits
 # of eval_ops.hip's (csrc/box_geom.h); the same reason for an entry of its own.
+# point_normals.hip: the neighbour order is decided by the f32 d2 of the numerics contract (its one fused step is spelled
+# out, csrc/common.h: sumsq3) and the sign decisions of the smoothing and orientation by f64 sums stated term by term
+# (include/omnipq_normals.h); the same reason again.
 EXTRA = {"fps.hip": ["-fno-slp-vectorize"], "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
-         "eval_iou.hip": ["-ffp-contract=off"], "detect.hip": ["-ffp-contract=off"]}
+         "eval_iou.hip": ["-ffp-contract=off"], "detect.hip": ["-ffp-contract=off"],
+         "point_normals.hip": ["-ffp-contract=off"]}
 
 
 def hipcc():

@@ -12,6 +12,7 @@
 // once per chunk and reused for the QPW queries; a wave stops as soon as all its balls are
 // full.  b*m/QPW waves keep all 256 CUs busy (sa1: 4096 waves).
 #include "common.h"
+#include "hash_grid.h"
 
 namespace omnipq {
 
@@ -89,31 +90,8 @@ __global__ __launch_bounds__(256) void ball_query_kernel(int n, int m, float rad
 //      (n <= a few hundred: rank = number of smaller hits), the first nsample stored in order, the tail padded with
 //      the smallest.  Unrelated cells that share a bucket only add candidates, which the distance test rejects.
 //      More hits than the LDS list holds: that centre falls back to the brute-force walk.
-constexpr int kBqBuckets = 8192;
+// (steps 1 and 3, the cell / bucket functions and kBqBuckets: csrc/hash_grid.h, shared with the k-NN query)
 constexpr int kBqCap = 1024;          // hits kept per centre before the fallback
-
-__device__ __forceinline__ int bq_cell(float x, float inv_h) { return (int)floorf(x * inv_h); }
-__device__ __forceinline__ int bq_bucket(int cx, int cy, int cz) {
-  return (int)(((unsigned)cx * 73856093u) ^ ((unsigned)cy * 19349663u) ^ ((unsigned)cz * 83492791u)) & (kBqBuckets - 1);
-}
-
-__global__ __launch_bounds__(256) void bq_cell_kernel(long long total, float inv_h, const float *__restrict__ xyz,
-                                                     int *__restrict__ bucket) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  bucket[i] = bq_bucket(bq_cell(xyz[i * 3 + 0], inv_h), bq_cell(xyz[i * 3 + 1], inv_h), bq_cell(xyz[i * 3 + 2], inv_h));
-}
-
-__global__ __launch_bounds__(256) void bq_sorted_xyz_kernel(long long total, int n, const float *__restrict__ xyz,
-                                                           const int *__restrict__ order, float *__restrict__ sorted) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const long long base = (i / n) * n;
-  const long long src = base + order[i];
-  sorted[i * 3 + 0] = xyz[src * 3 + 0];
-  sorted[i * 3 + 1] = xyz[src * 3 + 1];
-  sorted[i * 3 + 2] = xyz[src * 3 + 2];
-}
 
 __global__ __launch_bounds__(256) void bq_grid_kernel(int n, int m, float inv_h, float radius2, int nsample,
                                                      const float *__restrict__ new_xyz, const float *__restrict__ xyz,
@@ -230,9 +208,6 @@ __global__ __launch_bounds__(256) void bq_grid_kernel(int n, int m, float inv_h,
 }
 
 }  // namespace omnipq
-
-extern "C" int omnipq_sa_build_csr(int b, int n, int m, int s, const int *idx, int *offsets, int *order, int *scratch,
-                                   const omnipq_row_plan *plan, void *stream);
 
 // Workspace of omnipq_ball_query_grid in bytes.
 extern "C" long long omnipq_ball_query_grid_workspace_bytes(int b, int n) {

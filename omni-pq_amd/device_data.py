@@ -130,16 +130,24 @@ class SceneBank:
         self._dev = None
         return len(self.names) - 1
 
-    def add_scene(self, name, vertices, normals, instance_labels, semantic_labels, boxes, rectangles, total_quad_num,
-                  horizontal_quads):
+    def add_scene(self, name, vertices, normals=None, instance_labels=None, semantic_labels=None, boxes=None, rectangles=None,
+                  total_quad_num=None, horizontal_quads=None):
         """vertices (n, 6) xyz + rgb (or (n, 3) without use_color), normals (n, 3), instance_labels, semantic_labels (n),
         boxes (nb, 7) centre, size, nyu40 id (`_bbox.npy`), and what get_quads(name) returns.  -> the scene's slot.
+        normals=None: the scene has no `.normal.npy`; they are estimated on the device at upload with the constants of
+        scannet/compute_normal_for_pc.py (point_normals.estimate_normals) and stand in the arena where given ones would.
+        Only `normals` may be left out (the defaults of the arguments behind it keep the positional order of old calls).
         The arena is float32: vertices and normals are taken as the float32 arrays the dataset's files hold (the bit-for-bit
         agreement with the reference's item is for such files; a float64 file would be rounded here, not after the rotation)."""
         if self.config is None:
             raise ValueError("SceneBank: labelled scenes need a dataset_config (nyu40ids, mean_size_arr)")
+        if any(v is None for v in (instance_labels, semantic_labels, boxes, rectangles, total_quad_num, horizontal_quads)):
+            raise TypeError("SceneBank.add_scene: only `normals` may be left out")
         mesh_vertices = np.array(vertices, np.float32)
         n = mesh_vertices.shape[0]
+        estimate = normals is None
+        if estimate:
+            normals = np.zeros((n, 3), np.float32)           # the arena's rows; filled by upload()
         boxes = np.asarray(boxes, np.float64).reshape(-1, 7)
         rectangles = np.asarray(rectangles, np.float64)
         rectangles = rectangles.reshape(-1, rectangles.shape[-1] if rectangles.ndim == 2 else 8)
@@ -187,13 +195,20 @@ class SceneBank:
                                                     horizontal_quads.shape[0], 0, 0], np.int32)}
         if colors is not None:
             host["colors"] = np.ascontiguousarray(colors, np.float32)
+        host["estimate_normals"] = estimate
         return self._admit(name, 0, host)
 
-    def add_unlabelled_scene(self, name, vertices, normals, boxes):
+    def add_unlabelled_scene(self, name, vertices, normals=None, boxes=None):
         """The ARKit item: vertices (n, 3), normals (n, 3), boxes (nb, 7) centre, size, heading as `_bbox.npy` holds them.
         The static box preparation of arkitscenes_dataset.py:102-131 runs here, once (`_align_boxes`).  float32 points and
-        normals are assumed, as the dataset's files hold them."""
+        normals are assumed, as the dataset's files hold them.  normals=None: estimated on the device at upload, as in
+        add_scene (ARKitScenes/dataset/compute_normal_for_pc.py has the same constants)."""
+        if boxes is None:
+            raise TypeError("SceneBank.add_unlabelled_scene: only `normals` may be left out")
         points = np.array(vertices, np.float32)[:, 0:3]
+        estimate = normals is None
+        if estimate:
+            normals = np.zeros((points.shape[0], 3), np.float32)
         bb = np.array(boxes, np.float64).reshape(-1, 7)
         if bb.shape[0] > MAX_NUM_OBJ:
             raise ValueError(f"SceneBank: {name}: {bb.shape[0]} boxes, the item holds {MAX_NUM_OBJ}")
@@ -206,7 +221,7 @@ class SceneBank:
         labels[:MAX_NUM_OBJ * 7].reshape(MAX_NUM_OBJ, 7)[:bb.shape[0], 0:6] = bb[:, 0:6]
         n = mesh_vertices.shape[0]
         host = {"points": np.ascontiguousarray(mesh_vertices), "normals": np.ascontiguousarray(normals, np.float32),
-                "labels": labels, "meta": np.array([n, 0, bb.shape[0], 0, 0, 0, 0, 0], np.int32)}
+                "labels": labels, "meta": np.array([n, 0, bb.shape[0], 0, 0, 0, 0, 0], np.int32), "estimate_normals": estimate}
         return self._admit(name, 1, host)
 
     def __len__(self):
@@ -237,6 +252,7 @@ class SceneBank:
         dev["meta"] = torch.from_numpy(np.stack([r["meta"] for r in self._rows])).to(self.device)
         dev["labels"] = torch.from_numpy(np.stack([r["labels"] for r in self._rows])).to(self.device)
         dev["rows_total"] = int(counts.sum())
+        self._estimate_missing_normals(dev, counts)
         if self.flavour == 0:
             dev["nyu40ids"] = torch.tensor(np.asarray(self.config.nyu40ids).astype(np.int32), device=self.device)
             dev["mean_size"] = torch.tensor(np.asarray(self.config.mean_size_arr, np.float64), device=self.device)
@@ -244,6 +260,22 @@ class SceneBank:
             self._seed = torch.tensor([self._seed_value], dtype=torch.int64, device=self.device)
         self._dev = dev
         return dev
+
+    def _estimate_missing_normals(self, dev, counts):
+        """Scenes registered without normals: the recipe of compute_normal_for_pc.py:34-47 on the uploaded float32 coordinates
+        (k = 100, 5 smoothing steps, the recipe's view centre), written into the arena's rows.  The grid's cell comes from the
+        host copy of the points: nothing is read back from the device."""
+        if not any(r["estimate_normals"] for r in self._rows):
+            return
+        import point_normals
+        first = 0
+        for r, n in zip(self._rows, counts.tolist()):
+            if r["estimate_normals"]:
+                xyz = dev["points"][first:first + n, 0:3].contiguous().unsqueeze(0)
+                host_xyz = r["points"][:, 0:3]
+                cell = _ext.default_knn_cell(host_xyz.min(0), host_xyz.max(0), n, point_normals.RECIPE_K)
+                point_normals.estimate_normals(xyz, cell=cell, out=dev["normals"][first:first + n].unsqueeze(0))
+            first += n
 
     @property
     def seed(self):

@@ -486,6 +486,62 @@ def ball_query(new_xyz, xyz, radius, nsample, out=None):
     return idx
 
 
+KNN_MAX_K = 128          # include/omnipq_normals.h
+
+# default_knn_cell: cell = KNN_CELL_FACTOR * r_k, r_k = sqrt(k * A / (pi * n)) the radius that holds k points on a surface of
+# area A = the bounding box's.  The factor is the best of the cell sweep of tools/bench_normals.py (profiles/normals_ab.txt;
+# DESIGN.md 5.5 holds the table): on a room with furniture the dense objects finish in the first shell of cells and the sparse
+# walls in the second; smaller cells send the walls to a third shell, larger ones scan several times k candidates per query.
+# The cell never changes the result (include/omnipq_normals.h).
+KNN_CELL_FACTOR = 0.8
+
+
+def default_knn_cell(lo, hi, n, k):
+    """Cell edge for knn_query / estimate_normals from the bounding box corners `lo`, `hi` (3 host numbers each), the number
+    of points per scene and k.  Pure host arithmetic."""
+    w, l, h = (max(float(b) - float(a), 0.0) for a, b in zip(lo, hi))
+    area = 2.0 * (w * l + w * h + l * h)
+    cell = KNN_CELL_FACTOR * (k * area / (3.141592653589793 * max(int(n), 1))) ** 0.5
+    # a degenerate box (one point, a line): any positive edge is correct
+    return cell if cell > 0.0 and cell < float("inf") else 1.0
+
+
+def knn_query(new_xyz, xyz, k, cell):
+    """(B,M,3), (B,N,3) -> idx (B,M,k) i32, dist2 (B,M,k) f32: the k points with the smallest (d2, index), ascending; -1 / +inf
+    behind the N-th when N < k (include/omnipq_normals.h, stage 1).  cell: edge of the hash grid's cells, speed only."""
+    _check(new_xyz, "new_xyz", torch.float32)
+    _check(xyz, "xyz", torch.float32, cuda_like=new_xyz)
+    _need_gpu(new_xyz)
+    b, n = xyz.shape[0], xyz.shape[1]
+    m = new_xyz.shape[1]
+    idx = torch.empty((b, m, int(k)), device=new_xyz.device, dtype=torch.int32)
+    dist2 = torch.empty((b, m, int(k)), device=new_xyz.device, dtype=torch.float32)
+    ws = torch.empty((max(int(_lib0.omnipq_knn_workspace_bytes(b, n, m)), 16),), device=new_xyz.device, dtype=torch.uint8)
+    _run(_lib0.omnipq_knn, new_xyz, b, n, m, int(k), float(cell), _ptr(new_xyz), _ptr(xyz), _ptr(idx), _ptr(dist2), _ptr(ws))
+    return idx, dist2
+
+
+def estimate_normals(xyz, centre, k, iters, cell, out=None):
+    """(B,N,3) f32, centre (B,3) f64 -> (B,N,3) f32: k-NN, plane fit, `iters` smoothing steps, orientation away from `centre`
+    (include/omnipq_normals.h: omnipq_estimate_normals).  out: write into this contiguous (B,N,3) f32 tensor."""
+    _check(xyz, "xyz", torch.float32)
+    _need_gpu(xyz)
+    b, n = xyz.shape[0], xyz.shape[1]
+    if not (centre.dtype == torch.float64 and centre.is_contiguous() and tuple(centre.shape) == (b, 3) and
+            centre.device == xyz.device):
+        raise ValueError("estimate_normals: centre must be a contiguous (B, 3) float64 tensor on xyz's device")
+    if out is None:
+        out = torch.empty((b, n, 3), device=xyz.device, dtype=torch.float32)
+    elif not (out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (b, n, 3) and out.device == xyz.device):
+        raise ValueError("estimate_normals: out must be a contiguous (B, N, 3) float32 tensor on xyz's device")
+    nbytes = int(_lib0.omnipq_estimate_normals_workspace_bytes(b, n, int(k)))
+    if nbytes < 0:
+        raise ValueError(f"estimate_normals: k must be in [1, {KNN_MAX_K}] and B <= 65535")
+    ws = torch.empty((max(nbytes, 16),), device=xyz.device, dtype=torch.uint8)
+    _run(_lib0.omnipq_estimate_normals, xyz, b, n, int(k), int(iters), float(cell), _ptr(xyz), _ptr(centre), _ptr(out), _ptr(ws))
+    return out
+
+
 def group_points(points, idx):
     """(B,C,N), (B,M,S) i32 -> (B,C,M,S)   [group_points.cpp:19-42]"""
     _check(points, "points", torch.float32)

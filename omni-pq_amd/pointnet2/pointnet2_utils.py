@@ -8,6 +8,7 @@
     three_interpolate(features, idx, weight)      -> (B, C, n)              [:152-206]
     grouping_operation(features, idx)             -> (B, C, npoint, nsample)[:209-257]
     ball_query(radius, nsample, xyz, new_xyz)     -> (B, npoint, nsample) int32   [:260-291]
+    knn_query(k, xyz, new_xyz=None, cell=None)    -> (idx (B, M, k) int32, dist2)   (extension: include/omnipq_normals.h)
     QueryAndGroup(...), GroupAll(...)             nn.Modules               [:294-425]
 
 All heavy lifting happens in `pointnet2._ext` (HIP kernels for gfx950).  Outputs are fresh,
@@ -239,6 +240,22 @@ class BallQuery(Function):
 
 
 ball_query = BallQuery.apply
+
+
+def knn_query(k, xyz, new_xyz=None, cell=None):
+    """The k nearest points of xyz (B, N, 3) for every row of new_xyz (B, M, 3; None: xyz itself, each point then leads its
+    own row) -> (idx (B, M, k) int32, dist2 (B, M, k) float32), rows ascending in (d2, index); -1 / +inf behind the N-th
+    neighbour when N < k.  k <= 128.  cell: edge of the hash grid's cells (speed only); None derives it from the bounding
+    box, which reads six numbers back from the device -- pass a cell where no host read is wanted.  No gradient."""
+    xyz = xyz.detach().float().contiguous()
+    new_xyz = xyz if new_xyz is None else new_xyz.detach().float().contiguous()
+    if cell is None:
+        if xyz.shape[1] == 0:
+            cell = 1.0
+        else:
+            box = torch.stack([xyz.amin(dim=(0, 1)), xyz.amax(dim=(0, 1))]).cpu()
+            cell = _ext.default_knn_cell(box[0].tolist(), box[1].tolist(), xyz.shape[1], k)
+    return _ext.knn_query(new_xyz, xyz, int(k), float(cell))
 
 
 class QueryAndGroup(nn.Module):
