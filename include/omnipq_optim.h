@@ -189,6 +189,69 @@ int omnipq_adamw_scaled_finalize(int nchunks, const double *partials, const doub
                                  const double *scaler_cfg, struct omnipq_loss_scaler *scaler_state, float *result,
                                  float *coef, void *stream);
 
+/* The learning-rate schedule of the reference's utils/lr_scheduler.py: get_scheduler (GradualWarmupScheduler in front of
+ * CosineAnnealingLR or MultiStepLR, train.py:566 `scheduler.step()`) as one more scalar recurrence of the finalise launch.
+ * With e = sched_state[0], the number of scheduler.step() calls so far, W = warmup_iters and b = base_lr[g], in f64 and in this
+ * operation order (tests/lr_schedule_restatement.py is the same text in Python):
+ *     W > 0 and e <= W:   b / multiplier * ((multiplier - 1.) * e / W + 1.)          (at e == W this is not b for every b)
+ *     otherwise, k = e - W (k = e when W <= 0):
+ *       kind 0 (cosine):  eta_min + (b - eta_min) * (1 + cos(pi * k / t_max)) / 2
+ *       kind 1 (step):    b * gamma_pow[j],  j = the number of milestones <= k (bisect_right over the sorted milestones)
+ * gamma_pow[j] = gamma ** j is filled by the host, so the device needs no pow and the step schedule keeps the host's bits.
+ * The struct lives in DEVICE memory: a field changed there is seen by the next replay of a captured launch.  What a device
+ * struct holds cannot be checked from the host; a binding validates its host copy (kind 0 or 1, t_max >= 1, multiplier > 1,
+ * warmup_iters >= 0, 0 <= n_milestones <= omnipq_lr_schedule_max_milestones(), milestones sorted). */
+struct omnipq_lr_schedule {
+  int kind;                 /* 0 = cosine annealing, 1 = multi-step */
+  int n_milestones;         /* entries of `milestones` in use (kind 1) */
+  long long warmup_iters;   /* W; 0 = no warm-up */
+  long long t_max;          /* CosineAnnealingLR's T_max, in scheduler steps behind the warm-up */
+  double multiplier;        /* GradualWarmupScheduler's multiplier: the warm-up starts at b / multiplier */
+  double eta_min;           /* CosineAnnealingLR's eta_min */
+  long long milestones[8];  /* sorted, in scheduler steps behind the warm-up; duplicates count once each */
+  double gamma_pow[9];      /* gamma ** j for j = 0 .. 8 */
+};
+
+/* The layout of struct omnipq_lr_schedule as THIS build compiled it, one line in the format of omnipq_abi_records(), and the
+ * length of its `milestones` array.  The text and the static_asserts that hold it to the compiler's layout are written by
+ * omni-pq_amd/build.py from the definition above. */
+const char *omnipq_lr_schedule_record(void);
+int omnipq_lr_schedule_max_milestones(void);
+
+/* lr_now[g] = the schedule's value for e = sched_state[0] and base_lr[g], g < ngroups: one small launch.  For attach time and
+ * after a loaded state, so that lr_now always holds the device's own bits.  OMNIPQ_EINVAL, before anything is launched:
+ * ngroups < 1 or a null pointer. */
+int omnipq_lr_schedule_eval(int ngroups, const struct omnipq_lr_schedule *sched, const double *base_lr,
+                            const long long *sched_state, double *lr_now, void *stream);
+
+/* The superset of omnipq_adamw_scaled_finalize, one workgroup, the same kernel body: loss scaler (scaler_cfg and scaler_state:
+ * both NULL or both set), teacher (ema_state and ema_coef: both or neither), accumulation (accum) and schedule (sched, base_lr,
+ * sched_state and lr_now: all four or none) are each optional.  With a schedule the coefficient rows are formed with lr_now[g]
+ * in place of hyper[g][0]; then, on every APPLYING call and whether or not the norm is finite (train.py:566 does not look at
+ * the norm), sched_state[0] += 1 and lr_now is re-evaluated -- the value param_groups shows after scheduler.step().  A
+ * micro-batch that is not the applying one touches neither.  Thread 0 does all of it with ordinary stores.
+ * OMNIPQ_EINVAL, before anything is launched: an incomplete pair or quadruple, accum == NULL with accum_steps != 1, and
+ * everything the other finalise entry points refuse. */
+int omnipq_adamw_sched_finalize(int nchunks, const double *partials, const double *hyper, int ngroups, int accum_steps,
+                                long long *counters, long long *accum, long long *ema_state, float *ema_coef,
+                                const double *scaler_cfg, struct omnipq_loss_scaler *scaler_state,
+                                const struct omnipq_lr_schedule *sched, const double *base_lr, long long *sched_state,
+                                double *lr_now, float *result, float *coef, void *stream);
+
+/* Windowed statistics of the step's reported scalars (the reference's stat_dict loop, train.py:580-586: `stat_dict[key] +=
+ * end_points[key].item()` on the applying micro-batch), without a host read: one thread per entry, a grid of ceil(n / 256)
+ * workgroups, no atomics, capturable.
+ *   entries  n packed 16-byte records { const void *src; int32 kind (0 = f32, 1 = f64); int32 mode (0 = sum, 1 = last value) }
+ *            in device memory; src points at one device scalar.
+ *   sums     n doubles: mode 0: sums[i] += (double)*src -- the sequential f64 sum in call order, the bits of the reference's
+ *            Python-float `+=`; NaN and Inf propagate as there.  mode 1: sums[i] = (double)*src.
+ *   last     n doubles: last[i] = (double)*src, whatever the mode.
+ *   window   int64[2] = { steps accumulated, calls seen }, written by thread 0 of workgroup 0.
+ *   accum    the optimiser's { micro, apply } word or NULL.  Non-NULL with apply == 0: the call only increments `calls seen`.
+ * OMNIPQ_EINVAL, before anything is launched: n outside [1, 4096] or a null entries, sums, last or window. */
+int omnipq_stats_accumulate(int n, const void *entries, double *sums, double *last, long long *window,
+                            const long long *accum, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -211,7 +211,38 @@ def layout_checks(records):
     return "".join(s + "\n" for s in out)
 
 
-GENERATED = ("entry_points.inc", "abi_records.inc", "abi_layout_checks.inc")
+# plain (not typedef'd) structs whose record line and layout checks are generated as well: each reports its own line through
+# an entry point of its own (include/omnipq_optim.h: omnipq_lr_schedule_record) instead of through omnipq_abi_records()
+PLAIN_STRUCTS = ("omnipq_lr_schedule",)
+
+
+def plain_struct_record(name):
+    """`struct name field:t[*n] ...` of the headers' plain `struct name {...};`, in the letters of abi_records()."""
+    import re
+    inc = os.path.join(REPO, "include")
+    for header in sorted(f for f in os.listdir(inc) if f.endswith(".h")):
+        with open(os.path.join(inc, header)) as fh:
+            text = re.sub(r"/\*.*?\*/", " ", fh.read(), flags=re.S)
+        m = re.search(r"(?<!typedef)\s\bstruct\s+" + name + r"\s*\{([^{}]*)\}\s*;", text)
+        if m:
+            try:
+                return " ".join([f"struct {name}"] + list(_struct_fields(m.group(1), {})))
+            except ValueError as bad:
+                raise RuntimeError(f"{header}: {name}: field `{bad}` has no record letter") from None
+    raise RuntimeError(f"include/*.h define no `struct {name} {{...}};`")
+
+
+def plain_struct_text():
+    """Per struct of PLAIN_STRUCTS: its record line as the C string `<name>_record_text` and the static_asserts of
+    layout_checks() for it, for the translation unit that owns the struct's *_record() entry point."""
+    out = []
+    for name in PLAIN_STRUCTS:
+        line = plain_struct_record(name)
+        out.append(f'static const char {name}_record_text[] = "{line}";\n' + layout_checks(line + "\n"))
+    return "".join(out)
+
+
+GENERATED = ("entry_points.inc", "abi_records.inc", "abi_layout_checks.inc", "plain_struct_records.inc")
 
 
 def _c_string(text):
@@ -219,12 +250,13 @@ def _c_string(text):
 
 
 def _write_generated():
-    """build/generated/: the two texts above as C string literals and the layout checks, each rewritten only when its content
-    changes."""
+    """build/generated/: the two texts above as C string literals, the layout checks and the plain structs' records, each
+    rewritten only when its content changes."""
     gen = os.path.join(OBJDIR, "generated")
     os.makedirs(gen, exist_ok=True)
     records = abi_records()
-    for name, text in zip(GENERATED, (_c_string(entry_point_signatures()), _c_string(records), layout_checks(records))):
+    for name, text in zip(GENERATED, (_c_string(entry_point_signatures()), _c_string(records), layout_checks(records),
+                                     plain_struct_text())):
         path = os.path.join(gen, name)
         if not os.path.exists(path) or open(path).read() != text:
             with open(path, "w") as fh:

@@ -18,6 +18,10 @@
 // Dynamic loss scaling (torch.amp.GradScaler's two tensors and torch._amp_update_scale_) is one more scalar recurrence in the
 // finalise launch (kScaled): thread 0 divides the norm and the update's coefficient by the scale it reads from device memory
 // and, on an applying call, backs the scale off or grows it.  The two streaming launches do not know it exists.
+//
+// The learning-rate schedule (reference utils/lr_scheduler.py: get_scheduler; train.py:566) is the last scalar recurrence of the
+// step (kSched): thread 0 forms the coefficient rows with lr_now[g] instead of the staged rate and, on an applying call,
+// counts one scheduler step and re-evaluates lr_now for the next one.  omnipq_adamw_sched_finalize is the superset entry point.
 #include <math.h>
 #include <stddef.h>
 
@@ -179,11 +183,48 @@ __global__ __launch_bounds__(kAdamThreads) void adamw_grad_sqnorm_kernel(const A
   adamw_sqnorm_chunk<kAccum>(r.grad + base, sum, first, len, gs, partials + blockIdx.x);
 }
 
+// The schedule's value for scheduler step e and base rate b: include/omnipq_optim.h states the formulas and their operation
+// order (the library is built with -ffp-contract=off: every product and sum below rounds on its own, as in Python).
+__device__ __forceinline__ double lr_schedule_value(const omnipq_lr_schedule *__restrict__ s, long long e, double b) {
+  const long long w = s->warmup_iters;
+  long long k = e;
+  if (w > 0) {
+    if (e <= w) return b / s->multiplier * ((s->multiplier - 1.) * (double)e / (double)w + 1.);
+    k = e - w;
+  }
+  if (s->kind == 0) {
+    const double pi = 3.141592653589793;           // math.pi
+    return s->eta_min + (b - s->eta_min) * (1. + cos(pi * (double)k / (double)s->t_max)) / 2.;
+  }
+  int n = s->n_milestones;
+  n = n < 0 ? 0 : (n > 8 ? 8 : n);                 // whatever the device struct holds, the tables are not left
+  int j = 0;
+  while (j < n && s->milestones[j] <= k) ++j;      // bisect_right
+  return b * s->gamma_pow[j];
+}
+
+// an applying call's scheduler.step(): one more step counted, lr_now of the NEXT step (thread 0)
+__device__ __forceinline__ void lr_schedule_advance(const omnipq_lr_schedule *__restrict__ s, const double *__restrict__ base_lr,
+                                                    long long *__restrict__ state, double *__restrict__ lr_now, int ngroups) {
+  const long long e = state[0] + 1;
+  state[0] = e;
+  for (int g = 0; g < ngroups; ++g) lr_now[g] = lr_schedule_value(s, e, base_lr[g]);
+}
+
+__global__ __launch_bounds__(64) void lr_schedule_eval_kernel(int ngroups, const omnipq_lr_schedule *__restrict__ s,
+                                                              const double *__restrict__ base_lr,
+                                                              const long long *__restrict__ state,
+                                                              double *__restrict__ lr_now) {
+  const long long e = state[0];
+  for (int g = (int)threadIdx.x; g < ngroups; g += 64) lr_now[g] = lr_schedule_value(s, e, base_lr[g]);
+}
+
 // ema_state (kEma): int64[1] = the global_step the NEXT averaging uses; ema_coef: float[2] = { alpha, beta } for the update
 // scaler (kScaled): the dynamic loss scale S and its growth tracker; scaler_cfg: double[4] = { growth_factor, backoff_factor,
 // growth_interval, 0 }.  The gradients arrive as S * g: the norm and the update's coefficient are divided by the S read at
 // entry, and an applying call ends with the recurrence of torch._amp_update_scale_.
-template <bool kAccum, bool kEma, bool kScaled>
+// sched (kSched): the schedule, base_lr and lr_now: one double per group, sched_state: int64[1] = scheduler steps so far.
+template <bool kAccum, bool kEma, bool kScaled, bool kSched = false>
 __global__ __launch_bounds__(kAdamThreads) void adamw_finalize_kernel(int nchunks, const double *__restrict__ partials,
                                                                      const double *__restrict__ hyper, int ngroups,
                                                                      int accum_steps, long long *__restrict__ counters,
@@ -192,7 +233,11 @@ __global__ __launch_bounds__(kAdamThreads) void adamw_finalize_kernel(int nchunk
                                                                      const double *__restrict__ scaler_cfg,
                                                                      omnipq_loss_scaler *__restrict__ scaler,
                                                                      float *__restrict__ result, float *__restrict__ coef,
-                                                                     float *__restrict__ ema_coef) {
+                                                                     float *__restrict__ ema_coef,
+                                                                     const omnipq_lr_schedule *__restrict__ sched = nullptr,
+                                                                     const double *__restrict__ base_lr = nullptr,
+                                                                     long long *__restrict__ sched_state = nullptr,
+                                                                     double *__restrict__ lr_now = nullptr) {
   double acc = 0.0;
   for (int i = (int)threadIdx.x; i < nchunks; i += kAdamThreads) acc += partials[i];
   const double sum = block_sum_f64(acc);
@@ -255,13 +300,14 @@ __global__ __launch_bounds__(kAdamThreads) void adamw_finalize_kernel(int nchunk
   result[3] = gs * clip;
   if (!finite) {
     counters[1] += 1;
+    if (kSched) lr_schedule_advance(sched, base_lr, sched_state, lr_now, ngroups);      // train.py:566 does not look at the norm
     return;
   }
   const long long t = counters[0] + 1;
   counters[0] = t;
   for (int g = 0; g < ngroups; ++g) {
     const double *h = hyper + 8 * (size_t)g;
-    const double lr = h[0], beta1 = h[1], beta2 = h[2], eps = h[3], wd = h[4];
+    const double lr = kSched ? lr_now[g] : h[0], beta1 = h[1], beta2 = h[2], eps = h[3], wd = h[4];
     const double bc1 = 1.0 - pow(beta1, (double)t);
     const double bc2 = 1.0 - pow(beta2, (double)t);
     float *c = coef + 8 * (size_t)g;
@@ -274,6 +320,7 @@ __global__ __launch_bounds__(kAdamThreads) void adamw_finalize_kernel(int nchunk
     c[6] = (float)(1.0 / sqrt(bc2));
     c[7] = (float)eps;
   }
+  if (kSched) lr_schedule_advance(sched, base_lr, sched_state, lr_now, ngroups);
 }
 
 struct AdamCoef {
@@ -699,6 +746,81 @@ extern "C" int omnipq_adamw_scaled_finalize(int nchunks, const double *partials,
   else
     launch_scaled_finalize<false, false>(nchunks, partials, hyper, ngroups, 1, counters, nullptr, nullptr, nullptr,
                                          scaler_cfg, scaler_state, result, coef, st);
+  OMNIPQ_LAUNCH_CHECK();
+  return OMNIPQ_OK;
+}
+
+// ---- the learning-rate schedule: its record, its evaluation and the superset finalise -----------------------------------------
+
+// the record line and the static_asserts that hold it to the compiler's layout: written by omni-pq_amd/build.py from the header
+#include "plain_struct_records.inc"
+
+extern "C" const char *omnipq_lr_schedule_record(void) { return omnipq_lr_schedule_record_text; }
+
+extern "C" int omnipq_lr_schedule_max_milestones(void) {
+  static_assert(sizeof(((omnipq_lr_schedule *)0)->milestones) == 8 * sizeof(long long) &&
+                    sizeof(((omnipq_lr_schedule *)0)->gamma_pow) == 9 * sizeof(double),
+                "omnipq_lr_schedule: one power of gamma more than milestones");
+  return 8;
+}
+
+extern "C" int omnipq_lr_schedule_eval(int ngroups, const omnipq_lr_schedule *sched, const double *base_lr,
+                                       const long long *sched_state, double *lr_now, void *stream) {
+  if (ngroups < 1 || !sched || !base_lr || !sched_state || !lr_now) return OMNIPQ_EINVAL;
+  lr_schedule_eval_kernel<<<1, 64, 0, (hipStream_t)stream>>>(ngroups, sched, base_lr, sched_state, lr_now);
+  OMNIPQ_LAUNCH_CHECK();
+  return OMNIPQ_OK;
+}
+
+namespace {
+struct FinalizeArgs {
+  int nchunks;
+  const double *partials, *hyper;
+  int ngroups, accum_steps;
+  long long *counters, *accum, *ema_state;
+  float *ema_coef;
+  const double *scaler_cfg;
+  omnipq_loss_scaler *scaler_state;
+  const omnipq_lr_schedule *sched;
+  const double *base_lr;
+  long long *sched_state;
+  double *lr_now;
+  float *result, *coef;
+  hipStream_t stream;
+};
+
+// one template parameter per optional part, peeled off one at a time
+template <bool... kDone>
+static void launch_finalize(const FinalizeArgs &a, const bool *want) {
+  if constexpr (sizeof...(kDone) == 4) {
+    adamw_finalize_kernel<kDone...><<<1, kAdamThreads, 0, a.stream>>>(
+        a.nchunks, a.partials, a.hyper, a.ngroups, a.accum_steps, a.counters, a.accum, a.ema_state, a.scaler_cfg, a.scaler_state,
+        a.result, a.coef, a.ema_coef, a.sched, a.base_lr, a.sched_state, a.lr_now);
+  } else {
+    if (want[0])
+      launch_finalize<kDone..., true>(a, want + 1);
+    else
+      launch_finalize<kDone..., false>(a, want + 1);
+  }
+}
+}  // namespace
+
+extern "C" int omnipq_adamw_sched_finalize(int nchunks, const double *partials, const double *hyper, int ngroups,
+                                           int accum_steps, long long *counters, long long *accum, long long *ema_state,
+                                           float *ema_coef, const double *scaler_cfg, omnipq_loss_scaler *scaler_state,
+                                           const omnipq_lr_schedule *sched, const double *base_lr, long long *sched_state,
+                                           double *lr_now, float *result, float *coef, void *stream) {
+  if (nchunks < 0 || ngroups < 1 || accum_steps < 1) return OMNIPQ_EINVAL;
+  if (!hyper || !counters || !result || !coef || (nchunks > 0 && !partials)) return OMNIPQ_EINVAL;
+  if ((scaler_cfg == nullptr) != (scaler_state == nullptr)) return OMNIPQ_EINVAL;
+  if ((ema_state == nullptr) != (ema_coef == nullptr)) return OMNIPQ_EINVAL;
+  const int nsched = (sched != nullptr) + (base_lr != nullptr) + (sched_state != nullptr) + (lr_now != nullptr);
+  if (nsched != 0 && nsched != 4) return OMNIPQ_EINVAL;
+  if (!accum && accum_steps != 1) return OMNIPQ_EINVAL;
+  const FinalizeArgs a = {nchunks, partials, hyper, ngroups, accum ? accum_steps : 1, counters, accum, ema_state, ema_coef,
+                          scaler_cfg, scaler_state, sched, base_lr, sched_state, lr_now, result, coef, (hipStream_t)stream};
+  const bool want[4] = {accum != nullptr, ema_state != nullptr, scaler_state != nullptr, sched != nullptr};
+  launch_finalize<>(a, want);
   OMNIPQ_LAUNCH_CHECK();
   return OMNIPQ_OK;
 }

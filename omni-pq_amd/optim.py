@@ -40,6 +40,15 @@ squared-norm and update launches are unchanged -- and every applying call ends w
 torch._amp_update_scale_: a non-finite norm backs S off, `growth_interval` finite ones in a row grow it.  S is constant
 over an accumulation window.  A host-side GradScaler cannot do this inside a captured step: its step()/update() read
 found_inf on the host.  `scaler_state_dict()` / `load_scaler_state_dict()` speak GradScaler.state_dict()'s keys and types.
+
+The learning-rate schedule (the reference's utils/lr_scheduler.py: get_scheduler, stepped at train.py:566):
+`FusedAdamW(..., lr_schedule=LRSchedule(kind, n_iter_per_epoch, max_epoch, warmup_epoch, ...))`.  The groups' `lr` at
+construction are the base rates; the finalise launch (omnipq_adamw_sched_finalize, the superset of all the others) forms its
+coefficients from `lr_now` in device memory and every applying call counts one scheduler step and re-evaluates it -- warm-up,
+then cosine or multi-step, in float64 and the reference's operation order.  Nothing is staged per step (`staged` counts what
+sync_hyperparameters() sent), a captured launch follows the schedule by itself, and `LRSchedule.state_dict()` /
+`load_state_dict()` speak the reference's scheduler dicts.  Without `lr_schedule=` a host scheduler keeps working on
+`param_groups` as before.
 """
 import ctypes
 import math
@@ -111,6 +120,249 @@ class LossScaler:
                 f"backoff_factor={self.backoff_factor!r}, growth_interval={self.growth_interval!r})")
 
 
+class LRSchedule:
+    """The schedule the reference's utils/lr_scheduler.py: get_scheduler builds (GradualWarmupScheduler in front of
+    CosineAnnealingLR or MultiStepLR, stepped once per applying step: train.py:566), as a recurrence of the optimiser's finalise
+    launch: `FusedAdamW(..., lr_schedule=s)`.  The configuration is one struct omnipq_lr_schedule in DEVICE memory
+    (include/omnipq_optim.h states the formulas), next to the groups' base rates, the scheduler-step count `e` and `lr_now`, the
+    rates of the next step; every applying launch -- a replayed one too -- forms its coefficients from lr_now, counts e += 1
+    and re-evaluates lr_now.  Nothing is staged per step, and `scheduler.step()` has no place left in the loop: step() raises.
+
+    The arguments carry get_scheduler's names (from_args() reads them off the reference's `args`); any kind it does not build
+    raises its NotImplementedError.  `last_epoch` mirrors `e` on the host without a device read, like `optimizer.micro`.
+    state_dict() / load_state_dict() speak the reference's dicts: GradualWarmupScheduler's with its nested after_scheduler, or
+    torch's bare CosineAnnealingLR / MultiStepLR dict without a warm-up."""
+
+    KINDS = ("cosine", "step")
+
+    def __init__(self, kind, n_iter_per_epoch, max_epoch, warmup_epoch=-1, warmup_multiplier=100, lr_decay_epochs=(),
+                 lr_decay_rate=0.1, eta_min=1e-6):
+        if "cosine" in kind:
+            self.kind = "cosine"
+        elif "step" in kind:
+            self.kind = "step"
+        else:
+            raise NotImplementedError(f"scheduler {kind} not supported")
+        if isinstance(lr_decay_epochs, (int, np.integer)):
+            lr_decay_epochs = [lr_decay_epochs]
+        for name, v in (("n_iter_per_epoch", n_iter_per_epoch), ("max_epoch", max_epoch), ("warmup_epoch", warmup_epoch)):
+            if not _is_int(v):
+                raise ValueError(f"LRSchedule: {name} must be an integer, not {v!r}")
+        self.warmup_iters = int(warmup_epoch * n_iter_per_epoch) if warmup_epoch > 0 else 0
+        self.multiplier = warmup_multiplier
+        self.t_max = int((max_epoch - warmup_epoch) * n_iter_per_epoch)
+        self.eta_min = float(eta_min)
+        self.gamma = lr_decay_rate
+        self.milestones = sorted(int((m - warmup_epoch) * n_iter_per_epoch) for m in lr_decay_epochs) \
+            if self.kind == "step" else []
+        self.base_lrs = None
+        self.last_epoch = 0
+        self._opt = None
+        self.sched = self.base_lr = self.state = self.lr_now = None        # device memory, once attached to a GPU optimiser
+        self.validate()
+
+    @classmethod
+    def from_args(cls, args, n_iter_per_epoch):
+        """The names get_scheduler reads off `args`: lr_scheduler, max_epoch, warmup_epoch, and -- where it reads them --
+        warmup_multiplier (with a warm-up) and lr_decay_epochs / lr_decay_rate (step)."""
+        kw = {}
+        if "cosine" not in args.lr_scheduler and "step" in args.lr_scheduler:
+            kw.update(lr_decay_epochs=args.lr_decay_epochs, lr_decay_rate=args.lr_decay_rate)
+        if args.warmup_epoch > 0:
+            kw.update(warmup_multiplier=args.warmup_multiplier)
+        return cls(args.lr_scheduler, n_iter_per_epoch, args.max_epoch, args.warmup_epoch, **kw)
+
+    @staticmethod
+    def max_milestones():
+        return int(_ext()._lib0.omnipq_lr_schedule_max_milestones())
+
+    def validate(self):
+        """The host copy of the device struct: what the library cannot check once it is in device memory."""
+        if self.kind not in self.KINDS:
+            raise ValueError(f"LRSchedule: kind must be one of {self.KINDS}, not {self.kind!r}")
+        if not _is_int(self.t_max) or self.t_max < 1:
+            raise ValueError(f"LRSchedule: T_max = (max_epoch - warmup_epoch) * n_iter_per_epoch must be >= 1, not {self.t_max!r}")
+        if not _is_int(self.warmup_iters) or self.warmup_iters < 0:
+            raise ValueError(f"LRSchedule: warmup_iters must be an integer >= 0, not {self.warmup_iters!r}")
+        if self.warmup_iters > 0 and (not _is_real(self.multiplier) or not self.multiplier > 1.):
+            raise ValueError("multiplier should be greater than 1.")        # GradualWarmupScheduler's own words
+        if not _is_real(self.eta_min) or not math.isfinite(self.eta_min):
+            raise ValueError(f"LRSchedule: eta_min must be a finite number, not {self.eta_min!r}")
+        if not _is_real(self.gamma) or not math.isfinite(self.gamma):
+            raise ValueError(f"LRSchedule: lr_decay_rate must be a finite number, not {self.gamma!r}")
+        if list(self.milestones) != sorted(self.milestones) or not all(_is_int(m) for m in self.milestones):
+            raise ValueError(f"LRSchedule: milestones must be sorted integers, not {self.milestones!r}")
+        if len(self.milestones) > self.max_milestones():
+            raise ValueError(f"LRSchedule: {len(self.milestones)} milestones, the library's struct omnipq_lr_schedule holds "
+                             f"at most {self.max_milestones()}")
+
+    # ---- the formulas on the host (tests/lr_schedule_restatement.py is the contract) -----------------------------------------
+    def lr_at(self, e, b):
+        """the rate of base rate b after e scheduler steps, in float64 and the reference's operation order"""
+        w, k = self.warmup_iters, e
+        if w > 0:
+            if e <= w:
+                return b / self.multiplier * ((self.multiplier - 1.) * e / w + 1.)
+            k = e - w
+        if self.kind == "cosine":
+            return self.eta_min + (b - self.eta_min) * (1 + math.cos(math.pi * k / self.t_max)) / 2
+        return b * self.gamma ** sum(1 for m in self.milestones if m <= k)
+
+    # ---- the device side ---------------------------------------------------------------------------------------------------
+    def _struct(self):
+        rec = _ext().lr_schedule_struct()
+        s = rec()
+        nm = len(s.milestones)
+        if len(s.gamma_pow) != nm + 1 or nm != self.max_milestones():
+            raise RuntimeError("LRSchedule: the loaded library's struct omnipq_lr_schedule does not hold one power of gamma more "
+                               "than milestones")
+        s.kind, s.n_milestones = self.KINDS.index(self.kind), len(self.milestones)
+        s.warmup_iters, s.t_max = self.warmup_iters, self.t_max
+        s.multiplier, s.eta_min = float(self.multiplier), float(self.eta_min)
+        for j, m in enumerate(self.milestones):
+            s.milestones[j] = m
+        for j in range(nm + 1):
+            s.gamma_pow[j] = float(self.gamma ** j)          # Python's own pow: the step schedule keeps the host's bits
+        return s
+
+    def _attach(self, opt):
+        if self._opt is not None and self._opt is not opt:
+            raise ValueError("LRSchedule: already attached to another optimiser (its step count lives in that optimiser's launches)")
+        self._opt = opt
+        self.base_lrs = [float(g["lr"]) for g in opt.param_groups]
+        if opt.device.type != "cuda":
+            return
+        rec = _ext().lr_schedule_struct()
+        self.sched = torch.zeros(ctypes.sizeof(rec), dtype=torch.uint8, device=opt.device)
+        self.base_lr = torch.tensor(self.base_lrs, dtype=torch.float64, device=opt.device)
+        self.state = torch.full((1,), int(self.last_epoch), dtype=torch.int64, device=opt.device)
+        self.lr_now = torch.zeros(len(self.base_lrs), dtype=torch.float64, device=opt.device)
+        self.upload()
+
+    def upload(self):
+        """Validate the host copy, write it into the device struct and re-evaluate lr_now there (one small launch), all on the
+        current stream: a captured launch sees the change on its next replay."""
+        self.validate()
+        if self.sched is None:
+            return
+        raw = np.frombuffer(bytes(self._struct()), dtype=np.uint8).copy()
+        with torch.no_grad():
+            self.sched.copy_(torch.from_numpy(raw))
+        self._eval()
+
+    def _eval(self):
+        ext = _ext()
+        ext._run(ext._lib0.omnipq_lr_schedule_eval, self.lr_now, len(self.base_lrs), _ptr(self.sched), _ptr(self.base_lr),
+                 _ptr(self.state), _ptr(self.lr_now))
+
+    def field(self, name):
+        """A 0-dim (or 1-dim, for the two arrays) view of one field of the DEVICE struct: what is written through it is what the
+        next launch reads.  Nothing checks such a write; upload() is the checked way."""
+        if self.sched is None:
+            raise RuntimeError("LRSchedule.field: not attached to an optimiser on a GPU")
+        rec = _ext().lr_schedule_struct()
+        f = getattr(rec, name)
+        dtype = {"kind": torch.int32, "n_milestones": torch.int32, "multiplier": torch.float64, "eta_min": torch.float64,
+                 "gamma_pow": torch.float64}.get(name, torch.int64)
+        v = self.sched[f.offset:f.offset + f.size].view(dtype)
+        return v.reshape(()) if v.numel() == 1 else v
+
+    def _need_attached(self, what):
+        if self.base_lrs is None:
+            raise RuntimeError(f"LRSchedule.{what}: not attached yet -- the base rates are the groups' `lr` of "
+                               "FusedAdamW(..., lr_schedule=this)")
+
+    def get_last_lr(self):
+        """the rates the NEXT applying step uses, per group -- what param_groups shows after the reference's scheduler.step().
+        Reads lr_now back from the device (on an optimiser without a GPU: the same formulas on the host)."""
+        self._need_attached("get_last_lr")
+        if self.lr_now is not None:
+            return [float(x) for x in self.lr_now.cpu().tolist()]
+        return [self.lr_at(self.last_epoch, b) for b in self.base_lrs]
+
+    def set_last_epoch(self, e):
+        """Continue from scheduler step e (a resumed run): the device word, lr_now and the host mirror."""
+        if not _is_int(e) or e < 0:
+            raise ValueError(f"LRSchedule.set_last_epoch: an integer >= 0, not {e!r}")
+        self.last_epoch = int(e)
+        if self.state is not None:
+            with torch.no_grad():
+                self.state.fill_(int(e))
+            self._eval()
+
+    def step(self, epoch=None):
+        raise RuntimeError("LRSchedule.step: this schedule is stepped on the device, by every applying launch of the optimiser "
+                           "it is attached to (FusedAdamW(lr_schedule=...)) -- a host-side step would count twice")
+
+    # ---- the reference's dicts ---------------------------------------------------------------------------------------------
+    def _inner_config(self):
+        if self.kind == "cosine":
+            return {"T_max": self.t_max, "eta_min": self.eta_min}
+        from collections import Counter
+        return {"milestones": Counter(self.milestones), "gamma": self.gamma}
+
+    def state_dict(self):
+        """The keys and values the reference's scheduler holds after `last_epoch` steps of the same configuration:
+        GradualWarmupScheduler.state_dict() with its nested after_scheduler (a warm-up), torch's CosineAnnealingLR /
+        MultiStepLR state_dict() (none).  The outer `_last_lr` stays at the last warm-up value, as the reference leaves it."""
+        self._need_attached("state_dict")
+        e, w = self.last_epoch, self.warmup_iters
+        flags = {"_get_lr_called_within_step": False, "_is_initial": False}
+        now = self.get_last_lr()
+        if w == 0:
+            return dict(self._inner_config(), base_lrs=list(self.base_lrs), last_epoch=e, _step_count=e + 1, _last_lr=now, **flags)
+        k = max(e - w, 0)
+        inner = dict(self._inner_config(), base_lrs=list(self.base_lrs), last_epoch=k, _step_count=k + 1,
+                     _last_lr=now if k > 0 else list(self.base_lrs), **flags)
+        warm = min(e, w)
+        return dict(multiplier=self.multiplier, warmup_epoch=w, finished=False, base_lrs=list(self.base_lrs), last_epoch=e,
+                    _step_count=warm + 1, _last_lr=[self.lr_at(warm, b) for b in self.base_lrs], after_scheduler=inner, **flags)
+
+    def load_state_dict(self, state_dict):
+        """Take `last_epoch` from one of the reference's dicts after checking every configuration field it carries (T_max,
+        eta_min, milestones, gamma, multiplier, warmup_epoch, base_lrs) against this schedule's own; a mismatch raises and
+        changes nothing.  The dict is not modified."""
+        self._need_attached("load_state_dict")
+        from collections import Counter
+
+        def check(d, name, mine):
+            if name not in d:
+                return
+            theirs = d[name]
+            if name == "milestones":
+                theirs = sorted(Counter(theirs).elements()) if isinstance(theirs, dict) else sorted(theirs)
+                mine = list(self.milestones)
+            elif name == "base_lrs":
+                theirs = [float(x) for x in theirs]
+            if theirs != mine:
+                raise ValueError(f"LRSchedule.load_state_dict: the state was written with {name} = {d[name]!r}, this schedule "
+                                 f"has {mine!r}")
+
+        inner = state_dict.get("after_scheduler")
+        bare = state_dict if inner is None else inner
+        if (inner is not None) != (self.warmup_iters > 0):
+            raise ValueError("LRSchedule.load_state_dict: the state was written " +
+                             ("with" if inner is not None else "without") + " a warm-up, this schedule has " +
+                             (f"one of {self.warmup_iters} steps" if self.warmup_iters > 0 else "none"))
+        if ("T_max" in bare) != (self.kind == "cosine") or ("milestones" in bare) != (self.kind == "step"):
+            raise ValueError(f"LRSchedule.load_state_dict: the state is not that of a {self.kind} schedule")
+        for d in (state_dict, bare):
+            check(d, "base_lrs", list(self.base_lrs))
+        check(state_dict, "multiplier", self.multiplier)
+        check(state_dict, "warmup_epoch", self.warmup_iters)
+        check(bare, "T_max", self.t_max)
+        check(bare, "eta_min", self.eta_min)
+        check(bare, "milestones", None)
+        check(bare, "gamma", self.gamma)
+        e = state_dict["last_epoch"]
+        if not _is_int(e) or e < 0:
+            raise ValueError(f"LRSchedule.load_state_dict: last_epoch must be an integer >= 0, not {e!r}")
+        if inner is not None and "last_epoch" in inner and inner["last_epoch"] != max(e - self.warmup_iters, 0):
+            raise ValueError(f"LRSchedule.load_state_dict: after_scheduler.last_epoch = {inner['last_epoch']!r} does not follow "
+                             f"from last_epoch = {e} and warmup_epoch = {self.warmup_iters}")
+        self.set_last_epoch(e)
+
+
 class _Table:
     """The device tables of one (parameter, gradient) address set."""
     __slots__ = ("key", "shape_key", "records", "chunks", "partials", "nrec", "nchunks",
@@ -119,7 +371,7 @@ class _Table:
 
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
-                 max_norm=0.0, grad_scale=1.0, chunk_elems=CHUNK, accum_steps=1, loss_scaler=None):
+                 max_norm=0.0, grad_scale=1.0, chunk_elems=CHUNK, accum_steps=1, loss_scaler=None, lr_schedule=None):
         if amsgrad:
             raise NotImplementedError("FusedAdamW: amsgrad is not implemented (the reference does not use it)")
         if maximize:
@@ -136,6 +388,9 @@ class FusedAdamW(torch.optim.Optimizer):
             # the optimiser's own copy: growth_factor, backoff_factor and growth_interval may be changed on it
             loss_scaler = LossScaler(loss_scaler.init_scale, loss_scaler.growth_factor, loss_scaler.backoff_factor,
                                      loss_scaler.growth_interval)
+        if lr_schedule is not None and not isinstance(lr_schedule, LRSchedule):
+            raise ValueError("FusedAdamW: lr_schedule is an optim.LRSchedule or None (a torch scheduler steps from the host and "
+                             "writes param_groups; it keeps working without this argument)")
         # torch.optim.AdamW validates the values and knows which keys a param_group of THIS torch carries: its defaults are
         # taken over as they are, so that a state_dict of either optimiser has the other's param_groups keys
         probe = torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
@@ -202,6 +457,12 @@ class FusedAdamW(torch.optim.Optimizer):
         self._sent = None
         self._table_hit = None
         self.table_builds = 0
+        self.staged = 0                          # how often sync_hyperparameters() has sent rows to the device
+        # the learning-rate schedule on the device: the base rates are the groups' `lr` as they stand now; from here on
+        # param_groups[g]["lr"] IS the base rate and no launch reads it (the finalise launch reads lr_schedule.lr_now)
+        self.lr_schedule = lr_schedule
+        if lr_schedule is not None:
+            lr_schedule._attach(self)
         self.sync_hyperparameters()
 
     def add_param_group(self, param_group):
@@ -297,6 +558,8 @@ class FusedAdamW(torch.optim.Optimizer):
         """A captured launch() was replayed once: advance the host mirror as launch() itself does."""
         self._micro = (self._micro + 1) % self.accum_steps
         self._applied = self._micro == 0
+        if self._applied and self.lr_schedule is not None:
+            self.lr_schedule.last_epoch += 1     # the applying launch counted one scheduler step
 
     # ---- the mean teacher ------------------------------------------------------------------------------------------------------
     def attach_teacher(self, model, ema_model, decay, global_step=1):
@@ -373,7 +636,17 @@ class FusedAdamW(torch.optim.Optimizer):
         for s in state_dict["state"].values():
             if s.get("max_exp_avg_sq") is not None:
                 raise NotImplementedError("FusedAdamW.load_state_dict: the state was written with amsgrad=True")
+        if self.lr_schedule is not None:
+            # a state written under a host scheduler carries the rate of its step in `lr` and the base rate in `initial_lr`;
+            # here `lr` IS the base rate the device was given at construction, so a different base is refused, not staged
+            for i, (g, b) in enumerate(zip(state_dict["param_groups"], self.lr_schedule.base_lrs)):
+                if "initial_lr" in g and float(g["initial_lr"]) != b:
+                    raise ValueError(f"FusedAdamW.load_state_dict: group {i} was written with the base rate "
+                                     f"{g['initial_lr']!r}, the attached schedule has {b!r}")
         super().load_state_dict(state_dict)
+        if self.lr_schedule is not None:
+            for g, b in zip(self.param_groups, self.lr_schedule.base_lrs):
+                g["lr"] = b                  # the schedule owns the rate: LRSchedule.load_state_dict() restores its step
         for g in self.param_groups:
             if g.get("amsgrad") or g.get("maximize"):
                 raise NotImplementedError("FusedAdamW.load_state_dict: amsgrad / maximize are not implemented")
@@ -429,6 +702,7 @@ class FusedAdamW(torch.optim.Optimizer):
             self._stage_events[i] = ev
         self.staging = stage
         self._sent = rows
+        self.staged += 1
         return True
 
     # ---- the device table ----------------------------------------------------------------------------------------------------
@@ -554,7 +828,14 @@ class FusedAdamW(torch.optim.Optimizer):
                      self.chunk_elems, _ptr(self._hyper), ng, _ptr(tab.partials))
         # 2. finalise: with a loss scaler the superset entry point serves every family (accum / ema_state are None where the
         # family has none); without one, the entry point of the family, as before
-        if self.loss_scaler is not None:
+        if self.lr_schedule is not None:
+            # the superset of the superset: every part optional, the rates read from lr_schedule.lr_now and advanced there
+            sch, scaled = self.lr_schedule, self.loss_scaler is not None
+            ext._run(lib.omnipq_adamw_sched_finalize, self.result, tab.nchunks, _ptr(tab.partials), _ptr(self._hyper), ng,
+                     self.accum_steps, _ptr(self.counters), _ptr(self.accum), _ptr(self.ema_state), _ptr(self.ema_coef),
+                     _ptr(self._hyper[ng + 1] if scaled else None), _ptr(self.scaler_state), _ptr(sch.sched),
+                     _ptr(sch.base_lr), _ptr(sch.state), _ptr(sch.lr_now), _ptr(self.result), _ptr(self._coef))
+        elif self.loss_scaler is not None:
             ext._run(lib.omnipq_adamw_scaled_finalize, self.result, tab.nchunks, _ptr(tab.partials), _ptr(self._hyper), ng,
                      self.accum_steps, _ptr(self.counters), _ptr(self.accum), _ptr(self.ema_state), _ptr(self.ema_coef),
                      _ptr(self._hyper[ng + 1]), _ptr(self.scaler_state), _ptr(self.result), _ptr(self._coef))
@@ -581,7 +862,7 @@ class FusedAdamW(torch.optim.Optimizer):
         else:
             ext._run(lib.omnipq_adamw_update, self.result, tab.nrec, tab.nchunks, _ptr(tab.records), _ptr(tab.chunks),
                      self.chunk_elems, _ptr(self._coef), _ptr(self.result))
-        if accum:
+        if accum or self.lr_schedule is not None:
             self.replayed()
         else:
             self._applied = True
@@ -609,13 +890,15 @@ class FusedAdamW(torch.optim.Optimizer):
         return (self.exp_avg, self.exp_avg_sq, self.counters, self.result) + \
             ((self.scaler_state,) if self.loss_scaler is not None else ()) + \
             ((self.acc, self.accum) if self.accum_steps > 1 else ()) + \
+            ((self.lr_schedule.state, self.lr_schedule.lr_now) if self.lr_schedule is not None else ()) + \
             ((self.ema_state, self.ema_coef) + tuple(e for e, _ in self._teacher) if self._teacher is not None else ())
 
     def snapshot(self):
         """moments, counters and -- the warm-up and capture runs advance them too -- the accumulator, the device micro-batch
         counter and its host mirror; with a teacher attached its global_step, coefficients and weights as well; with a loss
-        scaler its scale and growth tracker"""
-        return [t.detach().clone() for t in self._saved_tensors()] + [(self._micro, self._applied)]
+        scaler its scale and growth tracker; with a learning-rate schedule its step count, lr_now and the host mirror"""
+        return [t.detach().clone() for t in self._saved_tensors()] + \
+            [(self._micro, self._applied, self.lr_schedule.last_epoch if self.lr_schedule is not None else None)]
 
     def restore(self, saved):
         tensors = self._saved_tensors()
@@ -624,4 +907,6 @@ class FusedAdamW(torch.optim.Optimizer):
         with torch.no_grad():
             for t, s in zip(tensors, saved):
                 t.copy_(s)
-        self._micro, self._applied = saved[-1]
+        self._micro, self._applied, e = saved[-1]
+        if self.lr_schedule is not None:
+            self.lr_schedule.last_epoch = e

@@ -119,6 +119,16 @@ def loss_scaler_struct():
 
 
 @functools.lru_cache(maxsize=None)
+def lr_schedule_struct():
+    """The `ctypes.Structure` of `struct omnipq_lr_schedule` (include/omnipq_optim.h: the learning-rate schedule in device
+    memory), from the record line the loaded library reports for it (omnipq_lr_schedule_record)."""
+    kind, name, *fields = _lib0.omnipq_lr_schedule_record().decode().split()
+    if (kind, name) != ("struct", "omnipq_lr_schedule"):
+        raise KeyError(f"pointnet2._ext: the loaded library ({_LIB_PATH}) reports `{kind} {name}` as its schedule record")
+    return _structure(name, fields)
+
+
+@functools.lru_cache(maxsize=None)
 def sa_infer_layer_struct():
     """The `ctypes.Structure` of `struct omnipq_sa_infer_layer` (include/omnipq_sa.h: the host record of one layer of
     omnipq_sa_infer), from the record line the loaded library reports for it (omnipq_sa_infer_layer_record)."""

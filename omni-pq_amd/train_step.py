@@ -14,7 +14,9 @@ become `loss = stepper.step(batch, labels, next_inputs=next_batch)`; `optimizer.
 it is and finds the gradients in `.grad` of the bare model's parameters, averaged over the ranks.  INTEGRATION.md shows
 the whole change.  The model is NOT wrapped in DistributedDataParallel: DDP reduces from per-parameter autograd hooks,
 which a captured step with deferred weight gradients never fires (`deferred_wgrads` refuses DDP parameters).  With `CapturedStep(..., optimizer=optim.FusedAdamW(...))` the clip and the AdamW step of train.py:562-563 run inside
-the captured step as well (three launches at its end, hyper-parameters in device memory) and only `scheduler.step()` stays.
+the captured step as well (three launches at its end, hyper-parameters in device memory) and only `scheduler.step()` stays --
+unless the optimizer carries `lr_schedule=optim.LRSchedule(...)`, which its finalise launch steps on the device; with
+`stats=` the reference's per-step `.item()` loop (train.py:580-586) becomes one more launch and one read per print_freq steps.
 
 Launched kernel by kernel (`graph=False`, or under DDP) the same step is host-bound (about 2.3x slower at batch 8 x
 40 000 points on MI355X); the capture is what makes the 650 dependent launches of 3-150 us run back to back.
@@ -115,17 +117,27 @@ class CapturedStep:
                      empty gradients, the SUM lives in the optimizer's accumulator.  Every step() is then one micro-batch and
                      one replay of the same graph: the micro-batch counter is a device word the captured launches read.
                      `stepper.is_update_step` (a host bool, valid once step() has returned) says whether that call
-                     applied the sum: call scheduler.step() and update_teacher() only then.  The gradients are summed, as
-                     in the reference (grad_scale = 1 / k for the mean).  With `buckets` every micro-batch's gradients are
+                     applied the sum: call scheduler.step() and update_teacher() only then (an optimizer built with
+                     lr_schedule=optim.LRSchedule(...) steps its schedule on the device, on those calls by itself).  The
+                     gradients are summed, as in the reference (grad_scale = 1 / k for the mean).  With `buckets` every
+                     micro-batch's gradients are
                      all-reduced before they are accumulated: the same sum, k times the communication (an all-reduce
                      deferred to the k-th micro-batch is not implemented).  A host-stepped optimizer accumulates outside:
                      step_freq stays 1, the caller adds `.grad` up after each step().
+    stats            None, or a callable returning the mapping of device scalars the step reports once the criterion has run
+                     (`lambda: objective.stats`, or a selection of stepper.end_points): the reference's stat_dict loop
+                     (train.py:578-586) as ONE launch at the end of the step body, behind the optimizer's (it reads their
+                     apply mark and the norm), captured with it.  `stepper.stats` is the step_stats.StepStats: keys are
+                     chosen by train.py:581's rule, `grad_norm` joins with an in-graph optimizer, only applying steps are
+                     accumulated, and `stepper.stats.read()` every print_freq steps is the loop's one host read.  The launch
+                     is on the main stream: lookahead=2 and buckets= need nothing special.  graph=False runs it eagerly.
     """
 
     def __init__(self, net, criterion, example_inputs, example_labels=None, *, model=None, amp_dtype=torch.bfloat16,
                  loss_scale=1.0, graph=True, prefetch="forward", fps_footprint=None, teacher=None, teacher_example=None,
                  ema=None, buckets=None, defer=True, warmup=3, distributed=False, before_capture=None,
-                 teacher_to_criterion=False, lookahead=1, head_rounds=None, optimizer=None, step_freq=1, ema_in_step=False):
+                 teacher_to_criterion=False, lookahead=1, head_rounds=None, optimizer=None, step_freq=1, ema_in_step=False,
+                 stats=None):
         if optimizer is not None:
             import optim
             if not isinstance(optimizer, optim.FusedAdamW):
@@ -158,6 +170,14 @@ class CapturedStep:
                 optimizer.grad_scale = 1.0 / float(loss_scale)
         self.optimizer = optimizer
         self.grad_total_norm = optimizer.grad_total_norm if optimizer is not None else None
+        if stats is not None and not callable(stats):
+            raise TypeError("CapturedStep(stats=...): a callable returning the mapping of the step's device scalars (for "
+                            "instance `lambda: objective.stats`) or None")
+        self._stats_source = stats
+        self.stats = None
+        if stats is not None:
+            import step_stats
+            self.stats = step_stats.StepStats()
         if lookahead not in (1, 2):
             raise ValueError("CapturedStep: lookahead is 1 or 2")
         if lookahead == 2 and prefetch != "forward":
@@ -296,6 +316,9 @@ class CapturedStep:
             if not self._capturing:
                 self.optimizer.sync_hyperparameters()
             self.optimizer.launch()
+        if self.stats is not None:
+            # behind the optimiser's launches on this stream: it reads their apply mark and the norm
+            self.stats.accumulate(self._stats_source(), self.optimizer)
         if not self._capturing:
             for m in heads:
                 m.hand_over_head()                   # (this stream waits for the head; the host does not)
@@ -384,6 +407,9 @@ class CapturedStep:
             if self.optimizer is not None:
                 self.optimizer.retarget()            # the table the captured launches read: the capture's own gradient tensors
                 self.optimizer.restore(opt_saved)
+            if self.stats is not None:
+                self.stats.retarget()                # ... and the statistics' table at the capture's own scalars
+                self.stats.reset()                   # the warm-up steps are in no window
             self._forget_plans()
             with torch.no_grad():
                 for b, saved in keep:
