@@ -5,7 +5,9 @@
  * (utils/nms.py:77-113 `nms_3d_faster` on the boxes' axis-aligned extents) and hand Python lists to QUADAPCalculator.
  * There every proposal is a Python iteration with ~10 `.detach().cpu().numpy()` reads (B x 256 of them per head and
  * batch); here one launch decodes all proposals of the batch and one launch runs the greedy suppression of every scene,
- * and the host reads the results back once.
+ * and the host reads the results back once.  The packed detections (omnipq_decode_boxes .. omnipq_pack_quads) leave the same
+ * results on the device, and omnipq_layout_f1 scores the packed quads there: QUADAPCalculator.compute_F1 (:695-736), the number
+ * an evaluation epoch returns, as five integers read once per epoch.
  * Conventions as in omnipq_pointops.h: device pointers, sizes, a hipStream_t, int return (0 = ok).
  */
 #ifndef OMNIPQ_EVAL_H
@@ -116,6 +118,38 @@ int omnipq_pack_boxes(int b, int k, int ncls, const unsigned char *keep, const f
 int omnipq_pack_quads(int b, int k, const unsigned char *keep, const float *prob, float conf, float quad_thres,
                       const double *corners8, const float *verts4, int *count, int *index, float *out_score,
                       double *out_corners8, int *count_f1, int *index_f1, float *out_verts4, void *stream);
+
+/* ---- layout F1 (csrc/layout_f1.hip) ------------------------------------------------------------------------
+ * The counts of models/ap_helper_pq.py:695-736 `QUADAPCalculator.compute_F1` for a batch, one workgroup per scene, on the F1
+ * list omnipq_pack_quads wrote.  The rule is the reference's as it stands:
+ *   ground-truth list of scene s   rows j in [0, g) of gt_verts4[s] with j < num_total[s, min(j, num_total_cols - 1)], in
+ *                                  increasing j (parse_quad_groundtruths with num_total_quads); npos = its length
+ *   two corners are the same       sqrt((dx dx + dy dy) + dz dz) <= same_thres, both corners widened from f32 to f64, every
+ *                                  product and sum rounded on its own; a NaN never passes
+ *   a predicted quad is correct    when some quad G of the list has all four dist(P[i], G[i]) or all four dist(P[i], G[i ^ 1])
+ *                                  (the order [1, 0, 3, 2]) within same_thres: tp_wall += 1, otherwise fp += 1; an empty list
+ *                                  makes every quad a false positive
+ *   ceiling and floor              get_ceiling_and_floor (:673-693) appends one entry per visited corner in BOTH branches, so
+ *                                  its `len(...) == 4` test holds exactly when the scene has two predicted quads.  Only then:
+ *                                  the ceiling list is corners 0, 1 of quad 0 and then of quad 1, the floor list corners 2, 3;
+ *                                  a corner is appended as it is when no earlier entry of its list is within same_thres, and
+ *                                  otherwise as the f32 midpoint (p + corner) / 2 with the FIRST such entry p; each list is
+ *                                  scored as a quad against ALL h rows of horizontal[s] -- the zero padding rows included, as
+ *                                  on the host -- and adds 1 to tp_horizontal when correct, never to fp
+ * verts4 (b, k, 4, 3) f32: rows [0, count_f1[s]) are read, count_f1 (b) i32 clamped to [0, k]; gt_verts4 (b, g, 4, 3) f32;
+ * num_total (b, num_total_cols) i64; horizontal (b, h, 4, 3) f32, h may be 0.
+ *   per_scene (b, 4) i32   written: [tp_wall, fp, npos, tp_horizontal]
+ *   acc       (5)    i64   incremented by the batch's four sums and by b scans: integer atomics, so the result does not
+ *                          depend on their order
+ * Either output may be NULL, not both.  k <= 4096, g <= omnipq_layout_f1_max_gt(), h <= 8, num_total_cols >= 1, same_thres
+ * finite and >= 0; anything else, or a missing pointer of a non-empty array, is OMNIPQ_EINVAL before the device is touched.
+ * b == 0 launches nothing.  The F1 itself stays a host expression over the five integers (ap_helper_pq.LayoutF1). */
+int omnipq_layout_f1(int b, int k, const int *count_f1, const float *verts4, int g, const float *gt_verts4,
+                     const long long *num_total, int num_total_cols, int h, const float *horizontal, double same_thres,
+                     int *per_scene, long long *acc, void *stream);
+
+/* The largest g omnipq_layout_f1 accepts (host only). */
+int omnipq_layout_f1_max_gt(void);
 
 #ifdef __cplusplus
 }

@@ -44,9 +44,11 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 # point_normals.hip: the neighbour order is decided by the f32 d2 of the numerics contract (its one fused step is spelled
 # out, csrc/common.h: sumsq3) and the sign decisions of the smoothing and orientation by f64 sums stated term by term
 # (include/omnipq_normals.h); the same reason again.
+# layout_f1.hip: a corner distance is three f64 products and two sums as numpy forms them, compared with a threshold; the same
+# reason once more.
 EXTRA = {"fps.hip": ["-fno-slp-vectorize"], "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
          "eval_iou.hip": ["-ffp-contract=off"], "detect.hip": ["-ffp-contract=off"],
-         "point_normals.hip": ["-ffp-contract=off"]}
+         "point_normals.hip": ["-ffp-contract=off"], "layout_f1.hip": ["-ffp-contract=off"]}
 
 
 def hipcc():

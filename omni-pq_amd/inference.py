@@ -18,13 +18,19 @@ ap_helper_pq.detect_predictions / detect_quad_predictions with `out=`: no host r
 The thresholds and modes of `config_dict` are launch ARGUMENTS of the captured kernels and so are fixed at capture: a changed
 config needs a new runner, and `run` raises when it finds the dict's scalars (or the dataset config's class counts and mean
 sizes) changed.  One rank only: multi-GPU evaluation is independent runners.
+
+    scorer = evaluate_layout_f1(runner, batches)              # batches: dicts of point_clouds and the quad labels, on the device
+    f1 = scorer.f1(calculated=True)                           # the first host read of the pass: five integers
+
+is the evaluation pass that ends in the layout F1: every batch is run with `to_host=False` and its quad record is
+scored on the device (ap_helper_pq.LayoutF1), so no record is copied and no Python list is built.
 """
 import gc
 
 import numpy as np
 import torch
 
-from train_step import _cloud
+from train_step import _cloud, lookahead
 
 
 def _config_snapshot(config_dict):
@@ -146,14 +152,15 @@ class CapturedInference:
             raise RuntimeError("CapturedInference.run: config_dict changed since the runner was built; its thresholds and "
                                "modes are launch arguments fixed at capture -- build a new runner for a new config")
 
-    def run(self, inputs=None, next_inputs=None):
+    def run(self, inputs=None, next_inputs=None, to_host=True):
         """Detections of `inputs`.  next_inputs: the batch the NEXT call will run (tensor / dict / callable(dst) filling the
         static buffer): its sampling runs underneath this forward.  inputs=None, or the very object announced as
         `next_inputs` by the previous call: the announced batch is taken as is; any other input is copied in and, with
-        prefetch="forward", sampled in front of the replay."""
+        prefetch="forward", sampled in front of the replay.  to_host=False: the records' to_host() copies are not queued
+        (their pinned twins keep what the last copy left): for a consumer that stays on the device (evaluate_layout_f1)."""
         self._check()
         if self.graph is None:
-            return self._finish(self._eager(inputs, next_inputs))
+            return self._finish(self._eager(inputs, next_inputs), to_host)
         net = self.net
         pc = None if inputs is None else _cloud(inputs)
         announced = self._have_next and (pc is None or (self._promised is not None and self._promised[0] is pc
@@ -182,7 +189,7 @@ class CapturedInference:
         self.graph.replay()
         self.replays += 1
         net.forget_prefetch()            # the replayed graph owns the sampling chain; no later eager forward may take its plan
-        return self._finish(self.records)
+        return self._finish(self.records, to_host)
 
     def forget_next(self):
         """Call after anything else ran a forward of `net` (another runner, a plain evaluation pass): that forward reused the
@@ -200,9 +207,28 @@ class CapturedInference:
         return self._body(_cloud(inputs), nxt, False)
 
     @staticmethod
-    def _finish(records):
+    def _finish(records, to_host=True):
+        if not to_host:
+            return records
         for boxes, quads in records.values():
             for det in (boxes, quads):
                 if det is not None:
                     det.to_host()                # eagerly, behind the replay on the same stream: no memcpy node in the graph
         return records
+
+
+def evaluate_layout_f1(runner, batches, prefix="last_"):
+    """The layout F1 of an evaluation pass without a host read per batch: -> ap_helper_pq.LayoutF1.
+
+    batches: an iterable of dicts holding `point_clouds` and the quad labels on the device (gt_quad_centers,
+    gt_normal_vectors, gt_quad_sizes, num_total_quads, horizontal_quads -- what device_data.DeviceLoader assembles).  Every
+    batch is run with the following one announced and to_host=False, and its quad record of `prefix` is scored where it is
+    (LayoutF1.step: two launches).  Nothing is read until the caller asks the returned scorer: .read() / .f1(calculated)."""
+    import ap_helper_pq
+    if not runner.quads or prefix not in runner.prefixes:
+        raise ValueError(f"evaluate_layout_f1: the runner packs no quad record for prefix {prefix!r}")
+    scorer = ap_helper_pq.LayoutF1(runner.cur.device)
+    for batch, nxt in lookahead(batches):
+        quads = runner.run(batch, next_inputs=nxt, to_host=False)[prefix][1]
+        scorer.step(quads, batch)
+    return scorer

@@ -12,7 +12,10 @@ The reference decodes every proposal in a Python loop with about ten `.detach().
 prediction head and batch, twice: a numpy and a tensor variant) and runs the suppression in numpy.  Here one launch decodes
 all proposals (omnipq_parse_quads), one launch suppresses per scene (omnipq_nms3d), and the results come back in ONE
 device-to-host copy; only the ragged Python lists the calculators consume are assembled on the host, as they must be.
-QUADAPCalculator itself is host bookkeeping in the reference too (lists of 4 x 3 corner arrays per scan) and stays so.
+QUADAPCalculator keeps the reference's host bookkeeping (lists of 4 x 3 corner arrays per scan) as its default route; its F1,
+the number an evaluation epoch returns, can also be counted on the device (csrc/layout_f1.hip): LayoutF1 scores a
+quad record against the batch's labels where both already are and is read once per epoch, and QUADAPCalculator(f1="device")
+sends the accumulated lists through the same kernel.
 There is no CPU path for the parsing: CPU tensors are refused (oracle/ap_oracle.py is the tests' CPU twin).
 Both calculators take `iou="device"` (default "host", the reference's route): compute_metrics then gets the box overlaps from
 csrc/eval_iou.hip through eval_det.eval_det_device, and compute_metrics_at(calculator, thresholds) scores several IoU thresholds
@@ -507,6 +510,121 @@ def detect_quad_predictions(end_points, config_dict, prefix="", out=None):
     return det
 
 
+# -------------------------------------------------------------------------------------------------- layout F1 on the device
+MAX_F1_GT = int(_lib.omnipq_layout_f1_max_gt())                         # g: the library's own limit
+MAX_F1_HORIZONTAL = 8                                                   # h (include/omnipq_eval.h)
+F1_KEYS = ("tp_wall", "fp", "npos", "tp_horizontal", "scans")
+
+
+def f1_from_counts(counts, calculated=False):
+    """compute_F1's closing expression in Python floats over the integer counts {tp_wall, fp, npos, tp_horizontal}: equal
+    counts give bit-equal F1, and npos == 0 raises ZeroDivisionError as the host route does."""
+    tp = counts["tp_wall"] + (counts["tp_horizontal"] if calculated else 0)
+    fp = counts["fp"]
+    p = tp / max((tp + fp), 1e-6)
+    r = tp / counts["npos"]
+    return 2.0 * p * r / max((p + r), 1e-6)
+
+
+def _as(t, dtype, shape, keep, name):
+    """`t` itself when it already is a contiguous `dtype` tensor of `shape`, otherwise a copy in the staging buffer keep[name]
+    (made once per shape): no allocation from the second call on either way"""
+    t = t.detach()
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"ap_helper_pq: `{name}` must be of shape {tuple(shape)}, not {tuple(t.shape)}")
+    if t.dtype == dtype and t.is_contiguous():
+        return t
+    buf = keep.get(name)
+    if buf is None or tuple(buf.shape) != tuple(shape) or buf.device != t.device:
+        buf = keep[name] = torch.empty(tuple(shape), device=t.device, dtype=dtype)
+    buf.copy_(t)
+    return buf
+
+
+class LayoutF1(object):
+    """The layout F1 of an evaluation run, counted on the device (csrc/layout_f1.hip).
+
+        scorer = LayoutF1(device)
+        for every batch:   scorer.step(quad_detections, labels)     # two launches, no host read; can be captured
+        scorer.f1(), scorer.f1(calculated=True)                     # one copy of five integers each (or read() once)
+
+    acc: int64 (5) device tensor [tp_wall, fp, npos, tp_horizontal, scans], incremented by every step with integer atomics.
+    It is a plain tensor: a multi-rank evaluation all-reduces it before reading (the caller's job).  One accumulator serves
+    both values of `calculated`."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("ap_helper_pq: LayoutF1 counts on the GPU (the HIP path has no CPU fallback)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.acc = torch.zeros((5,), device=self.device, dtype=torch.int64)
+        self._keep = {}
+
+    def step(self, det, end_points):
+        """Adds one batch.  det: the quad Detections of detect_quad_predictions; end_points: the batch's labels ON THE DEVICE,
+        as the data loader shapes them -- gt_quad_centers (B, >=g, >=3), gt_normal_vectors (B, >=g, 3), gt_quad_sizes
+        (B, >=g, 2), num_total_quads (B, cols) or (B,), horizontal_quads (B, h, 4, 3), g = min(rows, MAX_NUM_QUAD).  The
+        ground-truth corners come from omnipq_parse_quads (verts4 alone) into a buffer this object keeps; then one
+        omnipq_layout_f1 launch.  float32 / int64 contiguous labels are used where they are, others are first copied into
+        buffers kept here; from the second call on nothing is allocated."""
+        if not isinstance(det, Detections) or det.kind != "quads":
+            raise ValueError("ap_helper_pq: LayoutF1.step takes the quad record of detect_quad_predictions")
+        B, K, keep = det.B, det.K, self._keep
+        for name in ("gt_quad_centers", "gt_normal_vectors", "gt_quad_sizes", "num_total_quads", "horizontal_quads"):
+            t = end_points[name]
+            if not torch.is_tensor(t) or t.device != self.device:
+                raise RuntimeError(f"ap_helper_pq: `{name}` must be a tensor on {self.device} (LayoutF1 reads nothing from the host)")
+        if det.record.device != self.device:
+            raise RuntimeError(f"ap_helper_pq: the record is not on {self.device}")
+        g = min(int(end_points["gt_quad_centers"].shape[1]), MAX_NUM_QUAD)
+        c = _as(end_points["gt_quad_centers"][:, :g, 0:3], _F32, (B, g, 3), keep, "gt_quad_centers")
+        n = _as(end_points["gt_normal_vectors"][:, :g], _F32, (B, g, 3), keep, "gt_normal_vectors")
+        s = _as(end_points["gt_quad_sizes"][:, :g], _F32, (B, g, 2), keep, "gt_quad_sizes")
+        total = end_points["num_total_quads"].reshape(B, -1)
+        cols = int(total.shape[1])
+        total = _as(total, torch.int64, (B, cols), keep, "num_total_quads")
+        hz = end_points["horizontal_quads"]
+        h = int(hz.shape[1]) if hz.dim() == 4 else -1
+        if h < 0 or h > MAX_F1_HORIZONTAL:
+            raise ValueError(f"ap_helper_pq: horizontal_quads must be (B, h, 4, 3) with h <= {MAX_F1_HORIZONTAL}")
+        hz = _as(hz, _F32, (B, h, 4, 3), keep, "horizontal_quads")
+        gt = keep.get("gt_verts4")
+        if gt is None or tuple(gt.shape) != (B, g, 4, 3):
+            gt = keep["gt_verts4"] = torch.empty((B, g, 4, 3), device=self.device, dtype=_F32)
+        null = ctypes.c_void_p(0)
+        _ext._run(_lib.omnipq_parse_quads, c, B, g, _ext._ptr(c), _ext._ptr(n), _ext._ptr(s), null, LENGTH, null, null,
+                  _ext._ptr(gt), null)
+        _ext._run(_lib.omnipq_layout_f1, c, B, K, _ext._ptr(det.count_f1), _ext._ptr(det.verts4), g, _ext._ptr(gt),
+                  _ext._ptr(total), cols, h, _ext._ptr(hz) if h else null, SAME_THRES, null, _ext._ptr(self.acc))
+        return self
+
+    def read(self):
+        """{tp_wall, fp, npos, tp_horizontal, scans} as Python ints: ONE device-to-host copy (it waits for the steps queued
+        before it on the current stream)."""
+        return dict(zip(F1_KEYS, (int(v) for v in self.acc.cpu().tolist())))
+
+    def f1(self, calculated=False):
+        """QUADAPCalculator.compute_F1(calculated) of the scans added so far"""
+        return f1_from_counts(self.read(), calculated)
+
+    def reset(self):
+        self.acc.zero_()
+
+
+def _exact_f32(a, name):
+    """a as float32, refused when that would round a corner (the device scores f32 corners; the host route would score the
+    wider ones, and the two could then disagree)"""
+    a = np.asarray(a)
+    if a.dtype == np.float32:
+        return a
+    a32 = a.astype(np.float32)
+    if not np.array_equal(a32.astype(np.float64), a.astype(np.float64), equal_nan=True):
+        raise ValueError(f"ap_helper_pq: {name} are not exactly representable in float32; f1='device' scores float32 "
+                         "corners and does not round -- use f1='host' for these lists")
+    return a32
+
+
 class APCalculator(object):
     ''' Calculating Average Precision '''
 
@@ -587,17 +705,22 @@ def _metrics_dict(rec, ap, class2type_map):
 class QUADAPCalculator(object):
     ''' Average precision and F1 of the predicted layout quads, accumulated over the scans of an evaluation run '''
 
-    def __init__(self, ap_iou_thresh=0.25, class2type_map=None, logger=None, logger_i=None, iou="host"):
+    def __init__(self, ap_iou_thresh=0.25, class2type_map=None, logger=None, logger_i=None, iou="host", f1="host"):
         """
         Args:
             ap_iou_thresh: float between 0 and 1.0
                 IoU threshold to judge whether a prediction is positive.
             class2type_map: [optional] dict {class_int:class_name}
             iou: "host" (the default) or "device", as for APCalculator
+            f1: "host" (the default) or "device": compute_F1 counts the accumulated lists with one launch of
+                omnipq_layout_f1 (csrc/layout_f1.hip) instead of walking them in Python
         """
         self.ap_iou_thresh = ap_iou_thresh
         self.class2type_map = class2type_map
         self.iou = _iou_route(iou)
+        if f1 not in ("host", "device"):
+            raise ValueError(f"ap_helper_pq: f1 must be 'host' or 'device', not {f1!r}")
+        self.f1 = f1
         self.logger = logger
         self.I = logger_i
         self.reset()
@@ -664,7 +787,11 @@ class QUADAPCalculator(object):
 
     def compute_F1(self, calculated=False, is_ema=False):
         """F1 of the accumulated quads; with `calculated` the ceiling and the floor deduced from the predicted walls are
-        scored against the scan's horizontal ground-truth quads (true positives only, as in the reference)."""
+        scored against the scan's horizontal ground-truth quads (true positives only, as in the reference).
+        get_ceiling_and_floor appends one entry per visited corner in both of its branches, so the `len(...) == 4` tests
+        below hold exactly when the scan has two predicted quads."""
+        if self.f1 == "device":
+            return f1_from_counts(self.f1_counts_device(), calculated)
         tp = fp = 0
         npos = sum(len(self.gt_corners[i]) for i in range(self.scan_cnt))
         for i in range(self.scan_cnt):
@@ -686,3 +813,49 @@ class QUADAPCalculator(object):
         p = tp / max((tp + fp), 1e-6)
         r = tp / npos
         return 2.0 * p * r / max((p + r), 1e-6)
+
+    def f1_counts_device(self, device=None):
+        """{tp_wall, fp, npos, tp_horizontal, scans} of the accumulated lists from ONE omnipq_layout_f1 launch: the lists are
+        padded into arrays with b = scan_cnt and num_total_cols = 1 (a scan's ground-truth list is already cut, so its count
+        is its length), the per-scene rows come back in one copy and are summed here.  Refuses (ValueError) corners that are
+        not exactly float32 -- they are not rounded -- lists of more than MAX_PROPOSALS quads, more than MAX_F1_GT
+        ground-truth quads and scans whose `horizontal` differ in their row count or exceed MAX_F1_HORIZONTAL rows."""
+        b = self.scan_cnt
+        counts = dict.fromkeys(F1_KEYS, 0)
+        if b == 0:
+            return counts
+        k = max(max(len(self.pred_corners[i]) for i in range(b)), 1)
+        g = max(max(len(self.gt_corners[i]) for i in range(b)), 1)
+        if k > MAX_PROPOSALS:
+            raise ValueError(f"ap_helper_pq: f1='device' takes at most {MAX_PROPOSALS} predicted quads per scan (got {k})")
+        if g > MAX_F1_GT:
+            raise ValueError(f"ap_helper_pq: f1='device' takes at most {MAX_F1_GT} ground-truth quads per scan (got {g})")
+        hz = []
+        for i in range(b):
+            one = self.horizontal_corners[i]
+            one = one.detach().cpu().numpy() if torch.is_tensor(one) else np.asarray(one)
+            hz.append(_exact_f32(one, "horizontal quads").reshape(-1, 4, 3))
+        h = hz[0].shape[0]
+        if any(x.shape[0] != h for x in hz) or h > MAX_F1_HORIZONTAL:
+            raise ValueError(f"ap_helper_pq: f1='device' needs the same number (<= {MAX_F1_HORIZONTAL}) of horizontal quads "
+                             "for every scan: padding rows are scored like any other row")
+        verts = np.zeros((b, k, 4, 3), np.float32)
+        gt = np.zeros((b, g, 4, 3), np.float32)
+        count = np.zeros((b,), np.int32)
+        total = np.zeros((b, 1), np.int64)
+        for i in range(b):
+            for arr, lst, n, name in ((verts, self.pred_corners[i], count, "predicted corners"),
+                                      (gt, self.gt_corners[i], total, "ground-truth corners")):
+                n[i] = len(lst)
+                if len(lst):
+                    arr[i, :len(lst)] = _exact_f32(np.stack([np.asarray(q) for q in lst]), name).reshape(-1, 4, 3)
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        d = [torch.from_numpy(a).to(dev) for a in (count, verts, gt, total)]
+        dh = torch.from_numpy(np.ascontiguousarray(np.stack(hz))).to(dev) if h else None
+        rows = torch.empty((b, 4), device=dev, dtype=_I32)
+        null = ctypes.c_void_p(0)
+        _ext._run(_lib.omnipq_layout_f1, rows, b, k, _ext._ptr(d[0]), _ext._ptr(d[1]), g, _ext._ptr(d[2]), _ext._ptr(d[3]), 1,
+                  h, null if dh is None else _ext._ptr(dh), SAME_THRES, _ext._ptr(rows), null)
+        sums = rows.cpu().numpy().astype(np.int64).sum(0)
+        counts.update(zip(F1_KEYS, (int(v) for v in sums)), scans=b)
+        return counts
